@@ -94,7 +94,9 @@ __device__ __forceinline__ bf16x8 frag_kc(const unsigned char* lds, int row, int
     return *reinterpret_cast<const bf16x8*>(lds + row * 128 + ((ch ^ swz(row)) << 4));
 }
 
-template <bool A_KC, bool B_KC, bool ROWSUM>
+// R32 (forward form, ecamp_gemm_res32): the epilogue adds an f32 residual and stores f32 -- the residual linear layers of the f32 residual
+// stream where the persistent kernels do not apply
+template <bool A_KC, bool B_KC, bool ROWSUM, bool R32 = false>
 __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmArgs g) {
     constexpr int TILE_BYTES = 64 * OC_PITCH;  // >= BM*BK*2: one size fits both operand layouts
     __shared__ __attribute__((aligned(16))) unsigned char lds[2 * TILE_BYTES];
@@ -174,7 +176,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmArgs g) {
     for (int tm = 0; tm < 4; ++tm)
 #pragma unroll
         for (int tn = 0; tn < 4; ++tn)
-            epilogue4<bf16_t>(g, m0 + wm + tm * 16 + lrow, n0 + wn + tn * 16 + 4 * lk, acc[tm][tn], blockIdx.z);
+            epilogue4<bf16_t, R32>(g, m0 + wm + tm * 16 + lrow, n0 + wn + tn * 16 + 4 * lk, acc[tm][tn], blockIdx.z);
     if (do_rowsum && lk == 0) {  // every row of the ones-product is the same sum; lane (lk = 0, r = 0) owns column lrow
         const float al = g.alpha_dev_out ? g.alpha_out * g.alpha_dev_out[0] : g.alpha_out;
 #pragma unroll
@@ -704,8 +706,9 @@ static int q8_env() {
     static const int v = getenv("ECAMP_GEMM_Q8") ? atoi(getenv("ECAMP_GEMM_Q8")) : -1;
     return g_q8_mode != -2 ? g_q8_mode : v;
 }
-// epilogue variant of a call (-1: none fits)
-static int q8_epi(const float* bias, const void* residual, const void* pre_out, const void* gmul, int act, int out_f32) {
+// epilogue variant of a call (-1: none fits); res32: the residual is f32 (ecamp_gemm_res32)
+static int q8_epi(const float* bias, const void* residual, const void* pre_out, const void* gmul, int act, int out_f32, bool res32) {
+    if (res32) return (out_f32 && residual && !pre_out && !gmul && !act) ? 5 : -1;
     if (out_f32) return (!bias && !residual && !pre_out && !gmul && !act) ? 4 : -1;
     if (gmul) return (!bias && !pre_out && (act == 0 || act == 2)) ? 3 : -1;
     if (pre_out || act) return (pre_out && (act == 1 || act == 2) && !residual) ? 1 : -1;
@@ -725,7 +728,8 @@ static int q8_sch() {
 static q8_fn q8_pick(int a_kc, int b_kc, int epi, bool rowsum) {
     const int sch = q8_sch();
 #define Q8S(A, B, E, R) ((q8_fn)gemm_bf16_q8_kernel<A, B, E, 0, R, 1>)
-    if (a_kc && b_kc && (sch & 1)) return epi == 0 ? Q8S(true, true, 0, false) : epi == 1 ? Q8S(true, true, 1, false) : epi == 2 ? Q8S(true, true, 2, false) : (q8_fn) nullptr;
+    if (a_kc && b_kc && (sch & 1)) return epi == 0 ? Q8S(true, true, 0, false) : epi == 1 ? Q8S(true, true, 1, false) : epi == 2 ? Q8S(true, true, 2, false) :
+                                          epi == 5 ? Q8S(true, true, 5, false) : (q8_fn) nullptr;
     if (a_kc && !b_kc && (sch & 2)) return epi == 0 ? Q8S(true, false, 0, false) : epi == 2 ? Q8S(true, false, 2, false) : epi == 3 ? Q8S(true, false, 3, false) : (q8_fn) nullptr;
     if (!a_kc && !b_kc && epi == 4 && (sch & 4)) return rowsum ? Q8S(false, false, 4, true) : Q8S(false, false, 4, false);
 #undef Q8S
@@ -736,9 +740,9 @@ static q8_fn q8_pick(int a_kc, int b_kc, int epi, bool rowsum) {
 }
 static bool q8_legal(const void* A, const void* B, const void* C, int64_t M, int64_t N, int64_t K, int a_kc, int64_t lda, int b_kc, int64_t ldb, int64_t ldc,
                      const float* bias, const void* residual, int64_t ldr, const void* pre_out, int64_t ldp, const void* gmul, int64_t ldg, int act,
-                     int dtype, int out_f32, int split_k, const float* splitk_ws, const float* rowsum) {
+                     int dtype, int out_f32, int split_k, const float* splitk_ws, const float* rowsum, bool res32) {
     if (dtype != ECAMP_BF16) return false;
-    const int epi = q8_epi(bias, residual, pre_out, gmul, act, out_f32);
+    const int epi = q8_epi(bias, residual, pre_out, gmul, act, out_f32, res32);
     if (epi < 0 || !q8_pick(a_kc, b_kc, epi, rowsum != nullptr)) return false;
     if (split_k < 1) split_k = 1;
     if (split_k > 1 && epi != 4) return false;
@@ -752,11 +756,11 @@ static bool q8_legal(const void* A, const void* B, const void* C, int64_t M, int
     if ((a_kc ? M * lda : K * lda) * 2 > lim || (b_kc ? N * ldb : K * ldb) * 2 > lim) return false;
     if (!a_kc && M % 8) return false;
     if (split_k > 1) { if (!al16(splitk_ws) || (long)split_k * M * N * 4 > lim) return false; }
-    else if (ldc % 8 || M * ldc * (epi == 4 ? 4 : 2) > lim) return false;
+    else if (ldc % 8 || M * ldc * (epi >= 4 ? 4 : 2) > lim) return false;
     if (bias && !al16(bias)) return false;
     if (pre_out && (ldp % 8 || !al16(pre_out) || M * ldp * 2 > lim)) return false;
     if (gmul && (ldg % 8 || !al16(gmul) || M * ldg * 2 > lim)) return false;
-    if (residual && (ldr % 8 || !al16(residual) || M * ldr * 2 > lim)) return false;
+    if (residual && (ldr % 8 || !al16(residual) || M * ldr * (res32 ? 4 : 2) > lim)) return false;
     return true;
 }
 
@@ -778,6 +782,7 @@ static double q16_cost(int64_t M, int64_t N, int tn, int ncu) {
 }
 typedef void (*q16_fn)(GemmArgs);
 static q16_fn q16_pick(int b_kc, int epi, int nw) {
+    if (epi == 5) return b_kc ? (nw == 8 ? (q16_fn)gemm_bf16_q16_kernel<5, 8, true> : (q16_fn)gemm_bf16_q16_kernel<5, 6, true>) : (q16_fn) nullptr;
     if (b_kc) {
         if (nw == 8) return epi == 0 ? (q16_fn)gemm_bf16_q16_kernel<0, 8, true> : (q16_fn)gemm_bf16_q16_kernel<2, 8, true>;
         return epi == 0 ? (q16_fn)gemm_bf16_q16_kernel<0, 6, true> : (q16_fn)gemm_bf16_q16_kernel<2, 6, true>;
@@ -845,10 +850,11 @@ extern "C" int64_t ecamp_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K, i
     return split_k > 1 && M > 0 && N > 0 ? (int64_t)split_k * M * N * 4 : 0;
 }
 
-extern "C" int ecamp_gemm(const void* A, const void* B, void* C, int64_t M, int64_t N, int64_t K, int a_kc, int64_t lda,
-                          int b_kc, int64_t ldb, int64_t ldc, const float* bias, const void* residual, int64_t ldr,
-                          void* pre_out, int64_t ldp, const void* gmul, int64_t ldg, int act, float alpha, const float* alpha_dev, int dtype,
-                          int out_f32, int accumulate, int split_k, float* splitk_ws, float* rowsum, hipStream_t stream) {
+// ecamp_gemm, and (res32) ecamp_gemm_res32: the residual is f32 and so is C
+static int gemm_call(const void* A, const void* B, void* C, int64_t M, int64_t N, int64_t K, int a_kc, int64_t lda,
+                     int b_kc, int64_t ldb, int64_t ldc, const float* bias, const void* residual, int64_t ldr,
+                     void* pre_out, int64_t ldp, const void* gmul, int64_t ldg, int act, float alpha, const float* alpha_dev, int dtype,
+                     int out_f32, int accumulate, int split_k, float* splitk_ws, float* rowsum, hipStream_t stream, bool res32) {
     ECAMP_CHECK_ARG(A && B && C, "ecamp_gemm: null operand");
     ECAMP_CHECK_ARG(M > 0 && N > 0 && K > 0, "ecamp_gemm: bad shape %ld %ld %ld", (long)M, (long)N, (long)K);
     ECAMP_CHECK_ARG(dtype == ECAMP_F32 || dtype == ECAMP_BF16, "ecamp_gemm: bad dtype %d", dtype);
@@ -872,17 +878,17 @@ extern "C" int ecamp_gemm(const void* A, const void* B, void* C, int64_t M, int6
     // Row-contiguous forms whose [M, ld] operands pass 2 GB (the vocabulary projection at B = 512: 65536 x 30000 bf16) are run as
     // two calls over row halves, so that each half meets the 32-bit buffer offsets of the persistent kernels (q8_legal).
     if (a_kc && dtype == ECAMP_BF16 && split_k == 1 && !rowsum && M >= 512) {
-        const long lim = 0x7fffffffl, esz = out_f32 ? 4 : 2;
-        const bool big = M * ldc * esz > lim || M * lda * 2 > lim || (residual && M * ldr * 2 > lim) || (pre_out && M * ldp * 2 > lim) || (gmul && M * ldg * 2 > lim);
+        const long lim = 0x7fffffffl, esz = out_f32 ? 4 : 2, rsz = res32 ? 4 : 2;
+        const bool big = M * ldc * esz > lim || M * lda * 2 > lim || (residual && M * ldr * rsz > lim) || (pre_out && M * ldp * 2 > lim) || (gmul && M * ldg * 2 > lim);
         if (big) {
             const int64_t m1 = (M / 2 + 255) / 256 * 256;
             auto rows = [](const void* p, int64_t r, int64_t ld, int64_t es) { return p ? (const void*)((const char*)p + r * ld * es) : nullptr; };
-            int rc = ecamp_gemm(A, B, C, m1, N, K, a_kc, lda, b_kc, ldb, ldc, bias, residual, ldr, pre_out, ldp, gmul, ldg, act, alpha, alpha_dev, dtype,
-                                out_f32, accumulate, 1, nullptr, nullptr, stream);
+            int rc = gemm_call(A, B, C, m1, N, K, a_kc, lda, b_kc, ldb, ldc, bias, residual, ldr, pre_out, ldp, gmul, ldg, act, alpha, alpha_dev, dtype,
+                               out_f32, accumulate, 1, nullptr, nullptr, stream, res32);
             if (rc) return rc;
-            return ecamp_gemm(rows(A, m1, lda, 2), B, (void*)rows(C, m1, ldc, esz), M - m1, N, K, a_kc, lda, b_kc, ldb, ldc, bias, rows(residual, m1, ldr, 2), ldr,
-                              (void*)rows(pre_out, m1, ldp, 2), ldp, rows(gmul, m1, ldg, 2), ldg, act, alpha, alpha_dev, dtype, out_f32, accumulate, 1, nullptr,
-                              nullptr, stream);
+            return gemm_call(rows(A, m1, lda, 2), B, (void*)rows(C, m1, ldc, esz), M - m1, N, K, a_kc, lda, b_kc, ldb, ldc, bias, rows(residual, m1, ldr, rsz), ldr,
+                             (void*)rows(pre_out, m1, ldp, 2), ldp, rows(gmul, m1, ldg, 2), ldg, act, alpha, alpha_dev, dtype, out_f32, accumulate, 1, nullptr,
+                             nullptr, stream, res32);
         }
     }
     // ... and the weight-gradient form whose [K, ld] operands pass 2 GB as two calls over halves of the contraction, the second accumulating
@@ -890,11 +896,11 @@ extern "C" int ecamp_gemm(const void* A, const void* B, void* C, int64_t M, int6
         const long lim = 0x7fffffffl;
         if (K * lda * 2 > lim || K * ldb * 2 > lim) {
             const int64_t k1 = (K / 2 + 255) / 256 * 256;
-            int rc = ecamp_gemm(A, B, C, M, N, k1, a_kc, lda, b_kc, ldb, ldc, bias, residual, ldr, pre_out, ldp, gmul, ldg, act, alpha, alpha_dev, dtype, out_f32,
-                                accumulate, split_k, splitk_ws, rowsum, stream);
+            int rc = gemm_call(A, B, C, M, N, k1, a_kc, lda, b_kc, ldb, ldc, bias, residual, ldr, pre_out, ldp, gmul, ldg, act, alpha, alpha_dev, dtype, out_f32,
+                               accumulate, split_k, splitk_ws, rowsum, stream, res32);
             if (rc) return rc;
-            return ecamp_gemm((const char*)A + k1 * lda * 2, (const char*)B + k1 * ldb * 2, C, M, N, K - k1, a_kc, lda, b_kc, ldb, ldc, bias, residual, ldr, pre_out, ldp,
-                              gmul, ldg, act, alpha, alpha_dev, dtype, out_f32, 1, split_k, splitk_ws, rowsum, stream);
+            return gemm_call((const char*)A + k1 * lda * 2, (const char*)B + k1 * ldb * 2, C, M, N, K - k1, a_kc, lda, b_kc, ldb, ldc, bias, residual, ldr, pre_out, ldp,
+                             gmul, ldg, act, alpha, alpha_dev, dtype, out_f32, 1, split_k, splitk_ws, rowsum, stream, res32);
         }
     }
 
@@ -925,11 +931,11 @@ extern "C" int ecamp_gemm(const void* A, const void* B, void* C, int64_t M, int6
         const int q8m = q8_env();
         const long items8 = (long)ceil_div(M, 256) * ceil_div(N, 256) * split_k;
         if (q8m != 0 && (q8m == 2 || items8 >= q8_min_items() || q16_mode() == 3) && (a_kc || b_kc || g_p8_wgrad) &&
-            q8_legal(A, B, C, M, N, K, a_kc, lda, b_kc, ldb, ldc, bias, residual, ldr, pre_out, ldp, gmul, ldg, act, dtype, g.out_f32, split_k, splitk_ws, rowsum)) {
-            const int epi = q8_epi(bias, residual, pre_out, gmul, act, g.out_f32);
+            q8_legal(A, B, C, M, N, K, a_kc, lda, b_kc, ldb, ldc, bias, residual, ldr, pre_out, ldp, gmul, ldg, act, dtype, g.out_f32, split_k, splitk_ws, rowsum, res32)) {
+            const int epi = q8_epi(bias, residual, pre_out, gmul, act, g.out_f32, res32);
             {   // Q16: forward / data-gradient forms with a plain, bias or residual epilogue (same legality as Q8: 16-B alignment, < 2 GB)
                 const int m16 = q16_mode(), ncu16 = p8_num_cu();
-                if (m16 > 0 && a_kc && (epi == 0 || epi == 2) && split_k == 1 && !rowsum && (b_kc || ldb % 8 == 0)) {
+                if (m16 > 0 && a_kc && (epi == 0 || epi == 2 || epi == 5) && split_k == 1 && !rowsum && (b_kc || ldb % 8 == 0)) {
                     const double c256 = q16_cost(M, N, 256, ncu16), c192 = q16_cost(M, N, 192, ncu16);
                     // (the 192-column tile only where it removes a good part of a round: the report side's qkv projection -- 6.0 rounds of
                     // 3/4-size tiles against 4.5 -> 5 -- measured 8 % SLOWER inside the step, profiles/r05_gemm_in_step_vs_lab.txt)
@@ -1023,7 +1029,8 @@ extern "C" int ecamp_gemm(const void* A, const void* B, void* C, int64_t M, int6
         snprintf(tag, sizeof tag, "t128:%c:e-:%ld:%ld:%ld:s%d", a_kc && b_kc ? 'f' : a_kc ? 'd' : 'w', (long)M, (long)N, (long)K, split_k);
         ecamp_prof_begin(dtype == ECAMP_BF16 ? ECAMP_PROF_GEMM_BF16 : ECAMP_PROF_GEMM_F32, 2.0 * (double)M * (double)N * (double)K, stream, tag);
     }
-    if (dtype == ECAMP_BF16) LAUNCH(gemm_bf16_kernel); else LAUNCH(gemm_f32_kernel);
+    if (res32) hipLaunchKernelGGL((gemm_bf16_kernel<true, true, false, true>), grid, block, 0, stream, g);
+    else if (dtype == ECAMP_BF16) LAUNCH(gemm_bf16_kernel); else LAUNCH(gemm_f32_kernel);
 #undef LAUNCH
     if (split_k > 1) {
         long n4 = M * N / 4;
@@ -1035,6 +1042,24 @@ extern "C" int ecamp_gemm(const void* A, const void* B, void* C, int64_t M, int6
     if (prof) ecamp_prof_end(stream);
     ECAMP_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int ecamp_gemm(const void* A, const void* B, void* C, int64_t M, int64_t N, int64_t K, int a_kc, int64_t lda,
+                          int b_kc, int64_t ldb, int64_t ldc, const float* bias, const void* residual, int64_t ldr,
+                          void* pre_out, int64_t ldp, const void* gmul, int64_t ldg, int act, float alpha, const float* alpha_dev, int dtype,
+                          int out_f32, int accumulate, int split_k, float* splitk_ws, float* rowsum, hipStream_t stream) {
+    return gemm_call(A, B, C, M, N, K, a_kc, lda, b_kc, ldb, ldc, bias, residual, ldr, pre_out, ldp, gmul, ldg, act, alpha, alpha_dev, dtype, out_f32,
+                     accumulate, split_k, splitk_ws, rowsum, stream, false);
+}
+
+extern "C" int ecamp_gemm_res32(const void* A, const void* B, float* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
+                                const float* bias, const float* residual, int64_t ldr, int dtype, hipStream_t stream) {
+    ECAMP_CHECK_ARG(dtype == ECAMP_BF16, "ecamp_gemm_res32: 16-bit operands (dtype 1) expected, got %d", dtype);
+    ECAMP_CHECK_ARG(residual && ldr >= N && ldc >= N && ldr % 4 == 0 && ldc % 4 == 0, "ecamp_gemm_res32: f32 residual [M, ldr >= N] and output [M, ldc >= N], "
+                    "leading dimensions multiples of 4");
+    ECAMP_CHECK_ARG((reinterpret_cast<uintptr_t>(residual) & 15) == 0 && (reinterpret_cast<uintptr_t>(C) & 15) == 0, "ecamp_gemm_res32: 16-B aligned residual and output");
+    return gemm_call(A, B, C, M, N, K, 1, lda, 1, ldb, ldc, bias, residual, ldr, nullptr, 0, nullptr, 0, 0, 1.0f, nullptr, dtype, 1, 0, 1, nullptr,
+                     nullptr, stream, true);
 }
 
 // =============================================================================================

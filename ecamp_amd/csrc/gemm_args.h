@@ -67,7 +67,8 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
 }
 
-template <typename T>
+// R32: the residual is f32 (the f32 residual stream, ecamp_gemm_res32; out_f32 is set with it)
+template <typename T, bool R32 = false>
 __device__ __forceinline__ void epilogue4(const GemmArgs& g, int m, int n0, f32x4 acc, int z) {
     if (m >= g.M || n0 >= g.N) return;
     const float al = g.alpha_dev ? g.alpha * g.alpha_dev[0] : g.alpha;
@@ -96,7 +97,8 @@ __device__ __forceinline__ void epilogue4(const GemmArgs& g, int m, int n0, f32x
     }
     if (g.residual) {
         float p[4];
-        ld4<T>(reinterpret_cast<const T*>(g.residual) + (long)m * g.ldr + n0, p);
+        if constexpr (R32) ld4<float>(reinterpret_cast<const float*>(g.residual) + (long)m * g.ldr + n0, p);
+        else ld4<T>(reinterpret_cast<const T*>(g.residual) + (long)m * g.ldr + n0, p);
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] += p[r];
     }

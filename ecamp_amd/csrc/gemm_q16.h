@@ -58,7 +58,7 @@ template <> struct Q16FragN<false> {
     }
 };
 
-// EPI: 0 bf16 C = alpha*acc (+bias)   2 ... + residual.   NW: MFMA tiles per wave along N (8: 256-column tile, 6: 192-column tile).
+// EPI: 0 bf16 C = alpha*acc (+bias)   2 ... + residual   5 f32 C = alpha*acc (+bias) + f32 residual (the f32 residual stream).   NW: MFMA tiles per wave along N (8: 256-column tile, 6: 192-column tile).
 // B_KC: the N-side operand is contraction-contiguous (forward form) or strided (data-gradient form).
 template <int EPI, int NW, bool B_KC, int DBG = 0>   // DBG (lab only): 1 no MFMA, 2 no DMA, 4 no fragment reads, 8 conflict-free (wrong) transpose reads
 __device__ __forceinline__ void q16_body(const GemmArgs& g) {
@@ -172,9 +172,10 @@ __device__ __forceinline__ void q16_body(const GemmArgs& g) {
 
     // ---- epilogue: MFMA tile pair (2 p, 2 p + 1) of M tile i = 16 rows x 32 columns; a lane holds row l15 and the eight columns 8 lq .. 8 lq + 7
     const long ldo = g.ldc;
-    const __amdgpu_buffer_rsrc_t rC = __builtin_amdgcn_make_buffer_rsrc(g.C, 0, (int)(unsigned)((long)g.M * ldo * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rR = __builtin_amdgcn_make_buffer_rsrc((void*)(EPI == 2 && g.residual ? g.residual : g.C), 0, (int)(unsigned)((long)g.M * g.ldr * 2), 0x00020000);
-    const unsigned lane_o = (unsigned)((l15 * ldo + 8 * lq) * 2), lane_r = (unsigned)((l15 * g.ldr + 8 * lq) * 2);
+    constexpr int ESZ = EPI == 5 ? 4 : 2;   // bytes per element of C and of the residual
+    const __amdgpu_buffer_rsrc_t rC = __builtin_amdgcn_make_buffer_rsrc(g.C, 0, (int)(unsigned)((long)g.M * ldo * ESZ), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rR = __builtin_amdgcn_make_buffer_rsrc((void*)((EPI == 2 || EPI == 5) && g.residual ? g.residual : g.C), 0, (int)(unsigned)((long)g.M * g.ldr * ESZ), 0x00020000);
+    const unsigned lane_o = (unsigned)((l15 * ldo + 8 * lq) * ESZ), lane_r = (unsigned)((l15 * g.ldr + 8 * lq) * ESZ);
 #define Q16_SB() __builtin_amdgcn_sched_barrier(0)
     // 192-column tiles (the register budget allows it: 140-164 of 256 VGPRs): the bias of the wave's 96 columns, per lane the 3 x 8 values
     // it adds, is requested ONCE per output tile by six 16-B loads at the head of the tile's first K tile and landed by that K tile's
@@ -237,14 +238,15 @@ __device__ __forceinline__ void q16_body(const GemmArgs& g) {
             }
         }
         unsigned uo[8];
-        q8_u32x4 qr[8];
+        q8_u32x4 qr[8], qr2[8];   // (qr2: the second 16 B of an f32 residual)
 #pragma unroll
         for (int I = 0; I < 8; ++I) {
             const int mb = tm0 + wr * 128 + I * 16;
-            uo[I] = oob ? 0x80000000u : (unsigned)(((long)mb * ldo + nb) * 2) + lane_o;
-            if (EPI == 2) {
-                const unsigned ur = oob ? 0x80000000u : (unsigned)(((long)mb * g.ldr + nb) * 2) + lane_r;
+            uo[I] = oob ? 0x80000000u : (unsigned)(((long)mb * ldo + nb) * ESZ) + lane_o;
+            if (EPI == 2 || EPI == 5) {
+                const unsigned ur = oob ? 0x80000000u : (unsigned)(((long)mb * g.ldr + nb) * ESZ) + lane_r;
                 qr[I] = __builtin_amdgcn_raw_buffer_load_b128(rR, ur, 0, 0);
+                if (EPI == 5) qr2[I] = __builtin_amdgcn_raw_buffer_load_b128(rR, ur + 16, 0, 0);
             }
         }
         Q16_SB();
@@ -262,7 +264,14 @@ __device__ __forceinline__ void q16_body(const GemmArgs& g) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) { v[2 * r] += h16_lo(qr[I][r]); v[2 * r + 1] += h16_hi(qr[I][r]); }
             }
-            __builtin_amdgcn_raw_buffer_store_b128(q8_pack8(v), rC, uo[I], 0, 0);
+            if (EPI == 5) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { v[r] += __uint_as_float(qr[I][r]); v[4 + r] += __uint_as_float(qr2[I][r]); }
+                __builtin_amdgcn_raw_buffer_store_b128((q8_u32x4){__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])}, rC, uo[I], 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128((q8_u32x4){__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7])}, rC, uo[I] + 16, 0, 0);
+            } else {
+                __builtin_amdgcn_raw_buffer_store_b128(q8_pack8(v), rC, uo[I], 0, 0);
+            }
             Q16_SB();
         }
     };

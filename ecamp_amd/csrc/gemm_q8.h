@@ -154,6 +154,7 @@ __device__ __forceinline__ void q8_wait2(Q8Frag<true> (&)[2]) {}
 // epilogue can do -- with every option tested at run time the epilogue's branches push the kernel over its 256 registers:
 //   0  bf16 C = alpha*acc (+bias)            1  ... + save pre-activation + exact GELU        2  ... + residual
 //   3  bf16 C = alpha*acc * gelu'(gmul) (+residual)                                            4  f32: split-K slab, or C (+= old)
+//   5  f32 C = alpha*acc (+bias) + f32 residual (the f32 residual stream: ecamp_gemm_res32)
 typedef unsigned int q8_u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ q8_u32x4 q8_pack8(const float (&v)[8]) {
@@ -471,7 +472,7 @@ __device__ __forceinline__ void q8_body(const GemmArgs& g, const Q8Group& GR) {
 
     // ---- epilogue ---------------------------------------------------------------------------------------------------------------
     // buffer descriptors of the outputs (kernel constants; every byte offset fits 32 bits, checked by the host)
-    const int esz = EPI == 4 ? 4 : 2;
+    const int esz = (EPI == 4 || EPI == 5) ? 4 : 2;
     const long ldo = (EPI == 4 && g.partial) ? (long)g.N : g.ldc;
     const __amdgpu_buffer_rsrc_t rC = __builtin_amdgcn_make_buffer_rsrc(
         (EPI == 4 && g.partial) ? (void*)g.partial : g.C, 0,
@@ -482,10 +483,10 @@ __device__ __forceinline__ void q8_body(const GemmArgs& g, const Q8Group& GR) {
     const unsigned lane_o = (unsigned)((l31 * ldo + 8 * lh) * esz);          // lane part of an output offset
     const unsigned lane_p = (unsigned)((l31 * g.ldp + 8 * lh) * 2);
     const unsigned lane_g = (unsigned)((l31 * g.ldg + 8 * lh) * 2);
-    const unsigned lane_r = (unsigned)((l31 * g.ldr + 8 * lh) * 2);
+    const unsigned lane_r = (unsigned)((l31 * g.ldr + 8 * lh) * (EPI == 5 ? 4 : 2));
     const __amdgpu_buffer_rsrc_t rG = __builtin_amdgcn_make_buffer_rsrc((void*)(EPI == 3 ? g.gmul : g.C), 0, (int)(unsigned)((long)g.M * g.ldg * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rR = __builtin_amdgcn_make_buffer_rsrc((void*)((EPI == 2 || EPI == 3) && g.residual ? g.residual : g.C), 0,
-                                                                        (int)(unsigned)((long)g.M * g.ldr * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rR = __builtin_amdgcn_make_buffer_rsrc((void*)((EPI == 2 || EPI == 3 || EPI == 5) && g.residual ? g.residual : g.C), 0,
+                                                                        (int)(unsigned)((long)g.M * g.ldr * (EPI == 5 ? 4 : 2)), 0x00020000);
     // Bias of the wave's 64 output columns, per lane the 4 x 8 values it adds (NH, group of 8, half): requested ONCE per output tile by
     // eight 16-B loads behind the previous tile's epilogue and landed by the first K tile's counted DMA wait (they are older than the
     // parts that wait leaves in flight).  Round 5: the epilogue used to fetch them per quadrant through scalar loads -- four exposed
@@ -494,7 +495,7 @@ __device__ __forceinline__ void q8_body(const GemmArgs& g, const Q8Group& GR) {
     // a vector load it tracks; columns past N read 0 (descriptor bounds; N % 8 == 0).
     q8_u32x4 bq[2][2][2];
     typedef unsigned q8_u32x4s __attribute__((ext_vector_type(4)));
-    constexpr bool HAS_BIAS = (EPI <= 2) && !ITEMS;
+    constexpr bool HAS_BIAS = (EPI <= 2 || EPI == 5) && !ITEMS;
     const unsigned bias_lane = (unsigned)((wc * 64 + 8 * lh) * 4);
     auto bias_request = [&](int tn0) __attribute__((always_inline)) {
         if constexpr (HAS_BIAS) {
@@ -587,6 +588,7 @@ __device__ __forceinline__ void q8_body(const GemmArgs& g, const Q8Group& GR) {
                 if (EPI == 1) up[tm][gq] = oob ? 0x80000000u : (unsigned)((row * g.ldp + col) * 2) + lane_p;
                 if (EPI == 3) ug[tm][gq] = oob ? 0x80000000u : (unsigned)((row * g.ldg + col) * 2) + lane_g;
                 if (EPI == 2 || EPI == 3) ur[tm][gq] = oob ? 0x80000000u : (unsigned)((row * g.ldr + col) * 2) + lane_r;
+                if (EPI == 5) ur[tm][gq] = oob ? 0x80000000u : (unsigned)((row * g.ldr + col) * 4) + lane_r;
             }
         // e4m3 form with the GELU epilogue: the e4m3 copy of the output for the next GEMM (8 bytes per lane and group)
         float q8_inv = 0.f;
@@ -603,6 +605,11 @@ __device__ __forceinline__ void q8_body(const GemmArgs& g, const Q8Group& GR) {
             for (int gq = 0; gq < 2; ++gq) {
                 if (EPI == 3) qg[tm][gq] = __builtin_amdgcn_raw_buffer_load_b128(rG, ug[tm][gq], 0, 0);
                 if (EPI == 2 || (EPI == 3 && g.residual)) qr[tm][gq] = __builtin_amdgcn_raw_buffer_load_b128(rR, ur[tm][gq], 0, 0);
+                if (EPI == 5) {   // the f32 residual, 32 bytes per lane and group, read once: non-temporal (aux 2) -- which also keeps these eight
+                    // loads of 32 registers apart from a bias request in the eyes of tools/check_isa.py
+                    qo[tm][gq][0] = __builtin_amdgcn_raw_buffer_load_b128(rR, ur[tm][gq], 0, 2);
+                    qo[tm][gq][1] = __builtin_amdgcn_raw_buffer_load_b128(rR, ur[tm][gq] + 16, 0, 2);
+                }
                 if (EPI == 4 && !g.partial && g.accumulate) {
                     qo[tm][gq][0] = __builtin_amdgcn_raw_buffer_load_b128(rC, uo[tm][gq], 0, 0);
                     qo[tm][gq][1] = __builtin_amdgcn_raw_buffer_load_b128(rC, uo[tm][gq] + 16, 0, 0);
@@ -615,7 +622,7 @@ __device__ __forceinline__ void q8_body(const GemmArgs& g, const Q8Group& GR) {
                 float v[8];
 #pragma unroll
                 for (int r = 0; r < 8; ++r) v[r] = acc[2 * MH + tm][NH][8 * gq + r] * al;
-                if (EPI <= 2 && g.bias) {
+                if ((EPI <= 2 || EPI == 5) && g.bias) {
 #pragma unroll
                     for (int r = 0; r < 8; ++r) v[r] += bias[gq][r];
                 }
@@ -673,8 +680,12 @@ __device__ __forceinline__ void q8_body(const GemmArgs& g, const Q8Group& GR) {
                         v[2 * r + 1] += h16_hi(qr[tm][gq][r]);
                     }
                 }
-                if (EPI == 4) {
-                    if (!g.partial && g.accumulate) {
+                if (EPI == 5) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) { v[r] += __uint_as_float(qo[tm][gq][0][r]); v[4 + r] += __uint_as_float(qo[tm][gq][1][r]); }
+                }
+                if (EPI == 4 || EPI == 5) {
+                    if (EPI == 4 && !g.partial && g.accumulate) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) { v[r] += __uint_as_float(qo[tm][gq][0][r]); v[4 + r] += __uint_as_float(qo[tm][gq][1][r]); }
                     }

@@ -14,6 +14,12 @@ template <> struct LnVec<float, 4> {
     static __device__ __forceinline__ void cvt(const float4& v, float (&o)[4]) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
     static __device__ __forceinline__ float4 pack(const float (&o)[4]) { return make_float4(o[0], o[1], o[2], o[3]); }
 };
+template <> struct LnVec<float, 8> {   // (the f32 residual stream read beside 8-wide 16-bit rows: two 16-B accesses)
+    struct raw_t { float4 a, b; };
+    static __device__ __forceinline__ void cvt(const raw_t& v, float (&o)[8]) {
+        o[0] = v.a.x; o[1] = v.a.y; o[2] = v.a.z; o[3] = v.a.w; o[4] = v.b.x; o[5] = v.b.y; o[6] = v.b.z; o[7] = v.b.w;
+    }
+};
 template <> struct LnVec<bf16_t, 4> {
     typedef uint2 raw_t;
     static __device__ __forceinline__ void cvt(const uint2& v, float (&o)[4]) {
@@ -46,6 +52,12 @@ __device__ __forceinline__ void ln_dropout(uint64_t seed, uint64_t offset, long 
     }
 }
 
+// Element types of the kernels' rows.  T: f32 or the 16-bit format, every row of that type; ln_z32<bf16_t>: the f32 residual stream
+// (ECAMP(f32_residual=True)) -- the LayerNorm input (x forward, z backward) is f32, every other row 16-bit
+template <typename T> struct ln_z32 {};
+template <typename T> struct LnRow { typedef T io; typedef T z; };
+template <typename T> struct LnRow<ln_z32<T>> { typedef T io; typedef float z; };
+
 template <typename T, int IT, int VEC>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, const T* __restrict__ res, T* __restrict__ zout,
                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -53,7 +65,10 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
                                                      long rows, int cols, float eps, float drop_p, uint64_t seed,
                                                      uint64_t offset, unsigned char* __restrict__ q8, const float* __restrict__ q8_scale,
                                                      float* __restrict__ q8_amax) {
-    typedef LnVec<T, VEC> V;
+    typedef typename LnRow<T>::io TY;
+    typedef typename LnRow<T>::z TX;
+    typedef LnVec<TY, VEC> V;
+    typedef LnVec<TX, VEC> VX;
     typedef typename V::raw_t raw_t;
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -65,13 +80,14 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
     const int nv = cols / VEC;
     const float inv_keep = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
     // every load of the row is issued before the first value is consumed
-    raw_t rx[IT], rr[IT];
+    typename VX::raw_t rx[IT];
+    raw_t rr[IT];
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
         const int c = lane + 64 * i;
         if (c < nv) {
-            rx[i] = *reinterpret_cast<const raw_t*>(x + row * cols + c * VEC);
-            if (res) rr[i] = *reinterpret_cast<const raw_t*>(res + row * cols + c * VEC);
+            rx[i] = *reinterpret_cast<const typename VX::raw_t*>(reinterpret_cast<const TX*>(x) + row * cols + c * VEC);
+            if (res) rr[i] = *reinterpret_cast<const raw_t*>(reinterpret_cast<const TY*>(res) + row * cols + c * VEC);
         }
     }
     float v[IT][VEC];
@@ -80,7 +96,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
     for (int i = 0; i < IT; ++i) {
         const int c = lane + 64 * i;
         if (c < nv) {
-            V::cvt(rx[i], v[i]);
+            VX::cvt(rx[i], v[i]);
             if (drop_p > 0.f) {
                 float m[VEC];
                 ln_dropout<VEC>(seed, offset, row, nv, c, drop_p, inv_keep, m);
@@ -95,8 +111,8 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
             }
             if (zout) {
 #pragma unroll
-                for (int r = 0; r < VEC; ++r) v[i][r] = rnd<T>(v[i][r]);
-                *reinterpret_cast<raw_t*>(zout + row * cols + c * VEC) = V::pack(v[i]);
+                for (int r = 0; r < VEC; ++r) v[i][r] = rnd<TY>(v[i][r]);
+                *reinterpret_cast<raw_t*>(reinterpret_cast<TY*>(zout) + row * cols + c * VEC) = V::pack(v[i]);
             }
 #pragma unroll
             for (int r = 0; r < VEC; r += 4) s += (v[i][r] + v[i][r + 1]) + (v[i][r + 2] + v[i][r + 3]);
@@ -137,7 +153,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
                 o[4 * k + 2] = (v[i][4 * k + 2] - mu) * rs * g.z + b.z;
                 o[4 * k + 3] = (v[i][4 * k + 3] - mu) * rs * g.w + b.w;
             }
-            *reinterpret_cast<raw_t*>(y + row * cols + c * VEC) = V::pack(o);
+            *reinterpret_cast<raw_t*>(reinterpret_cast<TY*>(y) + row * cols + c * VEC) = V::pack(o);
             if (q8) {
                 unsigned int w[VEC / 4];
 #pragma unroll
@@ -145,7 +161,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
                     float u[4];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const float yr = rnd<T>(o[4 * k + r]);
+                        const float yr = rnd<TY>(o[4 * k + r]);
                         q8_max = fmaxf(q8_max, fabsf(yr));
                         u[r] = fminf(fmaxf(yr * q8_inv, -448.f), 448.f);
                     }
@@ -185,8 +201,12 @@ __global__ __launch_bounds__(LN_BWD_WAVES * 64) void ln_bwd_kernel(const T* __re
                                                      T* __restrict__ dz, T* __restrict__ dxdrop, float* __restrict__ dgamma,
                                                      float* __restrict__ dbeta, long rows, int cols, float drop_p,
                                                      uint64_t seed, uint64_t offset) {
-    typedef LnVec<T, VEC> V;
+    typedef typename LnRow<T>::io TY;
+    typedef typename LnRow<T>::z TZ;
+    typedef LnVec<TY, VEC> V;
+    typedef LnVec<TZ, VEC> VZ;
     typedef typename V::raw_t raw_t;
+    typedef typename VZ::raw_t zraw_t;
     extern __shared__ __attribute__((aligned(16))) float sh[];  // [8][cols]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nv = cols / VEC;
@@ -218,7 +238,9 @@ __global__ __launch_bounds__(LN_BWD_WAVES * 64) void ln_bwd_kernel(const T* __re
     // rows are software-pipelined: the loads of a wave's NEXT row are in flight while the current row is reduced, normalised and
     // stored (a row is a dependent chain load -> two wave reductions -> store; without the prefetch a CU has no load outstanding
     // for about half of it)
-    raw_t rdy[IT], rz[IT], rq[IT];
+    raw_t rdy[IT];
+    zraw_t rz[IT];
+    raw_t rq[IT];
     float nmu = 0.f, nrs = 0.f;
     const long stride = (long)gridDim.x * LN_BWD_WAVES;
     auto fetch = [&](long row) {
@@ -228,8 +250,8 @@ __global__ __launch_bounds__(LN_BWD_WAVES * 64) void ln_bwd_kernel(const T* __re
         for (int i = 0; i < IT; ++i) {
             const int c = lane + 64 * i;
             if (c < nv) {
-                rdy[i] = *reinterpret_cast<const raw_t*>(dy + ((unsigned)(row * cols) + (unsigned)(c * VEC)));
-                rz[i] = *reinterpret_cast<const raw_t*>(z + ((unsigned)(row * cols) + (unsigned)(c * VEC)));
+                rdy[i] = *reinterpret_cast<const raw_t*>(reinterpret_cast<const TY*>(dy) + ((unsigned)(row * cols) + (unsigned)(c * VEC)));
+                rz[i] = *reinterpret_cast<const zraw_t*>(reinterpret_cast<const TZ*>(z) + ((unsigned)(row * cols) + (unsigned)(c * VEC)));
             }
         }
     };
@@ -238,14 +260,15 @@ __global__ __launch_bounds__(LN_BWD_WAVES * 64) void ln_bwd_kernel(const T* __re
 #pragma unroll
         for (int i = 0; i < IT; ++i) {
             const int c = lane + 64 * i;
-            if (c < nv) rq[i] = *reinterpret_cast<const raw_t*>(dres + ((unsigned)(row * cols) + (unsigned)(c * VEC)));
+            if (c < nv) rq[i] = *reinterpret_cast<const raw_t*>(reinterpret_cast<const TY*>(dres) + ((unsigned)(row * cols) + (unsigned)(c * VEC)));
         }
     };
     long row = (long)blockIdx.x * LN_BWD_WAVES + wave;
     if (row < rows) { fetch(row); if (dres) fetch_q(row); }
     for (; row < rows; row += stride) {
         const float mu = nmu, rs = nrs;
-        raw_t cdy[IT], cz[IT];   // the current row, as it lies in memory
+        raw_t cdy[IT];   // the current row, as it lies in memory
+        zraw_t cz[IT];
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int i = 0; i < IT; ++i) {
@@ -254,7 +277,7 @@ __global__ __launch_bounds__(LN_BWD_WAVES * 64) void ln_bwd_kernel(const T* __re
             if (c < nv) {
                 float d[VEC], zz[VEC], gm[VEC];
                 V::cvt(cdy[i], d);
-                V::cvt(cz[i], zz);
+                VZ::cvt(cz[i], zz);
 #pragma unroll
                 for (int k = 0; k < VEC / 4; ++k) {
                     float g4[4];
@@ -280,7 +303,7 @@ __global__ __launch_bounds__(LN_BWD_WAVES * 64) void ln_bwd_kernel(const T* __re
             if (c < nv) {
                 float d[VEC], zz[VEC], o[VEC];
                 V::cvt(cdy[i], d);
-                V::cvt(cz[i], zz);
+                VZ::cvt(cz[i], zz);
 #pragma unroll
                 for (int k = 0; k < VEC / 4; ++k) {
                     float gm[4];
@@ -297,15 +320,15 @@ __global__ __launch_bounds__(LN_BWD_WAVES * 64) void ln_bwd_kernel(const T* __re
 #pragma unroll
                     for (int r = 0; r < VEC; ++r) o[r] += q[r];
                 }
-                *reinterpret_cast<raw_t*>(dz + ((unsigned)(row * cols) + (unsigned)(c * VEC))) = V::pack(o);
+                *reinterpret_cast<raw_t*>(reinterpret_cast<TY*>(dz) + ((unsigned)(row * cols) + (unsigned)(c * VEC))) = V::pack(o);
                 if (dxdrop) {
                     if (drop_p > 0.f) {
                         float m[VEC];
                         ln_dropout<VEC>(seed, offset, row, nv, c, drop_p, inv_keep, m);
 #pragma unroll
-                        for (int r = 0; r < VEC; ++r) o[r] = rnd<T>(o[r]) * m[r];
+                        for (int r = 0; r < VEC; ++r) o[r] = rnd<TY>(o[r]) * m[r];
                     }
-                    *reinterpret_cast<raw_t*>(dxdrop + ((unsigned)(row * cols) + (unsigned)(c * VEC))) = V::pack(o);
+                    *reinterpret_cast<raw_t*>(reinterpret_cast<TY*>(dxdrop) + ((unsigned)(row * cols) + (unsigned)(c * VEC))) = V::pack(o);
                 }
             }
         }
@@ -440,6 +463,63 @@ extern "C" int ecamp_layernorm_bwd(const void* dy, const void* z, const float* m
     if (dtype == ECAMP_F32) ln_bwd_launch<float>(dy, z, mean, rstd, gamma, dres_in, dz, dx_drop, dgamma, dbeta, rows, cols, drop_p, seed, offset, stream);
     else if (dtype == ECAMP_BF16) ln_bwd_launch<bf16_t>(dy, z, mean, rstd, gamma, dres_in, dz, dx_drop, dgamma, dbeta, rows, cols, drop_p, seed, offset, stream);
     else return ecamp_set_error(-1, "layernorm_bwd: bad dtype %d", dtype);
+    ECAMP_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- the f32 residual stream (ECAMP(f32_residual=True)): the LayerNorms that read it (timm Block norm1 / norm2, the encoder's `norm`, the
+// decoder's `decoder_norm`: model_ecamp.py:69,84,233-235,254-256) take f32 rows and leave a 16-bit y; their backward reads the f32 z.
+// The kernels above with T = ln_z32<bf16_t>, in the layouts ln_fwd_launch / ln_bwd_launch pick for 16-bit rows; no residual, dropout or e4m3 copy.
+extern "C" int ecamp_layernorm_fwd_x32(const float* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int64_t rows,
+                                       int32_t cols, float eps, int32_t dtype, hipStream_t stream) {
+    typedef ln_z32<bf16_t> T;
+    ECAMP_CHECK_ARG(x && gamma && beta && y && mean && rstd, "layernorm_fwd_x32: null pointer");
+    ECAMP_CHECK_ARG(cols % 4 == 0 && cols <= 2048 && rows > 0, "layernorm_fwd_x32: cols=%d must be a multiple of 4 and <= 2048", cols);
+    ECAMP_CHECK_ARG(dtype == ECAMP_BF16, "layernorm_fwd_x32: the output is 16-bit (dtype 1), got %d", dtype);
+    ECAMP_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 7) == 0, "layernorm_fwd_x32: x 16-B, y 8-B aligned");
+    dim3 grid(ceil_div(rows, 4)), block(256);
+#define L(IT_, V_) hipLaunchKernelGGL((ln_fwd_kernel<T, IT_, V_>), grid, block, 0, stream, (const T*)x, (const T*)nullptr, (T*)nullptr, gamma, beta, (T*)y, \
+                                      mean, rstd, (long)rows, cols, eps, 0.f, (uint64_t)0, (uint64_t)0, (unsigned char*)nullptr, (const float*)nullptr, (float*)nullptr)
+    if (cols % 8 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0) {   // 16-B stores of y (two 16-B loads of x per chunk)
+        const int it8 = ceil_div(cols / 8, 64);
+        if (it8 <= 1) L(1, 8); else if (it8 <= 2) L(2, 8); else L(4, 8);
+    } else {
+        const int it = ceil_div(cols / 4, 64);
+        if (it <= 1) L(1, 4); else if (it <= 2) L(2, 4); else if (it <= 3) L(3, 4); else if (it <= 4) L(4, 4); else L(8, 4);
+    }
+#undef L
+    ECAMP_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ecamp_layernorm_bwd_z32(const void* dy, const float* z, const float* mean, const float* rstd, const float* gamma, const void* dres_in,
+                                       void* dz, float* dgamma, float* dbeta, int64_t rows, int32_t cols, int32_t dtype, hipStream_t stream) {
+    typedef ln_z32<bf16_t> T;
+    ECAMP_CHECK_ARG(dy && z && mean && rstd && gamma && dz && dgamma && dbeta, "layernorm_bwd_z32: null pointer");
+    ECAMP_CHECK_ARG(cols % 4 == 0 && cols <= 2048 && rows > 0, "layernorm_bwd_z32: cols=%d must be a multiple of 4 and <= 2048", cols);
+    ECAMP_CHECK_ARG(rows * (int64_t)cols < (1ll << 30), "layernorm_bwd_z32: rows * cols must stay below 2^30 (32-bit element offsets)");
+    ECAMP_CHECK_ARG(dtype == ECAMP_BF16, "layernorm_bwd_z32: dy / dres / dz are 16-bit (dtype 1), got %d", dtype);
+    ECAMP_CHECK_ARG((reinterpret_cast<uintptr_t>(z) & 15) == 0, "layernorm_bwd_z32: z 16-B aligned");
+    size_t shm = (size_t)8 * cols * sizeof(float);
+    auto al16 = [](const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+#define L(IT_, V_, W_, G_)                                                                                               \
+    do {                                                                                                                 \
+        int nb = ceil_div(rows, W_);                                                                                     \
+        if (nb > 256) nb = 256;                                                                                          \
+        hipLaunchKernelGGL((ln_bwd_kernel<T, IT_, V_, W_, G_>), dim3(nb), dim3(W_ * 64), shm, stream, (const T*)dy, (const T*)z, mean, rstd, gamma, \
+                           (const T*)dres_in, (T*)dz, (T*)nullptr, dgamma, dbeta, (long)rows, cols, 0.f, (uint64_t)0, (uint64_t)0); \
+    } while (0)
+    bool done = false;
+    if (cols % 8 == 0 && cols <= 1024 && al16(dy) && al16(dres_in) && al16(dz)) {
+        const int it8 = ceil_div(cols / 8, 64);
+        if (it8 <= 1) { L(1, 8, 16, true); done = true; }
+        else if (cols > 768) { shm = (size_t)9 * cols * sizeof(float); L(2, 8, 12, false); done = true; }
+    }
+    if (!done) {
+        const int it = ceil_div(cols / 4, 64);
+        if (it <= 1) L(1, 4, 16, true); else if (it <= 2) L(2, 4, 16, true); else if (it <= 3) L(3, 4, 16, true); else if (it <= 4) L(4, 4, 16, true); else L(8, 4, 16, true);
+    }
+#undef L
     ECAMP_LAUNCH_CHECK();
     return 0;
 }

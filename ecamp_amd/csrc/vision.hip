@@ -325,6 +325,43 @@ extern "C" int ecamp_assemble_tokens(void* x, const float* cls, const float* pos
     return 0;
 }
 
+// the f32 residual stream (ECAMP(f32_residual=True)): the same tokens into a separate f32 tensor out[B, Lk+1, D] -- the 16-bit patch embedding
+// plus the f32 tables, autocast's `half conv output + f32 pos_embed -> f32` (model_ecamp.py:222,228-230)
+template <typename T>
+__global__ void assemble_tokens_x32_kernel(const T* __restrict__ x, float* __restrict__ out, const float* __restrict__ cls, const float* __restrict__ pos,
+                                           const int* __restrict__ ids_keep, long B, int Lk, int D4) {
+    const int Tt = Lk + 1;
+    long n = B * Tt * D4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        int d = (int)(i % D4);
+        long row = i / D4;
+        int t = (int)(row % Tt);
+        long b = row / Tt;
+        float v[4], q[4];
+        if (t == 0) {
+            ld4<float>(cls + d * 4, v);
+            ld4<float>(pos + d * 4, q);
+        } else {
+            ld4<T>(x + i * 4, v);
+            ld4<float>(pos + (long)(1 + ids_keep[b * Lk + t - 1]) * D4 * 4 + d * 4, q);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] += q[r];
+        st4<float>(out + i * 4, v);
+    }
+}
+extern "C" int ecamp_assemble_tokens_x32(const void* x, float* out, const float* cls, const float* pos, const int32_t* ids_keep, int64_t B, int32_t Lk,
+                                         int32_t D, int32_t dtype, hipStream_t stream) {
+    ECAMP_CHECK_ARG(x && out && cls && pos && ids_keep && D % 4 == 0, "assemble_tokens_x32: bad args");
+    ECAMP_CHECK_ARG(dtype == ECAMP_BF16, "assemble_tokens_x32: 16-bit patch embedding (dtype 1) expected, got %d", dtype);
+    long n = B * (Lk + 1) * (long)(D / 4);
+    int nb = (int)((n + 255) / 256);
+    if (nb > 8192) nb = 8192;
+    hipLaunchKernelGGL(assemble_tokens_x32_kernel<bf16_t>, dim3(nb), dim3(256), 0, stream, (const bf16_t*)x, out, cls, pos, ids_keep, (long)B, Lk, D / 4);
+    ECAMP_LAUNCH_CHECK();
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // K10  decoder un-shuffle (model_ecamp.py:245-251)
 //   fwd: xd[b,0] = y[b,0] + dpos[0] ; xd[b,1+j] = (r=ids_restore[b,j]) < Lk ? y[b,1+r] : mask_token) + dpos[1+j]
@@ -409,6 +446,42 @@ extern "C" int ecamp_unshuffle_fwd(const void* y, const int32_t* ids_restore, co
     if (nb > 8192) nb = 8192;
     if (dtype == ECAMP_F32) hipLaunchKernelGGL(unshuffle_fwd_kernel<float>, dim3(nb), dim3(256), 0, stream, (const float*)y, ids_restore, mask_token, dpos, (float*)xd, (long)B, L, Lk, D / 4);
     else hipLaunchKernelGGL(unshuffle_fwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, stream, (const bf16_t*)y, ids_restore, mask_token, dpos, (bf16_t*)xd, (long)B, L, Lk, D / 4);
+    ECAMP_LAUNCH_CHECK();
+    return 0;
+}
+// the f32 residual stream: xd f32 = (16-bit decoder_embed output | f32 mask token) + f32 decoder_pos_embed, autocast's promotion of
+// torch.cat([half, f32 mask tokens]) + f32 table (model_ecamp.py:245-251)
+template <typename T>
+__global__ void unshuffle_fwd_x32_kernel(const T* __restrict__ y, const int* __restrict__ ids_restore, const float* __restrict__ mtok,
+                                         const float* __restrict__ dpos, float* __restrict__ xd, long B, int L, int Lk, int D4) {
+    long n = B * (L + 1) * D4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        int d = (int)(i % D4);
+        long row = i / D4;
+        int t = (int)(row % (L + 1));
+        long b = row / (L + 1);
+        float v[4], q[4];
+        int src = 0;
+        if (t > 0) {
+            int r = ids_restore[b * L + t - 1];
+            src = r < Lk ? 1 + r : -1;
+        }
+        if (src >= 0) ld4<T>(y + ((b * (Lk + 1) + src) * (long)D4 + d) * 4, v);
+        else ld4<float>(mtok + d * 4, v);
+        ld4<float>(dpos + ((long)t * D4 + d) * 4, q);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] += q[r];
+        st4<float>(xd + i * 4, v);
+    }
+}
+extern "C" int ecamp_unshuffle_fwd_x32(const void* y, const int32_t* ids_restore, const float* mask_token, const float* dpos, float* xd,
+                                       int64_t B, int32_t L, int32_t Lk, int32_t D, int32_t dtype, hipStream_t stream) {
+    ECAMP_CHECK_ARG(y && ids_restore && mask_token && dpos && xd && D % 4 == 0, "unshuffle_fwd_x32: bad args");
+    ECAMP_CHECK_ARG(dtype == ECAMP_BF16, "unshuffle_fwd_x32: 16-bit decoder_embed output (dtype 1) expected, got %d", dtype);
+    long n = B * (L + 1) * (long)(D / 4);
+    int nb = (int)((n + 255) / 256);
+    if (nb > 8192) nb = 8192;
+    hipLaunchKernelGGL(unshuffle_fwd_x32_kernel<bf16_t>, dim3(nb), dim3(256), 0, stream, (const bf16_t*)y, ids_restore, mask_token, dpos, xd, (long)B, L, Lk, D / 4);
     ECAMP_LAUNCH_CHECK();
     return 0;
 }

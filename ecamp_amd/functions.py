@@ -125,6 +125,30 @@ def _vit_linear(m, x, lin, x8=None, next_w=None, **kw):
     return _dense(m, x, lin.weight, lin.bias.data, x8=x8, next_w=next_w, **kw)
 
 
+def f32_carrier(x32, dtype):
+    """The f32 residual stream (ECAMP(f32_residual=True)) as it crosses an autograd edge: a [M, D] view of `dtype` (the model's 16-bit
+    format) over the f32 rows' storage.  autograd converts a gradient to the dtype of the tensor it belongs to, and the gradient stream is
+    16-bit -- an f32 edge would put a cast kernel between every two stages.  Only f32_stream() reads a carrier's values."""
+    assert x32.dim() == 2 and x32.dtype == torch.float32 and x32.is_contiguous()
+    return x32.view(dtype)[:, 0::2]
+
+
+def f32_stream(x):
+    """The f32 rows behind a carrier made by f32_carrier (an f32 tensor is returned as it is)."""
+    if x.dtype == torch.float32:
+        return x
+    M, D = x.shape
+    assert x.stride() == (2 * D, 2) and x.storage_offset() % 2 == 0, "not an f32 residual-stream carrier"
+    return x.new_empty(0, dtype=torch.float32).set_(x.untyped_storage(), x.storage_offset() // 2, (M, D), (D, 1))
+
+
+def _ln_bwd(dy, z, mean, rstd, gamma, ggamma, gbeta, dres=None):
+    """layernorm_bwd of a ViT LayerNorm: its input z is f32 when it is the f32 residual stream, the gradients are 16-bit either way."""
+    if z.dtype != dy.dtype:
+        return ops.layernorm_bwd_z32(dy, z, mean, rstd, gamma, ggamma, gbeta, dres=dres)
+    return ops.layernorm_bwd(dy, z, mean, rstd, gamma, ggamma, gbeta, dres=dres)
+
+
 def _ln_q8(m, x, ln, weights, eps=None, **kw):
     """LayerNorm whose output feeds the dense layer of `weights`: -> (y, z, mean, rstd, y8 or None)."""
     site = _f8_site(m, x, weights)
@@ -150,7 +174,10 @@ class StemFn(torch.autograd.Function):
         cols = ops.im2col_gather(imgs, ids_keep, p, cd)
         pw = m.patch_embed.proj.weight
         x = ops.linear_fwd(cols, A.w(pw).view(D, -1), m.patch_embed.proj.bias.data)
-        ops.assemble_tokens_(x, m.cls_token.data, m.pos_embed.data, ids_keep, B, Lk, D)
+        if m.f32_residual:   # f32 tokens = 16-bit patch embedding + f32 position table (autocast: half conv + f32 pos_embed)
+            x = f32_carrier(ops.assemble_tokens_x32(x, m.cls_token.data, m.pos_embed.data, ids_keep, B, Lk, D), cd)
+        else:
+            ops.assemble_tokens_(x, m.cls_token.data, m.pos_embed.data, ids_keep, B, Lk, D)
         ctx.m, ctx.cols, ctx.Lk = m, cols, Lk
         ctx.mark_non_differentiable(imgs, mask, ids_restore, ids_keep)
         return x, imgs, mask, ids_restore, ids_keep
@@ -171,6 +198,8 @@ class StemFn(torch.autograd.Function):
 class VitBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, blk, m, B, T, heads):
+        if m.f32_residual:
+            return VitBlockFn._forward_f32(ctx, f32_stream(x), blk, m, B, T, heads)
         D = x.shape[1]
         hd = D // heads
         eps = blk.norm1.eps
@@ -187,6 +216,28 @@ class VitBlockFn(torch.autograd.Function):
         ctx.s = (x, mean1, rstd1, h, qkv, a, lse, x1, mean2, rstd2, h2, pre, u)
         ctx.cfg = (blk, m, B, T, heads)
         return x2
+
+    @staticmethod
+    def _forward_f32(ctx, x, blk, m, B, T, heads):
+        """The block on the f32 residual stream (ECAMP(f32_residual=True)): x, x1 and x2 are f32; the LayerNorms read them and write
+        16-bit GEMM inputs, the proj / fc2 epilogues add bias and residual to the f32 accumulator and store f32 (autocast's
+        `x + attn(norm1(x))` / `x + mlp(norm2(x))` with an f32 x, model_ecamp.py:233-234,254-255).  The backward is the common one."""
+        A, cd = m.arena, m.compute_dtype
+        D = x.shape[1]
+        hd = D // heads
+        h, _, mean1, rstd1 = ops.layernorm_fwd_x32(x, blk.norm1.weight.data, blk.norm1.bias.data, blk.norm1.eps, cd)
+        qkv = _vit_linear(m, h, blk.attn.qkv)
+        st = (T * 3 * D, 3 * D, hd)
+        flat = qkv.view(-1)
+        a, lse = ops.attn_fwd(flat, flat[D:], flat[2 * D:], B, heads, T, T, hd, st, st, st, hd ** -0.5)
+        a = a.view(B * T, D)
+        x1 = ops.linear_fwd_res32(a, A.w(blk.attn.proj.weight), blk.attn.proj.bias.data, x)
+        h2, _, mean2, rstd2 = ops.layernorm_fwd_x32(x1, blk.norm2.weight.data, blk.norm2.bias.data, blk.norm2.eps, cd)
+        u, pre = _vit_linear(m, h2, blk.mlp.fc1, act=m.gelu_act, save_pre=True)
+        x2 = ops.linear_fwd_res32(u, A.w(blk.mlp.fc2.weight), blk.mlp.fc2.bias.data, x1)
+        ctx.s = (x, mean1, rstd1, h, qkv, a, lse, x1, mean2, rstd2, h2, pre, u)
+        ctx.cfg = (blk, m, B, T, heads)
+        return f32_carrier(x2, cd)
 
     @staticmethod
     def backward(ctx, dx2):
@@ -211,7 +262,7 @@ class VitBlockFn(torch.autograd.Function):
         dpre = ops.linear_dgrad(dx2, A.w(fc2.weight), gmul=pre, gmul_is_grad=m.gelu_act == 2)
         _wgrad(A, dpre, h2, fc1.weight, gb=G(fc1.bias))
         dh2 = ops.linear_dgrad(dpre, A.w(fc1.weight))
-        dx1 = ops.layernorm_bwd(dh2, x1, mean2, rstd2, blk.norm2.weight.data, G(blk.norm2.weight), G(blk.norm2.bias), dres=dx2)
+        dx1 = _ln_bwd(dh2, x1, mean2, rstd2, blk.norm2.weight.data, G(blk.norm2.weight), G(blk.norm2.bias), dres=dx2)
         A.ready(fc2.weight, fc2.bias, fc1.weight, fc1.bias, blk.norm2.weight, blk.norm2.bias)
         _wgrad(A, dx1, a, proj.weight, gb=G(proj.bias))
         da = ops.linear_dgrad(dx1, A.w(proj.weight))
@@ -222,7 +273,7 @@ class VitBlockFn(torch.autograd.Function):
                      st, st, st, st, st, st, hd ** -0.5)
         _wgrad(A, dqkv, h, qk.weight, gb=G(qk.bias))
         dh = ops.linear_dgrad(dqkv, A.w(qk.weight))
-        dx = ops.layernorm_bwd(dh, x, mean1, rstd1, blk.norm1.weight.data, G(blk.norm1.weight), G(blk.norm1.bias), dres=dx1)
+        dx = _ln_bwd(dh, x, mean1, rstd1, blk.norm1.weight.data, G(blk.norm1.weight), G(blk.norm1.bias), dres=dx1)
         A.ready(proj.weight, proj.bias, qk.weight, qk.bias, blk.norm1.weight, blk.norm1.bias)
         return dx
 
@@ -231,7 +282,11 @@ class VitBlockFn(torch.autograd.Function):
 class NormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, ln, m):
-        y, _, mean, rstd = ops.layernorm_fwd(x, ln.weight.data, ln.bias.data, ln.eps)
+        if m.f32_residual:
+            x = f32_stream(x)
+            y, _, mean, rstd = ops.layernorm_fwd_x32(x, ln.weight.data, ln.bias.data, ln.eps, m.compute_dtype)
+        else:
+            y, _, mean, rstd = ops.layernorm_fwd(x, ln.weight.data, ln.bias.data, ln.eps)
         ctx.s = (x, mean, rstd, ln, m)
         return y
 
@@ -239,7 +294,7 @@ class NormFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, mean, rstd, ln, m = ctx.s
         G = m.arena.grad
-        dx = ops.layernorm_bwd(dy.contiguous(), x, mean, rstd, ln.weight.data, G(ln.weight), G(ln.bias))
+        dx = _ln_bwd(dy.contiguous(), x, mean, rstd, ln.weight.data, G(ln.weight), G(ln.bias))
         m.arena.ready(ln.weight, ln.bias)
         ctx.s = None
         return dx, None, None
@@ -253,8 +308,11 @@ class DecStemFn(torch.autograd.Function):
         L, Dd = m.num_patches, m.decoder_embed_dim
         Lk = ids_keep.shape[1]
         y = ops.linear_fwd(latent, A.w(m.decoder_embed.weight), m.decoder_embed.bias.data)
-        xd = ops.unshuffle_fwd(y, ids_restore, m.mask_token.data, m.decoder_pos_embed.data, B, L, Lk, Dd)
         ctx.s = (latent, ids_restore, ids_keep, m, B, Lk)
+        if m.f32_residual:   # f32 stream = 16-bit decoder_embed output or the f32 mask token, + the f32 position table
+            xd = ops.unshuffle_fwd_x32(y, ids_restore, m.mask_token.data, m.decoder_pos_embed.data, B, L, Lk, Dd)
+            return f32_carrier(xd.view(B * (L + 1), Dd), m.compute_dtype)
+        xd = ops.unshuffle_fwd(y, ids_restore, m.mask_token.data, m.decoder_pos_embed.data, B, L, Lk, Dd)
         return xd.view(B * (L + 1), Dd)
 
     @staticmethod
@@ -276,7 +334,11 @@ class DecStemFn(torch.autograd.Function):
 def _dec_head_fwd(m, xd):
     """decoder_norm -> decoder_pred on [B*(L+1), Dd] (model_ecamp.py:256-259); the cls row is still in the output."""
     ln = m.decoder_norm
-    h, _, mean, rstd = ops.layernorm_fwd(xd, ln.weight.data, ln.bias.data, ln.eps)
+    if m.f32_residual:
+        xd = f32_stream(xd)
+        h, _, mean, rstd = ops.layernorm_fwd_x32(xd, ln.weight.data, ln.bias.data, ln.eps, m.compute_dtype)
+    else:
+        h, _, mean, rstd = ops.layernorm_fwd(xd, ln.weight.data, ln.bias.data, ln.eps)
     pred = ops.linear_fwd(h, m.arena.w(m.decoder_pred.weight), m.decoder_pred.bias.data)
     return pred, (xd, mean, rstd, h)
 
@@ -288,7 +350,7 @@ def _dec_head_bwd(m, rec, dpred):
     dp, ln = m.decoder_pred, m.decoder_norm
     _wgrad(A, dpred, h, dp.weight, gb=G(dp.bias))
     dh = ops.linear_dgrad(dpred, A.w(dp.weight))
-    dxd = ops.layernorm_bwd(dh, xd, mean, rstd, ln.weight.data, G(ln.weight), G(ln.bias))
+    dxd = _ln_bwd(dh, xd, mean, rstd, ln.weight.data, G(ln.weight), G(ln.bias))
     A.ready(dp.weight, dp.bias, ln.weight, ln.bias)
     return dxd
 

@@ -63,6 +63,20 @@ def linear_fwd(x, w, bias=None, act=0, residual=None, save_pre=False, out_dtype=
     return (y, pre) if save_pre else y
 
 
+def linear_fwd_res32(x, w, bias, residual):
+    """y (f32) = x @ w.T + bias + residual (f32) -- the residual linear layers of the f32 residual stream (ECAMP(f32_residual=True)):
+    16-bit operands, the sum formed in f32 and never rounded to 16 bits.  x [M,K], w [N,K] 16-bit; residual [M,N] f32."""
+    _chk(x, w, residual)
+    M, K = x.shape
+    N = w.shape[0]
+    assert w.shape[1] == K and x.stride(1) == 1 and w.stride(1) == 1 and w.dtype == x.dtype and x.dtype != torch.float32
+    assert residual.dtype == torch.float32 and residual.shape == (M, N) and residual.stride(1) == 1
+    y = torch.empty((M, N), device=x.device, dtype=torch.float32)
+    call("ecamp_gemm_res32", ptr(x), ptr(w), ptr(y), M, N, K, x.stride(0), w.stride(0), N, ptr(bias), ptr(residual), residual.stride(0),
+         code(x.dtype), stream())
+    return y
+
+
 # --------------------------------------------------------------------------------------------- fp8 forward (configs[4])
 def quantize_fp8(x):
     """Per-tensor e4m3 quantisation of a contiguous f32/bf16 tensor (numel % 4 == 0): -> (q uint8 same shape, scale f32[1]);
@@ -271,6 +285,28 @@ def layernorm_bwd(dy, z, mean, rstd, gamma, ggamma, gbeta, dres=None, drop_p=0.0
     return (dz, dxd) if want_drop else dz
 
 
+def layernorm_fwd_x32(x, gamma, beta, eps, dtype):
+    """LayerNorm of an f32 row (the f32 residual stream) with a 16-bit output `dtype`: -> (y, x, mean, rstd) like layernorm_fwd."""
+    _chk(x, gamma, beta)
+    rows, cols = x.shape
+    assert x.is_contiguous() and x.dtype == torch.float32
+    y = torch.empty((rows, cols), device=x.device, dtype=dtype)
+    mean = torch.empty(rows, device=x.device, dtype=torch.float32)
+    rstd = torch.empty(rows, device=x.device, dtype=torch.float32)
+    call("ecamp_layernorm_fwd_x32", ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(rstd), rows, cols, float(eps), code(dtype), stream())
+    return y, x, mean, rstd
+
+
+def layernorm_bwd_z32(dy, z, mean, rstd, gamma, ggamma, gbeta, dres=None):
+    """layernorm_bwd of a LayerNorm whose input z is f32 (layernorm_fwd_x32); dy, dres and the result dz are 16-bit."""
+    rows, cols = dy.shape
+    assert dy.is_contiguous() and z.is_contiguous() and z.dtype == torch.float32 and (dres is None or dres.dtype == dy.dtype)
+    dz = torch.empty_like(dy)
+    call("ecamp_layernorm_bwd_z32", ptr(dy), ptr(z), ptr(mean), ptr(rstd), ptr(gamma), ptr(dres), ptr(dz), ptr(ggamma), ptr(gbeta), rows, cols,
+         code(dy.dtype), stream())
+    return dz
+
+
 # --------------------------------------------------------------------------------------------- attention
 def _st(t3):
     return _I64x3(*t3)
@@ -448,6 +484,20 @@ def im2col_gather(imgs, ids_keep, p, dtype):
 def assemble_tokens_(x, cls, pos, ids_keep, B, Lk, D):
     call("ecamp_assemble_tokens", ptr(x), ptr(cls), ptr(pos), ptr(ids_keep), B, Lk, D, code(x.dtype), stream())
     return x
+
+
+def assemble_tokens_x32(x, cls, pos, ids_keep, B, Lk, D):
+    """assemble_tokens_ into a NEW f32 tensor: the 16-bit patch-embed output x + the f32 position table (autocast's order)."""
+    out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    call("ecamp_assemble_tokens_x32", ptr(x), ptr(out), ptr(cls), ptr(pos), ptr(ids_keep), B, Lk, D, code(x.dtype), stream())
+    return out
+
+
+def unshuffle_fwd_x32(y, ids_restore, mask_token, dpos, B, L, Lk, D):
+    """unshuffle_fwd with an f32 result: the 16-bit decoder_embed output or the f32 mask token, + the f32 position table."""
+    xd = torch.empty((B, L + 1, D), device=y.device, dtype=torch.float32)
+    call("ecamp_unshuffle_fwd_x32", ptr(y), ptr(ids_restore), ptr(mask_token), ptr(dpos), ptr(xd), B, L, Lk, D, code(y.dtype), stream())
+    return xd
 
 
 def unshuffle_fwd(y, ids_restore, mask_token, dpos, B, L, Lk, D):

@@ -77,6 +77,9 @@ def get_args_parser():
     p.add_argument("--gelu_saved_grad", default=1, type=int, choices=[0, 1], help="bf16 mode: 1 = the fc1 / BertIntermediate epilogue saves gelu'(x) "
                    "for the backward pass (no erf in backward; one more bf16 rounding of the derivative), 0 = save x and recompute gelu' in f32 like "
                    "the reference's GeluBackward")
+    p.add_argument("--f32_residual", action="store_true", help="bf16 / fp16: store the image encoder's and decoder's residual streams in "
+                   "f32, as the reference's autocast does (an f32 stream plus a half branch is f32); GEMM inputs and gradients stay 16-bit. "
+                   "Keeps an fp16 stream that grows past 65504 finite. Not with the e4m3 forward; no effect in fp32")
     p.add_argument("--max_caption_length", default=256, type=int)
     p.add_argument("--synthetic", action="store_true", help="train on the synthetic stand-in dataset (random images and tokens) instead "
                    "of <data_path>/mimic-cxr-2.0.0-entity-llm.csv; without this flag a missing CSV is an error, as in the reference")
@@ -95,6 +98,18 @@ def get_args_parser():
     p.add_argument("--print_freq", default=20, type=int)
     p.add_argument("--snapshot_code", action="store_true", help="copy ./ into output_dir/job_dir like the reference does")
     return p
+
+
+def build_model(args):
+    """The model the flags describe (on the host; `main` moves it to the device).  Resolves --amp into --compute_dtype and, for fp16,
+    the dynamic loss scale, in `args` itself."""
+    if args.amp:
+        args.compute_dtype = args.amp
+    if args.compute_dtype == "fp16":
+        args.loss_scale = "dynamic"   # half's 5-bit exponent needs the reference's GradScaler (util/misc.py:251-271), as its autocast does
+    dtype = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}[args.compute_dtype]
+    return model_ecamp.__dict__[args.model](norm_pix_loss=args.norm_pix_loss, compute_dtype=dtype, gelu_saved_grad=bool(args.gelu_saved_grad),
+                                            f32_residual=args.f32_residual)
 
 
 def main(args):
@@ -147,12 +162,7 @@ def main(args):
     data_loader_train = DataLoader(dataset_train, sampler=sampler_train, batch_size=args.batch_size, num_workers=args.num_workers,
                                    pin_memory=args.pin_mem, drop_last=True, collate_fn=dataset_train.collate_fn)
 
-    if args.amp:
-        args.compute_dtype = args.amp
-    if args.compute_dtype == "fp16":
-        args.loss_scale = "dynamic"   # half's 5-bit exponent needs the reference's GradScaler (util/misc.py:251-271), as its autocast does
-    dtype = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}[args.compute_dtype]
-    model = model_ecamp.__dict__[args.model](norm_pix_loss=args.norm_pix_loss, compute_dtype=dtype, gelu_saved_grad=bool(args.gelu_saved_grad))
+    model = build_model(args)
     model.to(device)
     model_without_ddp = model
     print("Model = %s" % str(model_without_ddp))

@@ -76,7 +76,8 @@ class InterpolateConvSuperResolution(nn.Module):
 class ECAMP(nn.Module):
     def __init__(self, img_size=224, patch_size=16, in_chans=3, embed_dim=768, depth=12, num_heads=12, decoder_embed_dim=768,
                  decoder_depth=4, decoder_num_heads=6, mlp_ratio=4.0, norm_layer=nn.LayerNorm, norm_pix_loss=False,
-                 bert_config=None, compute_dtype=torch.bfloat16, sr_window=None, fp8_forward=False, gelu_saved_grad=None):
+                 bert_config=None, compute_dtype=torch.bfloat16, sr_window=None, fp8_forward=False, gelu_saved_grad=None,
+                 f32_residual=False):
         super().__init__()
         if in_chans != 3 or patch_size != 16:
             # (the SR head's fused kernels are built for 32-px super-patches = patch 16, the only value the reference constructs,
@@ -95,6 +96,12 @@ class ECAMP(nn.Module):
         if fp8_forward and compute_dtype != torch.bfloat16:
             raise ValueError("fp8_forward needs compute_dtype=torch.bfloat16")
         self.fp8_forward = bool(fp8_forward)
+        # The residual streams of the image encoder and decoder (stem -> blocks -> norm / decoder_norm) stored in f32, as autocast leaves
+        # them (an f32 stream + a half branch promotes to f32, model_ecamp.py:222-234,245-255); GEMM inputs, the gradient stream,
+        # parameters and the checkpoint stay as they are.  16-bit modes only: the f32 parity mode is f32 throughout already.
+        if f32_residual and fp8_forward:
+            raise ValueError("f32_residual is not available with fp8_forward (the e4m3 GEMMs keep a bf16 residual stream)")
+        self.f32_residual = bool(f32_residual) and compute_dtype in (torch.bfloat16, torch.float16)
         # fp8_forward also covers the MLM head (transform dense + vocabulary decoder) when set; ECAMP_FP8_HEAD=0/1 overrides the default
         self.fp8_head = os.environ.get("ECAMP_FP8_HEAD", "0") != "0"
         # GELU of the MLP / FFN blocks (timm Mlp.act, HF BertIntermediate): 2 = the fc1 epilogue saves gelu'(pre-activation) instead of the

@@ -25,11 +25,12 @@ typedef struct ihipStream_t* ecampStream_t; /* == hipStream_t */
 
 /* Bumped whenever an exported signature changes (2: ecamp_wgrad_group gained table_bytes, ecamp_gemm_fp8 its q8_* arguments;
  * 3: round 5 -- ecamp_dropout_mask, ecamp_prof_dump, ecamp_fp8_roll's amax history and margin; 4: round 6 -- ecamp_adamw_grouped's
- * `ctl`, ecamp_loss_scale_update, ecamp_half_format, the resample entry points).  ecamp_abi_version()
+ * `ctl`, ecamp_loss_scale_update, ecamp_half_format, the resample entry points; 5: the f32 residual stream -- ecamp_gemm_res32,
+ * ecamp_layernorm_fwd_x32, ecamp_layernorm_bwd_z32, ecamp_assemble_tokens_x32, ecamp_unshuffle_fwd_x32).  ecamp_abi_version()
  * returns the value the library was BUILT with; a consumer compares it with the header it was compiled against -- the Python binding
  * (ecamp_amd/_lib.py) refuses a library of another version, which is what protects an A/B of two builds (ECAMP_LIB, tools/ab_lib.sh)
  * from calling an older build with a newer argument list. */
-#define ECAMP_ABI_VERSION 4
+#define ECAMP_ABI_VERSION 5
 int ecamp_abi_version(void);
 const char* ecamp_last_error(void);
 /* The 16-bit activation format of THIS build -- what dtype code ECAMP_BF16 (1) stores.  0: bfloat16 (libecamp_hip.so, the benchmarked
@@ -57,6 +58,13 @@ int ecamp_gemm(const void* A, const void* B, void* C, int64_t M, int64_t N, int6
                int64_t ldb, int64_t ldc, const float* bias, const void* residual, int64_t ldr, void* pre_out, int64_t ldp,
                const void* gmul, int64_t ldg, int act, float alpha, const float* alpha_dev, int dtype, int out_f32, int accumulate,
                int split_k, float* splitk_ws, float* rowsum, ecampStream_t stream);
+/* The f32 residual stream (ECAMP(f32_residual=True); the stream autocast leaves in f32: an f32 x plus a half branch promotes to f32 at timm
+ * Block `x = x + attn(norm1(x))` / `x = x + mlp(norm2(x))`, model_ecamp.py:233-234,254-255): C f32 [M, ldc] = A B^T + bias[n] + residual
+ * (f32 [M, ldr]); A [M, lda] and B [N, ldb] 16-bit (dtype 1), both contraction-contiguous -- the forward form of ecamp_gemm with its
+ * residual epilogue, the sum formed from the f32 accumulator and never rounded to 16 bits.  Same kernels as ecamp_gemm (the persistent
+ * ones where their legality holds, counted by ecamp_gemm_q8_launches / ecamp_gemm_q16_launches); residual and C 16-B aligned. */
+int ecamp_gemm_res32(const void* A, const void* B, float* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
+                     const float* bias, const float* residual, int64_t ldr, int dtype, ecampStream_t stream);
 /* Split count the library recommends for ecamp_gemm(M, N, K, ...) with an f32 accumulated output (the weight-gradient call of
  * torch.autograd for nn.Linear, e.g. timm Mlp.fc1 at model_ecamp.py:233): it depends on which kernel the shape selects
  * (128^2 tiles, or the persistent 256^2 kernel whose work items should fill whole rounds of the chip).  Pure host arithmetic. */
@@ -150,6 +158,13 @@ int ecamp_layernorm_fwd(const void* x, const void* residual, void* z_out, const 
 int ecamp_layernorm_bwd(const void* dy, const void* z, const float* mean, const float* rstd, const float* gamma,
                         const void* dres_in, void* dz, void* dx_drop, float* dgamma, float* dbeta, int64_t rows, int32_t cols,
                         float drop_p, uint64_t seed, uint64_t offset, int32_t dtype, ecampStream_t stream);
+/* The LayerNorms of the f32 residual stream (timm Block norm1 / norm2, `norm`, `decoder_norm`: model_ecamp.py:69,84,233-235,254-256 --
+ * under autocast nn.LayerNorm runs in f32 on the f32 stream): x / z f32 [rows, cols]; y, dy, dres_in (nullable) and dz 16-bit (dtype 1).
+ * No residual or dropout fusion; otherwise ecamp_layernorm_fwd / ecamp_layernorm_bwd. */
+int ecamp_layernorm_fwd_x32(const float* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int64_t rows,
+                            int32_t cols, float eps, int32_t dtype, ecampStream_t stream);
+int ecamp_layernorm_bwd_z32(const void* dy, const float* z, const float* mean, const float* rstd, const float* gamma, const void* dres_in,
+                            void* dz, float* dgamma, float* dbeta, int64_t rows, int32_t cols, int32_t dtype, ecampStream_t stream);
 
 /* ---- attention (timm Attention.forward: softmax(q k^T * hd^-1/2) v; HF BertSelfAttention 4.42.4 incl. the
  * cross-attention mode of context_fusion.py:45-53).  strides = {batch, token, head} in elements, head_dim contiguous.
@@ -211,6 +226,10 @@ int ecamp_im2col_gather(const float* imgs, const int32_t* ids_keep, void* out, i
                         int32_t p, int32_t dtype, ecampStream_t stream); /* model_ecamp.py:220 + :185 */
 int ecamp_assemble_tokens(void* x, const float* cls, const float* pos, const int32_t* ids_keep, int64_t B, int32_t Lk, int32_t D,
                           int32_t dtype, ecampStream_t stream); /* model_ecamp.py:222,228-230 */
+/* ecamp_assemble_tokens into a separate f32 out [B, Lk+1, D] from the 16-bit (dtype 1) patch embedding x: the f32 residual stream's first
+ * value, autocast's half conv output + f32 pos_embed (model_ecamp.py:222,228-230) */
+int ecamp_assemble_tokens_x32(const void* x, float* out, const float* cls, const float* pos, const int32_t* ids_keep, int64_t B, int32_t Lk,
+                              int32_t D, int32_t dtype, ecampStream_t stream);
 /* The dataset's image transform on the device (pretrain_datasets.py:47-52,113-115: RandomResizedCrop(448, bicubic) + RandomHorizontalFlip +
  * Grayscale): B crops of a pre-decoded uint8 grayscale radiograph -> dst uint8 [B, out, out], equal BYTE FOR BYTE to
  * PIL's img.crop(box).resize((out, out), BICUBIC) (+ FLIP_LEFT_RIGHT, convert('L')) on the same pixels -- Pillow's two-pass antialiased
@@ -224,6 +243,10 @@ int ecamp_resample_crops_u8(const uint8_t* src, const int64_t* table, uint8_t* d
                             int32_t max_h, void* ws, int64_t ws_bytes, int32_t* err_flag, ecampStream_t stream);
 int ecamp_unshuffle_fwd(const void* y, const int32_t* ids_restore, const float* mask_token, const float* dpos, void* xd, int64_t B,
                         int32_t L, int32_t Lk, int32_t D, int32_t dtype, ecampStream_t stream); /* model_ecamp.py:245-251 */
+/* ecamp_unshuffle_fwd with an f32 xd from the 16-bit (dtype 1) y: the decoder's f32 residual stream (autocast promotes the cat of the half
+ * decoder_embed output with the f32 mask tokens, + the f32 decoder_pos_embed: model_ecamp.py:245-251) */
+int ecamp_unshuffle_fwd_x32(const void* y, const int32_t* ids_restore, const float* mask_token, const float* dpos, float* xd, int64_t B,
+                            int32_t L, int32_t Lk, int32_t D, int32_t dtype, ecampStream_t stream);
 int ecamp_unshuffle_bwd(const void* dxd, const int32_t* ids_restore, const int32_t* ids_keep, void* dy, float* dmask_token,
                         int64_t B, int32_t L, int32_t Lk, int32_t D, int32_t dtype, ecampStream_t stream);
 int ecamp_unpatchify_mim(const void* pred, const float* imgs, const float* mask, float* pred_img, float* loss_sum, int64_t B,
