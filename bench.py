@@ -3,7 +3,12 @@
 
     python bench.py --gpus 1 --steps 50 --warmup 10      (the defaults: SURVEY.md 8(d))
     python bench.py ... --dump-outputs DIR                (also write what the last timed step computed to DIR/*.npy: dump_outputs)
+    python bench.py ... --full                            (also every side measurement below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps of `value`, writes --dump-outputs and prints the result line: nothing else.  Everything
+below that is not `value` (the PCIe-inclusive leg, the forward-only / forward+backward / image-side rates, the roofline pass and the CPU
+baseline) runs only with --full.
 
 A "step" = one full optimizer-inclusive pre-training micro-step of configs[1]: ViT-B/16 MAE encoder/decoder + SR
 head + reference BERT (6L/6H/1536, vocab 30000) with context fusion, B=256 pairs per GPU, 224^2 encoder input (448^2
@@ -21,9 +26,9 @@ rates are reported too.
 `python bench.py --gpus N` with N > 1 and no RANK in the environment launches its own N ranks (one child process per GPU,
 RCCL over xGMI) before anything in this process touches the GPU; under torch.distributed.run it uses the ranks it is given.
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel = the bf16 MFMA GEMM family, timed live with HIP
-events on the launch stream over the timed region) and `cpu_baseline` (the oracle -- a CPU restatement of the
-reference validated against it -- timed on this box's host cores on a bounded sample; kind="port").
+Prints ONE JSON line on rank 0; with --full it also carries `roofline` (dominant kernel = the bf16 MFMA GEMM family, timed
+live with HIP events on the launch stream over a serialized pass of the step) and `cpu_baseline` (the oracle -- a CPU
+restatement of the reference validated against it -- timed on the host cores on a bounded sample; kind="port").
 """
 import argparse
 import ctypes
@@ -245,7 +250,7 @@ def launch_ranks(cmd, n, poll_s=0.2, grace_s=5.0, check_devices=True, limit_s=No
     return 0
 
 
-def main():
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)   # >= 50 timed steps after 10 warm-up
@@ -258,11 +263,19 @@ def main():
                     "of 616 MB of f32 [B,3,448,448]); the default stays the reference's f32 schema")
     ap.add_argument("--grad-dtype", default=os.environ.get("ECAMP_DDP_GRAD_DTYPE", "f32"), choices=["f32", "bf16"],
                     help="payload of the gradient all-reduce at N > 1 (f32 = the reference's; bf16 halves the bytes on the links)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-prof", action="store_true", help="do not bracket GEMM launches with HIP events")
-    ap.add_argument("--only-value", action="store_true", help="time the K steps of `value` and nothing else (kernel traces of the production step)")
+    mode = ap.add_mutually_exclusive_group()
+    mode.add_argument("--full", action="store_true", help="after `value`, also the PCIe-inclusive leg, the forward-only / forward+backward / "
+                      "image-side rates, the serialized roofline pass and the CPU baseline (a plain run times `value` and nothing else)")
+    mode.add_argument("--only-value", action="store_true", help="a plain run, which is the default (kept for existing command lines)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-prof", action="store_true", help="--full without the roofline pass (no HIP events around GEMM launches)")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last of them computed (losses, gradient norm, "
                     "a fixed sample of the updated weights) to DIR/*.npy on rank 0")
+    return ap
+
+
+def main():
+    ap = arg_parser()
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -405,11 +418,38 @@ def main():
                 "note": "all-reduce of the f32 gradient arena in buckets on a side HIP stream, overlapped with backward; ms = sum of the "
                         "buckets' event-bracketed durations on that stream on rank 0 (they overlap compute, so this is not added step time)"}
         red.timing = False
-    if args.only_value:
+
+    def record(dt, losses, input_note):
+        """The result line's fields that a plain run and --full share: `value` and what describes it."""
+        pairs = args.batch * world * args.steps
+        return {"metric": METRIC, "value": round(pairs / dt, 2), "unit": "pairs/s", "n_gpus": world, "steps": args.steps,
+                "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 3), "higher_is_better": True, "scaling": "weak",
+                "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+                "config": {"workload": "BASELINE.json configs[1]: ViT-B/16 MAE enc/dec + SR head + reference BERT (6L/6H/1536, vocab 30000) "
+                                       "+ context fusion; full train step (fwd+bwd+grad-norm+AdamW, dropout on)",
+                           "pairs_per_gpu": args.batch, "global_batch": args.batch * world,
+                           "image": "448^2 -> 224^2 encoder input" + (", uint8 grayscale crops normalised on the device" if args.image_u8 else ""),
+                           "seq_len": args.seq, "mask_ratio": 0.75, "accum_iter": 1, "parallelism": "dp%d" % world,
+                           "last_losses_mim_res_mlm": [round(x, 5) for x in losses]},
+                **({"loss_scale": {"mode": "dynamic (GradScaler: init 65536, x2 after 2000 clean steps, x0.5 and a skipped step on inf / nan)",
+                                   "scale": scaler.get_scale(), "skipped_steps": scaler.skipped_steps}} if scaler.dynamic else {}),
+                "input": input_note,
+                "step_ms": value_steps,
+                "resident_pairs_per_s": round(pairs / dt, 2), "resident_ms_per_step": round(1e3 * dt / args.steps, 3),   # = value (kept for the A/B tools)
+                "value_median_pairs_per_s": round(1e3 * args.batch * world / value_steps["median"], 2) if value_steps else None}
+
+    if not args.full:   # a plain run: the result line of the K steps above, nothing more
+        if world > 1:
+            t = torch.tensor([dt], device=dev, dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt = float(t.item())
         if rank == 0:
-            print(json.dumps({"metric": METRIC, "value": round(args.batch * world * args.steps / dt, 2), "unit": "pairs/s", "n_gpus": world,
-                              "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 3), "rccl": rccl,
-                              "step_ms": value_steps, "note": "--only-value (inputs resident): side measurements, roofline pass and CPU baseline skipped"}))
+            res = record(dt, [float(v.detach()) for v in out[:3]], "resident in HBM when the timed region starts (`value`, `ms_per_step`, `step_ms`)")
+            if rccl is not None:
+                res["rccl"] = rccl
+            res["note"] = ("plain run: the PCIe-inclusive leg, the forward-only / forward+backward / image-side rates, the roofline pass and the "
+                           "CPU baseline run with --full")
+            print(json.dumps(res), flush=True)
         if world > 1:
             dist.destroy_process_group()
         return
@@ -502,33 +542,19 @@ def main():
 
     if rank == 0:
         pairs = args.batch * world * args.steps
-        res = {"metric": METRIC, "value": round(pairs / dt, 2), "unit": "pairs/s", "n_gpus": world, "steps": args.steps,
-               "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 3), "higher_is_better": True, "scaling": "weak",
-               "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-               "config": {"workload": "BASELINE.json configs[1]: ViT-B/16 MAE enc/dec + SR head + reference BERT (6L/6H/1536, vocab 30000) "
-                                      "+ context fusion; full train step (fwd+bwd+grad-norm+AdamW, dropout on)",
-                          "pairs_per_gpu": args.batch, "global_batch": args.batch * world,
-                          "image": "448^2 -> 224^2 encoder input" + (", uint8 grayscale crops normalised on the device" if args.image_u8 else ""),
-                          "seq_len": args.seq, "mask_ratio": 0.75, "accum_iter": 1, "parallelism": "dp%d" % world,
-                          "last_losses_mim_res_mlm": [round(x, 5) for x in losses]},
-               **({"loss_scale": {"mode": "dynamic (GradScaler: init 65536, x2 after 2000 clean steps, x0.5 and a skipped step on inf / nan)",
-                                  "scale": scaler.get_scale(), "skipped_steps": scaler.skipped_steps}} if scaler.dynamic else {}),
-               "input": "resident in HBM when the timed region starts (`value`, `ms_per_step`, `step_ms`); the PCIe-inclusive rate of the same "
-                        "step is `host_inclusive_*` (pinned host batch -> HBM inside that timed region: every timed step issues the copy of the batch "
-                        "two steps ahead on a copy stream; steady-state pipeline primed by 3 untimed steps)",
-               "step_ms": value_steps,
-               "resident_pairs_per_s": round(pairs / dt, 2), "resident_ms_per_step": round(1e3 * dt / args.steps, 3),   # = value (kept for the A/B tools)
-               "value_median_pairs_per_s": round(1e3 * args.batch * world / value_steps["median"], 2) if value_steps else None,
-               "host_inclusive_pairs_per_s": round(pairs / dt_host, 2), "host_inclusive_ms_per_step": round(1e3 * dt_host / args.steps, 3),
-               "host_inclusive_step_ms": host_steps,
-               "h2d_ms_per_step": round(h2d_ms / max(h2d_n, 1), 3), "h2d_mb_per_step": round(h2d_bytes / max(h2d_n, 1) / 1e6, 1),
-               "h2d_gbps": round(h2d_bytes / max(h2d_ms, 1e-9) / 1e6, 2),
-               "h2d_gbps_needed": round(h2d_bytes / max(h2d_n, 1) / (dt / args.steps) / 1e9, 2),
-               "h2d_note": "event pairs around each batch's copies on the copy stream (rank 0); the copy of a batch hides under a step while "
-                           "h2d_gbps > h2d_gbps_needed (bytes per batch / resident step time); below that the box's PCIe path, not the kernels, sets "
-                           "host_inclusive_*",
-               "fwd_only_ms": round(1e3 * dt_fwd, 3), "fwd_only_pairs_per_s": round(args.batch * world / dt_fwd, 2),
-               "fwd_bwd_ms": round(1e3 * dt_fb, 3), "fwd_bwd_pairs_per_s": round(args.batch * world / dt_fb, 2)}
+        res = record(dt, losses, "resident in HBM when the timed region starts (`value`, `ms_per_step`, `step_ms`); the PCIe-inclusive rate of the same "
+                     "step is `host_inclusive_*` (pinned host batch -> HBM inside that timed region: every timed step issues the copy of the batch "
+                     "two steps ahead on a copy stream; steady-state pipeline primed by 3 untimed steps)")
+        res.update({"host_inclusive_pairs_per_s": round(pairs / dt_host, 2), "host_inclusive_ms_per_step": round(1e3 * dt_host / args.steps, 3),
+                    "host_inclusive_step_ms": host_steps,
+                    "h2d_ms_per_step": round(h2d_ms / max(h2d_n, 1), 3), "h2d_mb_per_step": round(h2d_bytes / max(h2d_n, 1) / 1e6, 1),
+                    "h2d_gbps": round(h2d_bytes / max(h2d_ms, 1e-9) / 1e6, 2),
+                    "h2d_gbps_needed": round(h2d_bytes / max(h2d_n, 1) / (dt / args.steps) / 1e9, 2),
+                    "h2d_note": "event pairs around each batch's copies on the copy stream (rank 0); the copy of a batch hides under a step while "
+                                "h2d_gbps > h2d_gbps_needed (bytes per batch / resident step time); below that the box's PCIe path, not the kernels, sets "
+                                "host_inclusive_*",
+                    "fwd_only_ms": round(1e3 * dt_fwd, 3), "fwd_only_pairs_per_s": round(args.batch * world / dt_fwd, 2),
+                    "fwd_bwd_ms": round(1e3 * dt_fb, 3), "fwd_bwd_pairs_per_s": round(args.batch * world / dt_fb, 2)})
         # the north-star's ">= 40 % MFMA roofline on the ViT-B/16 forward+backward at bs=256/GPU" in its own scope: the image side alone
         # (model_ecamp.py:218-264,276-300), 7.154 GMAC forward per image x 2 FLOP x 3 (fwd + dgrad + wgrad) = 42.92 GFLOP per image
         # (SURVEY.md 8(d)); production stream layout (weight gradients on the side stream), inputs resident

@@ -222,11 +222,11 @@ def test_ddp_wrapper_runs_rccl_on_the_side_stream(dev):
 
 
 def test_bench_prints_one_contract_line(dev):
-    """bench.py's output contract: exactly ONE JSON line on stdout with the driver's keys, the `roofline` object measured from
+    """bench.py --full's output contract: exactly ONE JSON line on stdout with the driver's keys, the `roofline` object measured from
     HIP events, and `cpu_baseline` only when asked for (skipped here to keep the test short)."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "8", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--batch", "8", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
@@ -257,6 +257,27 @@ def test_bench_prints_one_contract_line(dev):
     assert r["h2d_gbps"] > 0 and r["h2d_mb_per_step"] > 8 * 3 * 448 * 448 * 4 / 1e6
 
 
+def test_bench_plain_run_times_value_and_nothing_else(dev, tmp_path):
+    """bench.py without --full: ONE JSON line with the headline keys (`value` = the resident rate, as with --full), the dumped outputs
+    of the last timed step, and none of the side measurements (PCIe-inclusive leg, forward-only rates, roofline pass, CPU baseline)."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "8",
+                        "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600, cwd=root)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    r = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+              "data", "config", "step_ms"):
+        assert k in r, k
+    assert r["unit"] == "pairs/s" and r["n_gpus"] == 1 and r["steps"] == 2 and r["warmup"] == 1 and r["higher_is_better"] is True
+    assert r["dtype"] == "bf16" and abs(r["value"] - 8 * 1e3 / r["ms_per_step"]) < 1e-2 * r["value"]
+    for k in ("roofline", "cpu_baseline", "host_inclusive_pairs_per_s", "h2d_gbps", "fwd_only_ms", "fwd_bwd_ms", "vit_fwd_bwd_ms"):
+        assert k not in r, k
+    assert sorted(os.listdir(tmp_path / "out")) == ["grad_norm.npy", "losses_mim_res_mlm.npy", "params_sample.npy"]
+
+
 def test_bench_driver_protocol_value_is_explained_by_its_own_record(dev):
     """VERDICT r5 item 1.  The driver's command (`--steps 20 --warmup 5`, the B = 256 workload): `value` (inputs resident in HBM when the
     timed region starts) must be a steady number -- no step of the timed region more than 10 % over the median, mean = median -- and the
@@ -270,7 +291,7 @@ def test_bench_driver_protocol_value_is_explained_by_its_own_record(dev):
     torch.cuda.empty_cache()   # the child needs ~60 GB of the card this process may hold in its allocator's cache
 
     def run():
-        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-prof"],
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-prof"],
                            capture_output=True, text=True, timeout=900, cwd=root)
         assert p.returncode == 0, p.stderr[-2000:]
         r = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])

@@ -210,6 +210,21 @@ def test_bench_dump_outputs_writes_the_step_outputs_and_a_fixed_weight_sample(tm
                                                  model[1].bias.detach().numpy()]))  # small tensors in full, in parameter order
 
 
+def test_bench_side_measurements_only_with_full():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times `value` alone; the side measurements are opted into with --full.
+    --only-value (older command lines) names the plain run and cannot be combined with --full."""
+    import importlib.util, os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    ap = bench.arg_parser()
+    assert ap.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"]).full is False
+    assert ap.parse_args(["--full"]).full is True and ap.parse_args(["--only-value"]).full is False
+    with pytest.raises(SystemExit):
+        ap.parse_args(["--full", "--only-value"])
+
+
 def test_main_pretrain_needs_the_dataset_or_an_explicit_synthetic_flag(tmp_path):
     """a mistyped --data_path must not silently train on noise."""
     from ecamp_amd import main_pretrain

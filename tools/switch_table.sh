@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 run() {
   echo -n "$1: "
-  env $1 python3 $R/bench.py --no-cpu-baseline --steps 30 2>/dev/null | python3 -c "
+  env $1 python3 $R/bench.py --full --no-cpu-baseline --steps 30 2>/dev/null | python3 -c "
 import json,sys
 r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(r['value'], r['ms_per_step'], r['step_ms']['max'], r['roofline']['gemm_ms_per_step'], r['roofline']['serialized_ms_per_step'])"
 }
