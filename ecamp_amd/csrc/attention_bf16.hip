@@ -1162,15 +1162,11 @@ static void lds_optin(K kern, size_t bytes) {
 // ECAMP_ATTN_HEAD=0 keeps the 64-row streaming kernels (A/B measurements)
 static long g_head_launches = 0;   // development ABI: launches of the head-resident kernels so far (tests assert that they really ran)
 extern "C" int64_t ecamp_attn_head_launches(void) { return g_head_launches; }
-static int g_head_mode = -1;   // ecamp_set_option("attn_head", v): -1 = the environment decides
-void attn_set_head_mode(int on) { g_head_mode = on < 0 ? -1 : (on ? 1 : 0); }
-static bool head_enabled() {
-    static const int env = [] { const char* e = getenv("ECAMP_ATTN_HEAD"); return e ? atoi(e) : 1; }();
-    return (g_head_mode >= 0 ? g_head_mode : env) != 0;
-}
+void attn_set_head_mode(int on) { ecamp_opt_set("attn_head", on); }   // ecamp_set_option("attn_head", v): negative = the environment decides
+static bool head_enabled() { return ecamp_opt(OPT_ATTN_HEAD) != 0; }
 // workgroup size: one wave per 16-row tile up to `cap` waves (ECAMP_ATTN_WAVES overrides the cap: tuning)
 static int head_waves(int tiles, int cap) {
-    static const int env = [] { const char* e = getenv("ECAMP_ATTN_WAVES"); return e ? atoi(e) : 0; }();
+    const int env = ecamp_opt(OPT_ATTN_WAVES);
     if (env > 0) cap = env;
     return tiles < cap ? tiles : cap;
 }

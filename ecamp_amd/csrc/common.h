@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include "options.h"
 
 #define ECAMP_F32 0
 #define ECAMP_BF16 1

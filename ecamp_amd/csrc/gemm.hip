@@ -19,9 +19,11 @@
 #include <stdlib.h>
 #include <string.h>
 #include <stdint.h>
+#include <map>
+#include <string>
+#include <vector>
 
 #include "gemm_args.h"
-void attn_set_head_mode(int on);   // attention_bf16.hip
 #include "gemm_q8.h"
 #include "gemm_q16.h"
 
@@ -579,93 +581,10 @@ extern "C" int ecamp_quant_fp8(const void* x, const float* amax, void* q, float*
     ECAMP_LAUNCH_CHECK();
     return 0;
 }
-static int p8_num_cu();
-static int q8_env();
-static long q8_min_items();
-static long g_f8_q8_launches = 0;
-extern "C" int64_t ecamp_gemm_f8_q8_launches(void) { return g_f8_q8_launches; }
-extern "C" int ecamp_gemm_fp8(const void* A8, const void* B8, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
-                              int64_t ldc, const float* scale_a, const float* scale_b, const float* bias, const void* residual,
-                              int64_t ldr, void* pre_out, int64_t ldp, int act, void* q8_out, const float* q8_scale, float* q8_amax_slots,
-                              hipStream_t stream) {
-    ECAMP_CHECK_ARG(!q8_out || (q8_scale && q8_amax_slots && (act == 1 || act == 2) && pre_out && !residual && ldc == N),
-                    "ecamp_gemm_fp8: the e4m3 copy of the output needs its scale and amax slots, the GELU epilogue and a dense C");
-    ECAMP_CHECK_ARG(A8 && B8 && C && scale_a && scale_b, "ecamp_gemm_fp8: null operand");
-    ECAMP_CHECK_ARG(act >= 0 && act <= 2 && (act != 2 || pre_out), "ecamp_gemm_fp8: act=%d (0 none, 1 GELU, 2 GELU with the saved derivative in pre_out)", act);
-    ECAMP_CHECK_ARG(M > 0 && N > 0 && K > 0, "ecamp_gemm_fp8: bad shape %ld %ld %ld", (long)M, (long)N, (long)K);
-    ECAMP_CHECK_ARG(K % 16 == 0 && lda % 16 == 0 && ldb % 16 == 0 && N % 4 == 0, "ecamp_gemm_fp8: K, lda, ldb must be multiples of 16 and N of 4");
-    {   // outputs past 2 GB (the vocabulary projection at B = 512: 65536 x 30000 bf16): two calls over row halves, as ecamp_gemm does
-        const long lim = 0x7fffffffl;
-        if (M >= 512 && !q8_out && (M * ldc * 2 > lim || (residual && M * ldr * 2 > lim) || (pre_out && M * ldp * 2 > lim))) {
-            const int64_t m1 = (M / 2 + 255) / 256 * 256;
-            auto rows = [](const void* p, int64_t r, int64_t ld, int64_t es) { return p ? (const void*)((const char*)p + r * ld * es) : nullptr; };
-            int rc = ecamp_gemm_fp8(A8, B8, C, m1, N, K, lda, ldb, ldc, scale_a, scale_b, bias, residual, ldr, pre_out, ldp, act, nullptr, nullptr, nullptr, stream);
-            if (rc) return rc;
-            return ecamp_gemm_fp8(rows(A8, m1, lda, 1), B8, (void*)rows(C, m1, ldc, 2), M - m1, N, K, lda, ldb, ldc, scale_a, scale_b, bias, rows(residual, m1, ldr, 2),
-                                  ldr, (void*)rows(pre_out, m1, ldp, 2), ldp, act, nullptr, nullptr, nullptr, stream);
-        }
-    }
-    GemmArgs g;
-    g.dbg = 0; g.wide = 0; g.nsplit = 1;
-    g.A = A8; g.B = B8; g.C = C;
-    g.M = (int)M; g.N = (int)N; g.K = (int)K;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.bias = bias; g.residual = residual; g.ldr = ldr; g.pre_out = pre_out; g.ldp = ldp; g.gmul = nullptr; g.ldg = 0;
-    g.alpha = 1.0f; g.alpha_dev = nullptr; g.alpha_dev2 = nullptr; g.alpha_out = 1.0f; g.alpha_dev_out = nullptr;
-    g.q8_out = nullptr; g.q8_scale = nullptr; g.q8_amax = nullptr;
-    g.rowsum = nullptr;
-    g.act = act; g.out_f32 = 0; g.accumulate = 0;
-    g.k_per_split = (int)K;
-    g.partial = nullptr;
-    g.nbm = ceil_div(M, BM); g.nbn = ceil_div(N, BN);
-    const bool prof = ecamp_prof_active();
-    if (prof) ecamp_prof_begin(ECAMP_PROF_GEMM_FP8, 2.0 * (double)M * (double)N * (double)K, stream);
-    // the persistent 256 x 256 x 128 e4m3 form (gemm_q8.h, F8) from the same tile count up as the bf16 kernel, when its alignment /
-    // size conditions hold; otherwise the 128^2 kernel below.  ECAMP_F8_Q8=0 keeps everything on the 128^2 kernel (development A/B).
-    {
-        static const int f8q8 = getenv("ECAMP_F8_Q8") ? atoi(getenv("ECAMP_F8_Q8")) : 1;
-        const int q8m = q8_env();
-        const int epi = (pre_out || act) ? ((pre_out && (act == 1 || act == 2) && !residual) ? 1 : -1) : residual ? 2 : 0;
-        auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-        const long lim = 0x7fffffffl;
-        const long items8 = (long)ceil_div(M, 256) * ceil_div(N, 256);
-        const bool legal = f8q8 && q8m != 0 && epi >= 0 && K >= 256 && N % 8 == 0 && ldc % 8 == 0 && al16(A8) && al16(B8) && al16(C) &&
-                           M * lda <= lim && N * ldb <= lim && M * ldc * 2 <= lim && (!bias || al16(bias)) &&
-                           (!pre_out || (ldp % 8 == 0 && al16(pre_out) && M * ldp * 2 <= lim)) &&
-                           (!residual || (ldr % 8 == 0 && al16(residual) && M * ldr * 2 <= lim));
-        if (legal && (q8m == 2 || items8 >= q8_min_items())) {
-            typedef void (*f8_fn)(GemmArgs);
-            const f8_fn fn = epi == 0 ? (f8_fn)gemm_f8_q8_kernel<0> : epi == 1 ? (f8_fn)gemm_f8_q8_kernel<1> : (f8_fn)gemm_f8_q8_kernel<2>;
-            g.nbm = ceil_div(M, 256); g.nbn = ceil_div(N, 256); g.nsplit = 1; g.wide = 1;
-            g.alpha_dev = scale_a; g.alpha_dev2 = scale_b;
-            g.q8_out = q8_out; g.q8_scale = q8_scale; g.q8_amax = q8_amax_slots;
-            const size_t shm = 10 * Q8_HALF;
-            static bool attr[3] = {false, false, false};
-            if (!attr[epi]) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); attr[epi] = true; }
-            const int ncu = p8_num_cu();
-            hipLaunchKernelGGL(fn, dim3((unsigned)(items8 < ncu ? items8 : ncu)), dim3(512), shm, stream, g);
-            ++g_f8_q8_launches;
-            if (prof) ecamp_prof_end(stream);
-            ECAMP_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-    hipLaunchKernelGGL(gemm_fp8_kernel, dim3(g.nbm * g.nbn), dim3(256), 0, stream, g, scale_a, scale_b);
-    if (prof) ecamp_prof_end(stream);
-    if (q8_out) {   // the 128^2 kernel has no third output: one pass over C afterwards gives the same bytes
-        const long n4 = M * N / 4;
-        int nb = (int)((n4 + 255) / 256);
-        if (nb > 4096) nb = 4096;
-        hipLaunchKernelGGL(quant_fp8_delayed_kernel<bf16_t>, dim3(nb), dim3(256), 0, stream, (const bf16_t*)C, q8_scale, (unsigned int*)q8_out, q8_amax_slots, n4);
-    }
-    ECAMP_LAUNCH_CHECK();
-    return 0;
-}
-
 // =============================================================================================
-// host entry
+// host side: device size and switches, the persistent launch, kernel selection, entry points
 // =============================================================================================
-// ---- kernel selection ------------------------------------------------------------------------------------------
+// A persistent workgroup needs a whole CU (all 160 KB of LDS, all registers), so the persistent kernels run on one workgroup per CU.
 static int p8_num_cu() {
     static int ncu = 0;
     if (!ncu) {
@@ -674,159 +593,222 @@ static int p8_num_cu() {
         if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
         // development (profiles/r05_epilogue_scale.txt): persistent launches on fewer workgroups than CUs, so that launches of two streams
         // sit side by side instead of one behind the other
-        const char* cap = getenv("ECAMP_GEMM_GRID_CAP");
-        if (cap && atoi(cap) >= 32 && atoi(cap) < ncu) {
-            ncu = atoi(cap);
+        const int cap = ecamp_opt(OPT_GEMM_GRID_CAP);
+        if (cap >= 32 && cap < ncu) {
+            ncu = cap;
             fprintf(stderr, "[ecamp_hip] WARNING: ECAMP_GEMM_GRID_CAP=%d -- a development switch: every persistent GEMM of this process runs on %d "
                             "workgroups instead of one per CU\n", ncu, ncu);
         }
     }
     return ncu;
 }
-// A persistent workgroup needs a whole CU (all 160 KB of LDS, all registers): when another kernel holds even one wave on a CU, the
-// workgroup assigned there starts late and the launch takes up to twice as long (tools/hog_probe.py: +11-17 % on the step with a
-// co-resident spinning kernel, against +1-5 % for the 128^2 kernel).  During the backward pass of a multi-GPU run RCCL's
-// all-reduce workgroups are such co-tenants.  Two process-wide switches (ecamp_set_option): "p8_wgrad" = 0 keeps the
-// weight-gradient form off the persistent kernel; "p8_wgrad_reserve_cus" = n launches it with n fewer workgroups than CUs, so
-// that a communication kernel that is already resident (or arrives between two GEMMs) finds CUs without displacing a
-// persistent workgroup.  The data-parallel wrapper sets the reserve; the forward pass has no communication beside it.
-static int g_p8_wgrad = 1;
-static int g_p8_wgrad_reserve = 0;
-// "q8_bwd_grid" = n > 0 launches the DATA-GRADIENT form on min(items, n) workgroups instead of one per CU; n >= items gives one
-// output tile per workgroup, i.e. the hardware dispatcher hands tiles to whichever CU is free.  That is what the data-parallel
-// wrapper asks for: beside RCCL's all-reduce workgroups a persistent workgroup whose CU is taken starts late and holds its whole
-// static share of the tiles back, while one-tile workgroups simply flow around the occupied CUs.  Measured cost on a GPU of its
-// own (tools/grid_ab.sh): +0.15 ms per step for the data-gradient form (+0.4 ms if the forward form did the same, which it does not
-// need: nothing communicates during forward) -- the cross-tile DMA prefetch of the persistent loop is worth that much and no more.
-static int g_q8_bwd_grid = 0;
-
-// ---- Q8 (gemm_q8.h): the persistent 256x256x64 kernel.  ECAMP_GEMM_Q8 / option "q8_mode": -1 automatic (default), 0 never, 2 whenever legal.
-static int g_q8_mode = -2;
-static int q8_env() {
-    static const int v = getenv("ECAMP_GEMM_Q8") ? atoi(getenv("ECAMP_GEMM_Q8")) : -1;
-    return g_q8_mode != -2 ? g_q8_mode : v;
+// CUs a persistent launch of the BACKWARD pass (data-gradient, weight-gradient and grouped forms of Q8) may use.  When another kernel
+// holds even one wave on a CU, the workgroup assigned there starts late and the launch takes up to twice as long (tools/hog_probe.py:
+// +11-17 % on the step with a co-resident spinning kernel, against +1-5 % for the 128^2 kernel).  During the backward pass of a
+// multi-GPU run RCCL's all-reduce workgroups are such co-tenants, so "p8_wgrad_reserve_cus" = n leaves n CUs to them when at least 64
+// remain.  The data-parallel wrapper sets it; the forward pass has no communication beside it.
+static int p8_bwd_cus() {
+    const int ncu = p8_num_cu(), reserve = ecamp_opt(OPT_P8_WGRAD_RESERVE);
+    return reserve > 0 && ncu - reserve >= 64 ? ncu - reserve : ncu;
 }
+// the Q8 kernel is selected from this many 256^2 work items up (measured: 150 tiles on 256 CUs still beat the 128^2 kernel by 10-20 %)
+static long q8_min_items() {
+    const int v = ecamp_opt(OPT_Q8_MIN_ITEMS);
+    return v == OPT_AUTO ? (long)(0.5 * p8_num_cu()) : v;
+}
+// weight-gradient GEMMs: work items (tiles x split-K slices) the split is chosen for.  A slice costs an M x N f32 slab written and
+// re-read, so fewer, longer items are cheaper per FLOP; on the side stream the rest of the chip is busy with the data-gradient chain
+// anyway.
+static long wgrad_target_items(int ncu) {
+    const int v = ecamp_opt(OPT_WGRAD_ITEMS);
+    return v > 0 ? v : ncu;
+}
+
+static long g_q8_launches = 0, g_q16_launches = 0, g_f8_q8_launches = 0, g_wg_launches = 0;
+extern "C" int64_t ecamp_gemm_q8_launches(void) { return g_q8_launches; }
+extern "C" int64_t ecamp_gemm_q16_launches(void) { return g_q16_launches; }
+extern "C" int64_t ecamp_gemm_f8_q8_launches(void) { return g_f8_q8_launches; }
+extern "C" int64_t ecamp_wgrad_group_launches(void) { return g_wg_launches; }
+
+// ---- the persistent launch: min(items, cap) workgroups of `block` threads with the whole 160 KB LDS of a CU, which a kernel has to be
+// allowed once (Q8, Q16, the e4m3 form and the item-table form)
+static void persistent_lds_optin(const void* fn) {
+    static const void* seen[64];
+    static int n_seen = 0;
+    for (int i = 0; i < n_seen; ++i)
+        if (seen[i] == fn) return;
+    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 10 * Q8_HALF);
+    if (n_seen < 64) seen[n_seen++] = fn;
+}
+template <typename... Args>
+static void launch_persistent(void (*fn)(Args...), long items, long cap, int block, hipStream_t stream, Args... args) {
+    persistent_lds_optin(reinterpret_cast<const void*>(fn));
+    hipLaunchKernelGGL(fn, dim3((unsigned)(items < cap ? items : cap)), dim3(block), 10 * Q8_HALF, stream, args...);
+}
+
+// the neutral argument block of a dense C[M,N] = A . B: no epilogue, unit scales, one K slice, the 128^2 tile grid
+static GemmArgs gemm_args(const void* A, const void* B, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc) {
+    GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.A = A; g.B = B; g.C = C;
+    g.M = (int)M; g.N = (int)N; g.K = (int)K;
+    g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+    g.alpha = 1.0f; g.alpha_out = 1.0f;
+    g.k_per_split = (int)K; g.nsplit = 1;
+    g.nbm = ceil_div(M, BM); g.nbn = ceil_div(N, BN);
+    return g;
+}
+// Operands past 2 GB are run as two calls over halves of the rows (or of the contraction), so that each half meets the 32-bit buffer
+// offsets of the persistent kernels: the first half in whole 256-row tiles, the second from `at_row` on
+static int64_t first_half(int64_t rows) { return (rows / 2 + 255) / 256 * 256; }
+static const void* at_row(const void* p, int64_t r, int64_t ld, int64_t es) { return p ? (const void*)((const char*)p + r * ld * es) : nullptr; }
+static const long LIM_2GB = 0x7fffffffl;
+static bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+
+static void splitk_reduce(const float* ws, void* C, int64_t M, int64_t N, int64_t ldc, int split_k, float alpha, const float* alpha_dev, int accumulate,
+                          hipStream_t stream) {
+    const long n4 = M * N / 4;
+    int nb = (int)((n4 + 255) / 256);
+    if (nb > 2048) nb = 2048;
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(nb), dim3(256), 0, stream, ws, reinterpret_cast<float*>(C), (long)M, (long)N, (long)ldc, split_k, alpha, alpha_dev,
+                       accumulate);
+}
+
+static void launch_t128(void (*fn)(GemmArgs), const GemmArgs& g, hipStream_t stream) {
+    hipLaunchKernelGGL(fn, dim3(g.nbm * g.nbn, 1, g.nsplit), dim3(256), 0, stream, g);
+}
+
+// ---- kernel selection ------------------------------------------------------------------------------------------
+typedef void (*gemm_fn)(GemmArgs);
+// the 128^2 kernels: every shape and alignment ecamp_gemm accepts
+static gemm_fn t128_pick(int dtype, int a_kc, int b_kc, bool rowsum, bool res32) {
+    if (res32) return gemm_bf16_kernel<true, true, false, true>;
+#define T128(KERN)                                                                                                                         \
+    (a_kc && b_kc ? (gemm_fn)KERN<true, true, false> : a_kc ? (gemm_fn)KERN<true, false, false> : b_kc ? (gemm_fn)KERN<false, true, false> \
+                                                     : rowsum ? (gemm_fn)KERN<false, false, true> : (gemm_fn)KERN<false, false, false>)
+    return dtype == ECAMP_BF16 ? T128(gemm_bf16_kernel) : T128(gemm_f32_kernel);
+#undef T128
+}
+// Q8 (gemm_q8.h): the persistent eight-wave 256x256x64 kernel; switch "q8_mode".
 // epilogue variant of a call (-1: none fits); res32: the residual is f32 (ecamp_gemm_res32)
-static int q8_epi(const float* bias, const void* residual, const void* pre_out, const void* gmul, int act, int out_f32, bool res32) {
-    if (res32) return (out_f32 && residual && !pre_out && !gmul && !act) ? 5 : -1;
-    if (out_f32) return (!bias && !residual && !pre_out && !gmul && !act) ? 4 : -1;
-    if (gmul) return (!bias && !pre_out && (act == 0 || act == 2)) ? 3 : -1;
-    if (pre_out || act) return (pre_out && (act == 1 || act == 2) && !residual) ? 1 : -1;
-    if (residual) return 2;
+static int q8_epi(const GemmArgs& g, bool res32) {
+    if (res32) return (g.out_f32 && g.residual && !g.pre_out && !g.gmul && !g.act) ? 5 : -1;
+    if (g.out_f32) return (!g.bias && !g.residual && !g.pre_out && !g.gmul && !g.act) ? 4 : -1;
+    if (g.gmul) return (!g.bias && !g.pre_out && (g.act == 0 || g.act == 2)) ? 3 : -1;
+    if (g.pre_out || g.act) return (g.pre_out && (g.act == 1 || g.act == 2) && !g.residual) ? 1 : -1;
+    if (g.residual) return 2;
     return 0;
 }
-static long g_q8_launches = 0;
-extern "C" int64_t ecamp_gemm_q8_launches(void) { return g_q8_launches; }
-typedef void (*q8_fn)(GemmArgs);
-// "q8_sch" (development A/B; env ECAMP_Q8_SCH): bit 0 forward form, bit 1 data-gradient form, bit 2 weight-gradient form, bit 3 the
-// grouped weight gradients on the lean stream (gemm_q8.h SCH = 1) instead of the round-3 stream
-static int g_q8_sch = -1;
-static int q8_sch() {
-    static const int v = getenv("ECAMP_Q8_SCH") ? atoi(getenv("ECAMP_Q8_SCH")) : 7;
-    return g_q8_sch >= 0 ? g_q8_sch : v;
-}
-static q8_fn q8_pick(int a_kc, int b_kc, int epi, bool rowsum) {
-    const int sch = q8_sch();
-#define Q8S(A, B, E, R) ((q8_fn)gemm_bf16_q8_kernel<A, B, E, 0, R, 1>)
+// switch "q8_sch" picks the operand stream of each form (gemm_q8.h SCH = 1: the lean stream)
+static gemm_fn q8_pick(int a_kc, int b_kc, int epi, bool rowsum) {
+    const int sch = ecamp_opt(OPT_Q8_SCH);
+#define Q8S(A, B, E, R) ((gemm_fn)gemm_bf16_q8_kernel<A, B, E, 0, R, 1>)
     if (a_kc && b_kc && (sch & 1)) return epi == 0 ? Q8S(true, true, 0, false) : epi == 1 ? Q8S(true, true, 1, false) : epi == 2 ? Q8S(true, true, 2, false) :
-                                          epi == 5 ? Q8S(true, true, 5, false) : (q8_fn) nullptr;
-    if (a_kc && !b_kc && (sch & 2)) return epi == 0 ? Q8S(true, false, 0, false) : epi == 2 ? Q8S(true, false, 2, false) : epi == 3 ? Q8S(true, false, 3, false) : (q8_fn) nullptr;
+                                          epi == 5 ? Q8S(true, true, 5, false) : (gemm_fn) nullptr;
+    if (a_kc && !b_kc && (sch & 2)) return epi == 0 ? Q8S(true, false, 0, false) : epi == 2 ? Q8S(true, false, 2, false) : epi == 3 ? Q8S(true, false, 3, false) : (gemm_fn) nullptr;
     if (!a_kc && !b_kc && epi == 4 && (sch & 4)) return rowsum ? Q8S(false, false, 4, true) : Q8S(false, false, 4, false);
 #undef Q8S
-    if (a_kc && b_kc) return epi == 0 ? gemm_bf16_q8_kernel<true, true, 0> : epi == 1 ? gemm_bf16_q8_kernel<true, true, 1> : epi == 2 ? gemm_bf16_q8_kernel<true, true, 2> : (q8_fn) nullptr;
-    if (a_kc && !b_kc) return epi == 0 ? gemm_bf16_q8_kernel<true, false, 0> : epi == 2 ? gemm_bf16_q8_kernel<true, false, 2> : epi == 3 ? gemm_bf16_q8_kernel<true, false, 3> : (q8_fn) nullptr;
+    if (a_kc && b_kc) return epi == 0 ? gemm_bf16_q8_kernel<true, true, 0> : epi == 1 ? gemm_bf16_q8_kernel<true, true, 1> : epi == 2 ? gemm_bf16_q8_kernel<true, true, 2> : (gemm_fn) nullptr;
+    if (a_kc && !b_kc) return epi == 0 ? gemm_bf16_q8_kernel<true, false, 0> : epi == 2 ? gemm_bf16_q8_kernel<true, false, 2> : epi == 3 ? gemm_bf16_q8_kernel<true, false, 3> : (gemm_fn) nullptr;
     if (!a_kc && !b_kc && epi == 4) return rowsum ? gemm_bf16_q8_kernel<false, false, 4, 0, true> : gemm_bf16_q8_kernel<false, false, 4, 0, false>;
     return nullptr;
 }
-static bool q8_legal(const void* A, const void* B, const void* C, int64_t M, int64_t N, int64_t K, int a_kc, int64_t lda, int b_kc, int64_t ldb, int64_t ldc,
-                     const float* bias, const void* residual, int64_t ldr, const void* pre_out, int64_t ldp, const void* gmul, int64_t ldg, int act,
-                     int dtype, int out_f32, int split_k, const float* splitk_ws, const float* rowsum, bool res32) {
+// `g` as gemm_call fills it (nsplit = the rounded split count, partial = the split-K workspace)
+static bool q8_legal(const GemmArgs& g, int a_kc, int b_kc, int dtype, bool res32) {
     if (dtype != ECAMP_BF16) return false;
-    const int epi = q8_epi(bias, residual, pre_out, gmul, act, out_f32, res32);
-    if (epi < 0 || !q8_pick(a_kc, b_kc, epi, rowsum != nullptr)) return false;
-    if (split_k < 1) split_k = 1;
+    const int epi = q8_epi(g, res32), split_k = g.nsplit;
+    if (epi < 0 || !q8_pick(a_kc, b_kc, epi, g.rowsum != nullptr)) return false;
     if (split_k > 1 && epi != 4) return false;
+    const long M = g.M, N = g.N, K = g.K;
     long kps = (K + split_k - 1) / split_k;
     kps = (kps + 63) / 64 * 64;
     const long ns = (K + kps - 1) / kps, last = K - (ns - 1) * kps;
     if (kps < 128 || last <= 64) return false;   // every work item (the last slice included) has at least two K tiles
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    const long lim = 0x7fffffffl;
-    if (N % 8 || lda % 8 || ldb % 8 || !al16(A) || !al16(B) || !al16(C)) return false;
-    if ((a_kc ? M * lda : K * lda) * 2 > lim || (b_kc ? N * ldb : K * ldb) * 2 > lim) return false;
+    if (N % 8 || g.lda % 8 || g.ldb % 8 || !al16(g.A) || !al16(g.B) || !al16(g.C)) return false;
+    if ((a_kc ? M * g.lda : K * g.lda) * 2 > LIM_2GB || (b_kc ? N * g.ldb : K * g.ldb) * 2 > LIM_2GB) return false;
     if (!a_kc && M % 8) return false;
-    if (split_k > 1) { if (!al16(splitk_ws) || (long)split_k * M * N * 4 > lim) return false; }
-    else if (ldc % 8 || M * ldc * (epi >= 4 ? 4 : 2) > lim) return false;
-    if (bias && !al16(bias)) return false;
-    if (pre_out && (ldp % 8 || !al16(pre_out) || M * ldp * 2 > lim)) return false;
-    if (gmul && (ldg % 8 || !al16(gmul) || M * ldg * 2 > lim)) return false;
-    if (residual && (ldr % 8 || !al16(residual) || M * ldr * (res32 ? 4 : 2) > lim)) return false;
+    if (split_k > 1) { if (!al16(g.partial) || (long)split_k * M * N * 4 > LIM_2GB) return false; }
+    else if (g.ldc % 8 || M * g.ldc * (epi >= 4 ? 4 : 2) > LIM_2GB) return false;
+    if (g.bias && !al16(g.bias)) return false;
+    if (g.pre_out && (g.ldp % 8 || !al16(g.pre_out) || M * g.ldp * 2 > LIM_2GB)) return false;
+    if (g.gmul && (g.ldg % 8 || !al16(g.gmul) || M * g.ldg * 2 > LIM_2GB)) return false;
+    if (g.residual && (g.ldr % 8 || !al16(g.residual) || M * g.ldr * (res32 ? 4 : 2) > LIM_2GB)) return false;
     return true;
 }
-
-// ---- Q16 (gemm_q16.h): four waves on the 16x16x32 MFMA, forward and data-gradient forms, 256- or 192-column tiles.
-// "q16_mode" (env ECAMP_Q16): 0 never; 1 (default) where the 192-column tile removes idle last-round time (the 768-wide outputs of the model);
-// 2 every eligible call, with the tile width the round count favours; 3 (tests) as 2 whatever the size
-static int g_q16_mode = -1;
-static int q16_mode() {
-    static const int v = getenv("ECAMP_Q16") ? atoi(getenv("ECAMP_Q16")) : 1;
-    return g_q16_mode >= 0 ? g_q16_mode : v;
-}
-static long g_q16_launches = 0;
-extern "C" int64_t ecamp_gemm_q16_launches(void) { return g_q16_launches; }
-// rounds of the chip a launch needs with TN-column tiles, in units of one 256 x 256 tile's time (a 256 x 192 tile costs ~0.79 of it:
+// Q16 (gemm_q16.h): four waves on the 16x16x32 MFMA, forward and data-gradient forms, 256- or 192-column tiles; switch "q16_mode".
+// Rounds of the chip a launch needs with TN-column tiles, in units of one 256 x 256 tile's time (a 256 x 192 tile costs ~0.79 of it:
 // tools/gemm_lab, profiles/r05_vendor_vs_q8.txt)
 static double q16_cost(int64_t M, int64_t N, int tn, int ncu) {
     const long tiles = (long)ceil_div(M, 256) * ceil_div(N, tn);
     return (double)((tiles + ncu - 1) / ncu) * (tn == 192 ? 0.79 : 1.0);
 }
-typedef void (*q16_fn)(GemmArgs);
-static q16_fn q16_pick(int b_kc, int epi, int nw) {
-    if (epi == 5) return b_kc ? (nw == 8 ? (q16_fn)gemm_bf16_q16_kernel<5, 8, true> : (q16_fn)gemm_bf16_q16_kernel<5, 6, true>) : (q16_fn) nullptr;
+static gemm_fn q16_pick(int b_kc, int epi, int nw) {
+    if (epi == 5) return b_kc ? (nw == 8 ? (gemm_fn)gemm_bf16_q16_kernel<5, 8, true> : (gemm_fn)gemm_bf16_q16_kernel<5, 6, true>) : (gemm_fn) nullptr;
     if (b_kc) {
-        if (nw == 8) return epi == 0 ? (q16_fn)gemm_bf16_q16_kernel<0, 8, true> : (q16_fn)gemm_bf16_q16_kernel<2, 8, true>;
-        return epi == 0 ? (q16_fn)gemm_bf16_q16_kernel<0, 6, true> : (q16_fn)gemm_bf16_q16_kernel<2, 6, true>;
+        if (nw == 8) return epi == 0 ? (gemm_fn)gemm_bf16_q16_kernel<0, 8, true> : (gemm_fn)gemm_bf16_q16_kernel<2, 8, true>;
+        return epi == 0 ? (gemm_fn)gemm_bf16_q16_kernel<0, 6, true> : (gemm_fn)gemm_bf16_q16_kernel<2, 6, true>;
     }
-    if (nw == 8) return epi == 0 ? (q16_fn)gemm_bf16_q16_kernel<0, 8, false> : (q16_fn)gemm_bf16_q16_kernel<2, 8, false>;
-    return epi == 0 ? (q16_fn)gemm_bf16_q16_kernel<0, 6, false> : (q16_fn)gemm_bf16_q16_kernel<2, 6, false>;
+    if (nw == 8) return epi == 0 ? (gemm_fn)gemm_bf16_q16_kernel<0, 8, false> : (gemm_fn)gemm_bf16_q16_kernel<2, 8, false>;
+    return epi == 0 ? (gemm_fn)gemm_bf16_q16_kernel<0, 6, false> : (gemm_fn)gemm_bf16_q16_kernel<2, 6, false>;
 }
 
-extern "C" int ecamp_set_option(const char* name, int32_t value) {
-    ECAMP_CHECK_ARG(name != nullptr, "set_option: null name");
-    if (strcmp(name, "q16_mode") == 0) { g_q16_mode = (value >= 0 && value <= 3) ? value : -1; return 0; }
-    if (strcmp(name, "q8_mode") == 0) { g_q8_mode = (value == 0 || value == 2) ? value : -1; return 0; }   // -1 auto, 0 never, 2 whenever legal
-    if (strcmp(name, "p8_wgrad") == 0) { g_p8_wgrad = value ? 1 : 0; return 0; }
-    if (strcmp(name, "p8_wgrad_reserve_cus") == 0) { g_p8_wgrad_reserve = value < 0 ? 0 : value; return 0; }
-    if (strcmp(name, "q8_bwd_grid") == 0) { g_q8_bwd_grid = value < 0 ? 0 : value; return 0; }
-    if (strcmp(name, "q8_sch") == 0) { g_q8_sch = value; return 0; }
-    if (strcmp(name, "attn_head") == 0) { attn_set_head_mode(value); return 0; }   // attention_bf16.hip: 1 head kernels (default), 0 streaming kernels
-    return ecamp_set_error(-1, "set_option: unknown option '%s'", name);
-}
-
-// the Q8 kernel is selected from this many 256^2 work items up (measured: 150 tiles on 256 CUs still beat the 128^2 kernel by 10-20 %)
-static long q8_min_items() {
-    static const long v = getenv("ECAMP_Q8_MIN_ITEMS") ? atol(getenv("ECAMP_Q8_MIN_ITEMS")) : (long)(0.5 * p8_num_cu());
-    return v;
-}
-// weight-gradient GEMMs: work items (tiles x split-K slices) the split is chosen for.  A slice costs an M x N f32 slab written and
-// re-read, so fewer, longer items are cheaper per FLOP; on the side stream the rest of the chip is busy with the data-gradient chain
-// anyway.  ECAMP_WGRAD_ITEMS overrides (development).
-static long wgrad_target_items(int ncu) {
-    static const long v = getenv("ECAMP_WGRAD_ITEMS") ? atol(getenv("ECAMP_WGRAD_ITEMS")) : 0;
-    return v > 0 ? v : ncu;
+// What serves one ecamp_gemm / ecamp_gemm_res32 call.  The profiler tag is name:form:e<epi>:M:N:K:<tail><n> with n the split count
+// (tail 's') or the tile width (tail 'w'); tools/gemm_in_step.py and the ecamp_prof_dump consumers parse it.
+enum GemmFamily { GEMM_T128, GEMM_Q8, GEMM_Q16 };
+struct GemmChoice {
+    GemmFamily family;
+    gemm_fn fn;
+    int tm, tn;     // output tile
+    int block;      // threads per workgroup
+    long cap;       // persistent families: workgroups at most (each walks its share of the items)
+    const char* name;
+    char form, epi, tail;   // form: f = forward x w^T, d = data gradient dy w, w = weight gradient dy^T x
+};
+// Chooses the kernel for the call `g` describes; reads switches and the CU count, changes nothing.
+static GemmChoice gemm_select(const GemmArgs& g, int a_kc, int b_kc, int dtype, bool res32) {
+    const char form = a_kc && b_kc ? 'f' : a_kc ? 'd' : 'w';
+    GemmChoice c = {GEMM_T128, t128_pick(dtype, a_kc, b_kc, g.rowsum != nullptr, res32), BM, BN, 256, 0, "t128", form, '-', 's'};
+    // the persistent kernels: from q8_min_items() work items up ("q16_mode" 3, the tests', whatever the size), where Q8 is legal
+    const int q8m = ecamp_opt(OPT_Q8_MODE), m16 = ecamp_opt(OPT_Q16_MODE);
+    const long items8 = (long)ceil_div(g.M, 256) * ceil_div(g.N, 256) * g.nsplit;
+    if (q8m == 0 || !(q8m == 2 || items8 >= q8_min_items() || m16 == 3) || !(a_kc || b_kc || ecamp_opt(OPT_P8_WGRAD)) || !q8_legal(g, a_kc, b_kc, dtype, res32))
+        return c;
+    const int epi = q8_epi(g, res32), ncu = p8_num_cu();
+    c.epi = (char)('0' + epi);
+    // "q8_bwd_grid" = n > 0 launches the DATA-GRADIENT form on min(items, n) workgroups instead of one per CU; n >= items gives one
+    // output tile per workgroup, i.e. the hardware dispatcher hands tiles to whichever CU is free.  That is what the data-parallel
+    // wrapper asks for: beside RCCL's all-reduce workgroups a persistent workgroup whose CU is taken starts late and holds its whole
+    // static share of the tiles back, while one-tile workgroups simply flow around the occupied CUs.  Measured cost on a GPU of its
+    // own (tools/grid_ab.sh): +0.15 ms per step for the data-gradient form (+0.4 ms if the forward form did the same, which it does not
+    // need: nothing communicates during forward) -- the cross-tile DMA prefetch of the persistent loop is worth that much and no more.
+    const int bwd_grid = a_kc && !b_kc ? ecamp_opt(OPT_Q8_BWD_GRID) : 0;
+    // Q16: forward / data-gradient forms with a plain, bias or residual epilogue (same legality as Q8: 16-B alignment, < 2 GB)
+    if (m16 > 0 && a_kc && (epi == 0 || epi == 2 || epi == 5) && g.nsplit == 1 && !g.rowsum && (b_kc || g.ldb % 8 == 0)) {
+        const double c256 = q16_cost(g.M, g.N, 256, ncu), c192 = q16_cost(g.M, g.N, 192, ncu);
+        // (the 192-column tile only where it removes a good part of a round: the report side's qkv projection -- 6.0 rounds of
+        // 3/4-size tiles against 4.5 -> 5 -- measured 8 % SLOWER inside the step, profiles/r05_gemm_in_step_vs_lab.txt)
+        const int nw = c192 <= 0.9 * c256 ? 6 : 8;
+        if (m16 >= 2 || nw == 6) {
+            c.family = GEMM_Q16; c.fn = q16_pick(b_kc, epi, nw); c.tm = 256; c.tn = nw * 32; c.block = 256; c.name = "q16"; c.tail = 'w';
+            c.cap = bwd_grid > 0 ? bwd_grid : ncu;
+            return c;
+        }
+    }
+    c.family = GEMM_Q8; c.fn = q8_pick(a_kc, b_kc, epi, g.rowsum != nullptr); c.tm = 256; c.tn = 256; c.block = 512; c.name = "q8";
+    c.cap = bwd_grid > 0 ? bwd_grid : a_kc && b_kc ? ncu : p8_bwd_cus();
+    return c;
 }
 
 extern "C" int ecamp_gemm_suggest_split(int64_t M, int64_t N, int64_t K, int a_kc, int b_kc, int dtype) {
     if (M <= 0 || N <= 0 || K <= 0) return 1;
-    int ncu = p8_num_cu();
-    if (!(a_kc && b_kc) && g_p8_wgrad_reserve > 0 && ncu - g_p8_wgrad_reserve >= 64) ncu -= g_p8_wgrad_reserve;   // as the launch does
+    const int ncu = a_kc && b_kc ? p8_num_cu() : p8_bwd_cus();   // as the launch does
     // 128^2 kernel: about four resident workgroups per CU
     const long tiles = (long)ceil_div(M, 128) * ceil_div(N, 128);
     long s_old = 1024 / tiles;
     if (s_old < 1) s_old = 1;
     const long cap = (K + 255) / 256;
     if (s_old > cap) s_old = cap;
-    if (dtype != ECAMP_BF16 || q8_env() == 0 || (a_kc != 0) != (b_kc != 0) || (!a_kc && !b_kc && !g_p8_wgrad)) return (int)s_old;
+    if (dtype != ECAMP_BF16 || ecamp_opt(OPT_Q8_MODE) == 0 || (a_kc != 0) != (b_kc != 0) || (!a_kc && !b_kc && !ecamp_opt(OPT_P8_WGRAD))) return (int)s_old;
     // persistent 256^2 kernel: one workgroup per CU walks the work items; pick the split count whose item count fills whole
     // rounds of the chip, preferring fewer splits (each split writes and re-reads an M x N f32 slab)
     const long t8 = (long)ceil_div(M, 256) * ceil_div(N, 256);
@@ -875,170 +857,59 @@ static int gemm_call(const void* A, const void* B, void* C, int64_t M, int64_t N
     ECAMP_CHECK_ARG(split_k == 1 || splitk_ws, "ecamp_gemm: split_k > 1 requires a workspace of split_k*M*N floats");
     ECAMP_CHECK_ARG(split_k == 1 || (!bias && !residual && !pre_out && !gmul && !act), "ecamp_gemm: split-K has no epilogue");
 
-    // Row-contiguous forms whose [M, ld] operands pass 2 GB (the vocabulary projection at B = 512: 65536 x 30000 bf16) are run as
-    // two calls over row halves, so that each half meets the 32-bit buffer offsets of the persistent kernels (q8_legal).
+    // Row-contiguous forms whose [M, ld] operands pass 2 GB (the vocabulary projection at B = 512: 65536 x 30000 bf16): two calls over row halves
     if (a_kc && dtype == ECAMP_BF16 && split_k == 1 && !rowsum && M >= 512) {
-        const long lim = 0x7fffffffl, esz = out_f32 ? 4 : 2, rsz = res32 ? 4 : 2;
-        const bool big = M * ldc * esz > lim || M * lda * 2 > lim || (residual && M * ldr * rsz > lim) || (pre_out && M * ldp * 2 > lim) || (gmul && M * ldg * 2 > lim);
-        if (big) {
-            const int64_t m1 = (M / 2 + 255) / 256 * 256;
-            auto rows = [](const void* p, int64_t r, int64_t ld, int64_t es) { return p ? (const void*)((const char*)p + r * ld * es) : nullptr; };
+        const long esz = out_f32 ? 4 : 2, rsz = res32 ? 4 : 2;
+        if (M * ldc * esz > LIM_2GB || M * lda * 2 > LIM_2GB || (residual && M * ldr * rsz > LIM_2GB) || (pre_out && M * ldp * 2 > LIM_2GB) ||
+            (gmul && M * ldg * 2 > LIM_2GB)) {
+            const int64_t m1 = first_half(M);
             int rc = gemm_call(A, B, C, m1, N, K, a_kc, lda, b_kc, ldb, ldc, bias, residual, ldr, pre_out, ldp, gmul, ldg, act, alpha, alpha_dev, dtype,
                                out_f32, accumulate, 1, nullptr, nullptr, stream, res32);
             if (rc) return rc;
-            return gemm_call(rows(A, m1, lda, 2), B, (void*)rows(C, m1, ldc, esz), M - m1, N, K, a_kc, lda, b_kc, ldb, ldc, bias, rows(residual, m1, ldr, rsz), ldr,
-                             (void*)rows(pre_out, m1, ldp, 2), ldp, rows(gmul, m1, ldg, 2), ldg, act, alpha, alpha_dev, dtype, out_f32, accumulate, 1, nullptr,
+            return gemm_call(at_row(A, m1, lda, 2), B, (void*)at_row(C, m1, ldc, esz), M - m1, N, K, a_kc, lda, b_kc, ldb, ldc, bias, at_row(residual, m1, ldr, rsz), ldr,
+                             (void*)at_row(pre_out, m1, ldp, 2), ldp, at_row(gmul, m1, ldg, 2), ldg, act, alpha, alpha_dev, dtype, out_f32, accumulate, 1, nullptr,
                              nullptr, stream, res32);
         }
     }
     // ... and the weight-gradient form whose [K, ld] operands pass 2 GB as two calls over halves of the contraction, the second accumulating
-    if (!a_kc && !b_kc && dtype == ECAMP_BF16 && out_f32 && K >= 1024) {
-        const long lim = 0x7fffffffl;
-        if (K * lda * 2 > lim || K * ldb * 2 > lim) {
-            const int64_t k1 = (K / 2 + 255) / 256 * 256;
-            int rc = gemm_call(A, B, C, M, N, k1, a_kc, lda, b_kc, ldb, ldc, bias, residual, ldr, pre_out, ldp, gmul, ldg, act, alpha, alpha_dev, dtype, out_f32,
-                               accumulate, split_k, splitk_ws, rowsum, stream, res32);
-            if (rc) return rc;
-            return gemm_call((const char*)A + k1 * lda * 2, (const char*)B + k1 * ldb * 2, C, M, N, K - k1, a_kc, lda, b_kc, ldb, ldc, bias, residual, ldr, pre_out, ldp,
-                             gmul, ldg, act, alpha, alpha_dev, dtype, out_f32, 1, split_k, splitk_ws, rowsum, stream, res32);
-        }
+    if (!a_kc && !b_kc && dtype == ECAMP_BF16 && out_f32 && K >= 1024 && (K * lda * 2 > LIM_2GB || K * ldb * 2 > LIM_2GB)) {
+        const int64_t k1 = first_half(K);
+        int rc = gemm_call(A, B, C, M, N, k1, a_kc, lda, b_kc, ldb, ldc, bias, residual, ldr, pre_out, ldp, gmul, ldg, act, alpha, alpha_dev, dtype, out_f32,
+                           accumulate, split_k, splitk_ws, rowsum, stream, res32);
+        if (rc) return rc;
+        return gemm_call(at_row(A, k1, lda, 2), at_row(B, k1, ldb, 2), C, M, N, K - k1, a_kc, lda, b_kc, ldb, ldc, bias, residual, ldr, pre_out, ldp,
+                         gmul, ldg, act, alpha, alpha_dev, dtype, out_f32, 1, split_k, splitk_ws, rowsum, stream, res32);
     }
 
-    GemmArgs g;
-    g.dbg = 0; g.wide = 0; g.nsplit = 1;
-    g.A = A; g.B = B; g.C = C;
-    g.M = (int)M; g.N = (int)N; g.K = (int)K;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+    GemmArgs g = gemm_args(A, B, C, M, N, K, lda, ldb, ldc);
     g.bias = bias; g.residual = residual; g.ldr = ldr; g.pre_out = pre_out; g.ldp = ldp; g.gmul = gmul; g.ldg = ldg;
-    g.alpha = alpha;
-    g.alpha_dev = alpha_dev;
-    g.alpha_dev2 = nullptr;
-    g.q8_out = nullptr; g.q8_scale = nullptr; g.q8_amax = nullptr;
-    g.alpha_out = alpha;
-    g.alpha_dev_out = alpha_dev;
+    g.alpha = g.alpha_out = alpha;
+    g.alpha_dev = g.alpha_dev_out = alpha_dev;
     g.rowsum = rowsum;
     g.act = act; g.out_f32 = (out_f32 || dtype == ECAMP_F32) ? 1 : 0; g.accumulate = accumulate;
-    const int ktile = dtype == ECAMP_BF16 ? BK : FK;
+    const int ktile = dtype == ECAMP_BF16 ? BK : FK;   // whole K tiles per slice: the split count only ever goes down
     long kps = (K + split_k - 1) / split_k;
     kps = ((kps + ktile - 1) / ktile) * ktile;
     split_k = (int)((K + kps - 1) / kps);
-    g.k_per_split = (int)kps;
-    g.partial = split_k > 1 ? splitk_ws : nullptr;
-    if (split_k > 1) { g.alpha = 1.0f; g.alpha_dev = nullptr; }
-    g.nbm = ceil_div(M, BM); g.nbn = ceil_div(N, BN);
-    dim3 grid(g.nbm * g.nbn, 1, split_k), block(256);
-    {
-        const int q8m = q8_env();
-        const long items8 = (long)ceil_div(M, 256) * ceil_div(N, 256) * split_k;
-        if (q8m != 0 && (q8m == 2 || items8 >= q8_min_items() || q16_mode() == 3) && (a_kc || b_kc || g_p8_wgrad) &&
-            q8_legal(A, B, C, M, N, K, a_kc, lda, b_kc, ldb, ldc, bias, residual, ldr, pre_out, ldp, gmul, ldg, act, dtype, g.out_f32, split_k, splitk_ws, rowsum, res32)) {
-            const int epi = q8_epi(bias, residual, pre_out, gmul, act, g.out_f32, res32);
-            {   // Q16: forward / data-gradient forms with a plain, bias or residual epilogue (same legality as Q8: 16-B alignment, < 2 GB)
-                const int m16 = q16_mode(), ncu16 = p8_num_cu();
-                if (m16 > 0 && a_kc && (epi == 0 || epi == 2 || epi == 5) && split_k == 1 && !rowsum && (b_kc || ldb % 8 == 0)) {
-                    const double c256 = q16_cost(M, N, 256, ncu16), c192 = q16_cost(M, N, 192, ncu16);
-                    // (the 192-column tile only where it removes a good part of a round: the report side's qkv projection -- 6.0 rounds of
-                    // 3/4-size tiles against 4.5 -> 5 -- measured 8 % SLOWER inside the step, profiles/r05_gemm_in_step_vs_lab.txt)
-                    const int nw = c192 <= 0.9 * c256 ? 6 : 8;
-                    if (m16 >= 2 || nw == 6) {
-                        q16_fn f16 = q16_pick(b_kc, epi, nw);
-                        g.nbm = ceil_div(M, 256); g.nbn = ceil_div(N, nw * 32);
-                        g.nsplit = 1; g.wide = 1;
-                        const long total16 = (long)g.nbm * g.nbn;
-                        const size_t shm16 = 10 * Q8_HALF;
-                        static q16_fn attr16[16];
-                        static int n_attr16 = 0;
-                        bool seen16 = false;
-                        for (int i = 0; i < n_attr16; ++i) seen16 = seen16 || attr16[i] == f16;
-                        if (!seen16) {
-                            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(f16), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm16);
-                            if (n_attr16 < 16) attr16[n_attr16++] = f16;
-                        }
-                        const bool prof16 = ecamp_prof_active();
-                        if (prof16) {
-                            char tag[40];
-                            snprintf(tag, sizeof tag, "q16:%c:e%d:%ld:%ld:%ld:w%d", b_kc ? 'f' : 'd', epi, (long)M, (long)N, (long)K, nw * 32);
-                            ecamp_prof_begin(ECAMP_PROF_GEMM_BF16, 2.0 * (double)M * (double)N * (double)K, stream, tag);
-                        }
-                        long grid16 = ncu16;
-                        {   // data-gradient form beside a co-tenant: the same switch as the eight-wave kernel's (g_q8_bwd_grid below) -- with
-                            // it on, one output tile per workgroup and the hardware dispatcher deals the tiles
-                            static const int env_bwd16 = getenv("ECAMP_Q8_BWD_GRID") ? atoi(getenv("ECAMP_Q8_BWD_GRID")) : 0;
-                            const int bg16 = g_q8_bwd_grid > 0 ? g_q8_bwd_grid : env_bwd16;
-                            if (!b_kc && bg16 > 0) grid16 = bg16;
-                        }
-                        hipLaunchKernelGGL(f16, dim3((unsigned)(total16 < grid16 ? total16 : grid16)), dim3(256), shm16, stream, g);
-                        ++g_q16_launches;
-                        if (prof16) ecamp_prof_end(stream);
-                        ECAMP_LAUNCH_CHECK();
-                        return 0;
-                    }
-                }
-            }
-            q8_fn fn = q8_pick(a_kc, b_kc, epi, rowsum != nullptr);
-            g.nbm = ceil_div(M, 256); g.nbn = ceil_div(N, 256);
-            g.nsplit = split_k; g.wide = 1;
-            int ncu = p8_num_cu();
-            if (!(a_kc && b_kc) && g_p8_wgrad_reserve > 0 && ncu - g_p8_wgrad_reserve >= 64) ncu -= g_p8_wgrad_reserve;
-            const long total8 = (long)g.nbm * g.nbn * split_k;
-            const size_t shm = 10 * Q8_HALF;   // the whole 160 KB LDS of a CU
-            static q8_fn attr_done[32];
-            static int n_attr = 0;
-            bool seen = false;
-            for (int i = 0; i < n_attr; ++i) seen = seen || attr_done[i] == fn;
-            if (!seen) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-                if (n_attr < 32) attr_done[n_attr++] = fn;
-            }
-            const bool prof8 = ecamp_prof_active();
-            if (prof8) {   // tag: form (f = forward x w^T, d = data gradient dy w, w = weight gradient dy^T x), epilogue, M N K, split
-                char tag[40];
-                snprintf(tag, sizeof tag, "q8:%c:e%d:%ld:%ld:%ld:s%d", a_kc && b_kc ? 'f' : a_kc ? 'd' : 'w', epi, (long)M, (long)N, (long)K, split_k);
-                ecamp_prof_begin(ECAMP_PROF_GEMM_BF16, 2.0 * (double)M * (double)N * (double)K, stream, tag);
-            }
-            {   // data-gradient form beside a co-tenant (see g_q8_bwd_grid): the hardware dispatcher deals the items
-                static const int env_bwd = getenv("ECAMP_Q8_BWD_GRID") ? atoi(getenv("ECAMP_Q8_BWD_GRID")) : 0;
-                const int bg = g_q8_bwd_grid > 0 ? g_q8_bwd_grid : env_bwd;
-                if (a_kc && !b_kc && bg > 0) ncu = bg;
-            }
-            hipLaunchKernelGGL(fn, dim3((unsigned)(total8 < ncu ? total8 : ncu)), dim3(512), shm, stream, g);
-            ++g_q8_launches;
-            if (split_k > 1) {
-                long n4 = M * N / 4;
-                int nb = (int)((n4 + 255) / 256);
-                if (nb > 2048) nb = 2048;
-                hipLaunchKernelGGL(splitk_reduce_kernel, dim3(nb), dim3(256), 0, stream, splitk_ws, reinterpret_cast<float*>(C), (long)M, (long)N,
-                                   (long)ldc, split_k, alpha, alpha_dev, accumulate);
-            }
-            if (prof8) ecamp_prof_end(stream);
-            ECAMP_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-#define LAUNCH(KERN)                                                             \
-    do {                                                                         \
-        if (a_kc && b_kc) hipLaunchKernelGGL((KERN<true, true, false>), grid, block, 0, stream, g);        \
-        else if (a_kc && !b_kc) hipLaunchKernelGGL((KERN<true, false, false>), grid, block, 0, stream, g); \
-        else if (!a_kc && b_kc) hipLaunchKernelGGL((KERN<false, true, false>), grid, block, 0, stream, g); \
-        else if (rowsum) hipLaunchKernelGGL((KERN<false, false, true>), grid, block, 0, stream, g);        \
-        else hipLaunchKernelGGL((KERN<false, false, false>), grid, block, 0, stream, g);                   \
-    } while (0)
+    g.k_per_split = (int)kps; g.nsplit = split_k;
+    if (split_k > 1) { g.partial = splitk_ws; g.alpha = 1.0f; g.alpha_dev = nullptr; }   // the reduce applies the caller's scale
+
+    const GemmChoice c = gemm_select(g, a_kc, b_kc, dtype, res32);
+    g.nbm = ceil_div(M, c.tm); g.nbn = ceil_div(N, c.tn);
+    g.wide = c.family != GEMM_T128;
     const bool prof = ecamp_prof_active();
     if (prof) {
         char tag[40];
-        snprintf(tag, sizeof tag, "t128:%c:e-:%ld:%ld:%ld:s%d", a_kc && b_kc ? 'f' : a_kc ? 'd' : 'w', (long)M, (long)N, (long)K, split_k);
+        snprintf(tag, sizeof tag, "%s:%c:e%c:%ld:%ld:%ld:%c%d", c.name, c.form, c.epi, (long)M, (long)N, (long)K, c.tail, c.tail == 'w' ? c.tn : split_k);
         ecamp_prof_begin(dtype == ECAMP_BF16 ? ECAMP_PROF_GEMM_BF16 : ECAMP_PROF_GEMM_F32, 2.0 * (double)M * (double)N * (double)K, stream, tag);
     }
-    if (res32) hipLaunchKernelGGL((gemm_bf16_kernel<true, true, false, true>), grid, block, 0, stream, g);
-    else if (dtype == ECAMP_BF16) LAUNCH(gemm_bf16_kernel); else LAUNCH(gemm_f32_kernel);
-#undef LAUNCH
-    if (split_k > 1) {
-        long n4 = M * N / 4;
-        int nb = (int)((n4 + 255) / 256);
-        if (nb > 2048) nb = 2048;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(nb), dim3(256), 0, stream, splitk_ws, reinterpret_cast<float*>(C), (long)M, (long)N,
-                           (long)ldc, split_k, alpha, alpha_dev, accumulate);
+    if (c.family == GEMM_T128) {
+        launch_t128(c.fn, g, stream);
+    } else {
+        launch_persistent(c.fn, (long)g.nbm * g.nbn * split_k, c.cap, c.block, stream, g);
+        ++(c.family == GEMM_Q8 ? g_q8_launches : g_q16_launches);
     }
+    if (split_k > 1) splitk_reduce(splitk_ws, C, M, N, ldc, split_k, alpha, alpha_dev, accumulate, stream);
     if (prof) ecamp_prof_end(stream);
     ECAMP_LAUNCH_CHECK();
     return 0;
@@ -1062,6 +933,64 @@ extern "C" int ecamp_gemm_res32(const void* A, const void* B, float* C, int64_t 
                      nullptr, stream, true);
 }
 
+// ---- the e4m3 forward GEMM -----------------------------------------------------------------------------------------
+// The persistent 256 x 256 x 128 e4m3 form (gemm_q8.h, F8) from the same tile count up as the bf16 kernel, when its alignment / size
+// conditions hold; nullptr: the 128^2 kernel.  ECAMP_F8_Q8=0 keeps everything on the 128^2 kernel (development A/B).
+static gemm_fn f8_select(const GemmArgs& g) {
+    const int q8m = ecamp_opt(OPT_Q8_MODE);
+    const int epi = (g.pre_out || g.act) ? ((g.pre_out && (g.act == 1 || g.act == 2) && !g.residual) ? 1 : -1) : g.residual ? 2 : 0;
+    const long M = g.M, N = g.N, items8 = (long)ceil_div(M, 256) * ceil_div(N, 256);
+    const bool legal = ecamp_opt(OPT_F8_Q8) && q8m != 0 && epi >= 0 && g.K >= 256 && N % 8 == 0 && g.ldc % 8 == 0 && al16(g.A) && al16(g.B) && al16(g.C) &&
+                       M * g.lda <= LIM_2GB && N * g.ldb <= LIM_2GB && M * g.ldc * 2 <= LIM_2GB && (!g.bias || al16(g.bias)) &&
+                       (!g.pre_out || (g.ldp % 8 == 0 && al16(g.pre_out) && M * g.ldp * 2 <= LIM_2GB)) &&
+                       (!g.residual || (g.ldr % 8 == 0 && al16(g.residual) && M * g.ldr * 2 <= LIM_2GB));
+    if (!legal || !(q8m == 2 || items8 >= q8_min_items())) return nullptr;
+    return epi == 0 ? (gemm_fn)gemm_f8_q8_kernel<0> : epi == 1 ? (gemm_fn)gemm_f8_q8_kernel<1> : (gemm_fn)gemm_f8_q8_kernel<2>;
+}
+extern "C" int ecamp_gemm_fp8(const void* A8, const void* B8, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
+                              int64_t ldc, const float* scale_a, const float* scale_b, const float* bias, const void* residual,
+                              int64_t ldr, void* pre_out, int64_t ldp, int act, void* q8_out, const float* q8_scale, float* q8_amax_slots,
+                              hipStream_t stream) {
+    ECAMP_CHECK_ARG(!q8_out || (q8_scale && q8_amax_slots && (act == 1 || act == 2) && pre_out && !residual && ldc == N),
+                    "ecamp_gemm_fp8: the e4m3 copy of the output needs its scale and amax slots, the GELU epilogue and a dense C");
+    ECAMP_CHECK_ARG(A8 && B8 && C && scale_a && scale_b, "ecamp_gemm_fp8: null operand");
+    ECAMP_CHECK_ARG(act >= 0 && act <= 2 && (act != 2 || pre_out), "ecamp_gemm_fp8: act=%d (0 none, 1 GELU, 2 GELU with the saved derivative in pre_out)", act);
+    ECAMP_CHECK_ARG(M > 0 && N > 0 && K > 0, "ecamp_gemm_fp8: bad shape %ld %ld %ld", (long)M, (long)N, (long)K);
+    ECAMP_CHECK_ARG(K % 16 == 0 && lda % 16 == 0 && ldb % 16 == 0 && N % 4 == 0, "ecamp_gemm_fp8: K, lda, ldb must be multiples of 16 and N of 4");
+    // outputs past 2 GB (the vocabulary projection at B = 512: 65536 x 30000 bf16): two calls over row halves, as ecamp_gemm does
+    if (M >= 512 && !q8_out && (M * ldc * 2 > LIM_2GB || (residual && M * ldr * 2 > LIM_2GB) || (pre_out && M * ldp * 2 > LIM_2GB))) {
+        const int64_t m1 = first_half(M);
+        int rc = ecamp_gemm_fp8(A8, B8, C, m1, N, K, lda, ldb, ldc, scale_a, scale_b, bias, residual, ldr, pre_out, ldp, act, nullptr, nullptr, nullptr, stream);
+        if (rc) return rc;
+        return ecamp_gemm_fp8(at_row(A8, m1, lda, 1), B8, (void*)at_row(C, m1, ldc, 2), M - m1, N, K, lda, ldb, ldc, scale_a, scale_b, bias, at_row(residual, m1, ldr, 2),
+                              ldr, (void*)at_row(pre_out, m1, ldp, 2), ldp, act, nullptr, nullptr, nullptr, stream);
+    }
+    GemmArgs g = gemm_args(A8, B8, C, M, N, K, lda, ldb, ldc);
+    g.bias = bias; g.residual = residual; g.ldr = ldr; g.pre_out = pre_out; g.ldp = ldp;
+    g.act = act;
+    const gemm_fn q8 = f8_select(g);
+    const bool prof = ecamp_prof_active();
+    if (prof) ecamp_prof_begin(ECAMP_PROF_GEMM_FP8, 2.0 * (double)M * (double)N * (double)K, stream);
+    if (q8) {
+        g.nbm = ceil_div(M, 256); g.nbn = ceil_div(N, 256); g.wide = 1;
+        g.alpha_dev = scale_a; g.alpha_dev2 = scale_b;
+        g.q8_out = q8_out; g.q8_scale = q8_scale; g.q8_amax = q8_amax_slots;
+        launch_persistent(q8, (long)g.nbm * g.nbn, p8_num_cu(), 512, stream, g);
+        ++g_f8_q8_launches;
+    } else {
+        hipLaunchKernelGGL(gemm_fp8_kernel, dim3(g.nbm * g.nbn), dim3(256), 0, stream, g, scale_a, scale_b);
+    }
+    if (prof) ecamp_prof_end(stream);
+    if (q8_out && !q8) {   // the 128^2 kernel has no third output: one pass over C afterwards gives the same bytes
+        const long n4 = M * N / 4;
+        int nb = (int)((n4 + 255) / 256);
+        if (nb > 4096) nb = 4096;
+        hipLaunchKernelGGL(quant_fp8_delayed_kernel<bf16_t>, dim3(nb), dim3(256), 0, stream, (const bf16_t*)C, q8_scale, (unsigned int*)q8_out, q8_amax_slots, n4);
+    }
+    ECAMP_LAUNCH_CHECK();
+    return 0;
+}
+
 // =============================================================================================
 // Grouped weight gradients: the (up to four) dW_p (+)= alpha * dY_p^T X_p of one transformer block -- same contraction length
 // `rows`, different shapes and operands -- as ONE launch of the Q8 kernel's item-table form (gemm_q8.h, ITEMS) plus one grouped
@@ -1069,9 +998,6 @@ extern "C" int ecamp_gemm_res32(const void* A, const void* B, float* C, int64_t 
 // stores with nothing to overlap per ~90 us launch, and 7-28 slabs per output tile (256 MB written and re-read per encoder
 // block).  Here the K tiles of ALL tiles of the block are dealt out evenly, in order, to the workgroups (ranges run across
 // tile boundaries), so a tile has 2-4 slabs and a workgroup one ring fill per block.
-#include <map>
-#include <string>
-#include <vector>
 struct WgTile { int prob, m0, n0, first, count; };
 struct WgRedProb { float* C; long ldc; int M, N; float alpha; int accumulate; const float* alpha_dev; };
 struct WgRedArgs { const WgTile* tiles; const float* slabs; int ntiles, pad; WgRedProb p[4]; };
@@ -1112,10 +1038,18 @@ struct WgPlan {
 };
 static std::map<std::string, WgPlan> g_wg_plans;
 
+// output tiles of a group
+static long wg_tiles(int n, const int64_t* n_out, const int64_t* k_in) {
+    long tiles = 0;
+    for (int p = 0; p < n; ++p) tiles += (long)ceil_div(n_out[p], 256) * ceil_div(k_in[p], 256);
+    return tiles;
+}
+
 static const WgPlan* wg_plan(int n, const int64_t* n_out, const int64_t* k_in, const unsigned* has_bias, int64_t rows, int ncu) {
+    const int reserve = ecamp_opt(OPT_P8_WGRAD_RESERVE);   // caps the piece count (p8_bwd_cus)
     std::string key((const char*)n_out, n * sizeof(int64_t));
     key.append((const char*)k_in, n * sizeof(int64_t)).append((const char*)has_bias, n * sizeof(unsigned)).append((const char*)&rows, 8).append((const char*)&ncu, 4);
-    key.append((const char*)&g_p8_wgrad_reserve, sizeof(int));   // the reserve caps the piece count
+    key.append((const char*)&reserve, sizeof(int));
     auto it = g_wg_plans.find(key);
     if (it != g_wg_plans.end()) return &it->second;
     const long KT = (rows + 63) / 64;
@@ -1127,10 +1061,9 @@ static const WgPlan* wg_plan(int n, const int64_t* n_out, const int64_t* k_in, c
     std::vector<Q8ItemRec>& items = pl.items;
     std::vector<int>& first = pl.first;
     // ECAMP_WGRAD_PLAN=0: the round-2 dealing (K tiles of all tiles dealt out evenly in tile order; ranges run across tile boundaries)
-    static const int plan_mode = getenv("ECAMP_WGRAD_PLAN") ? atoi(getenv("ECAMP_WGRAD_PLAN")) : 1;
+    const int plan_mode = ecamp_opt(OPT_WGRAD_PLAN);
     const long T = (long)tiles.size();
-    int cap = p8_num_cu();                            // workgroups the launch may use: every CU, minus the data-parallel reserve
-    if (g_p8_wgrad_reserve > 0 && cap - g_p8_wgrad_reserve >= 64) cap -= g_p8_wgrad_reserve;
+    const int cap = p8_bwd_cus();                     // workgroups the launch may use: every CU, minus the data-parallel reserve
     long S = (ncu + T / 2) / T;                       // K segments per tile: one (tile, segment) piece per workgroup
     while (S > 1 && (T * S > cap || KT / S < 4)) --S;
     if (plan_mode == 1 && S >= 1 && T * S >= ncu / 2 && T * S <= cap) {
@@ -1188,33 +1121,25 @@ static const WgPlan* wg_plan(int n, const int64_t* n_out, const int64_t* k_in, c
 // workgroup on every CU that chain's kernels wait for whole 250-us items (39.7-39.9 ms per step against 39.4 with per-layer
 // launches), with 192 they do not (39.4-39.9 against 39.7-40.1 on the same boxes; 160: +0.6 ms, 64: +4 ms).  ECAMP_WGRAD_GROUP_CUS overrides.
 static int wg_ncu() {
-    static const int env = getenv("ECAMP_WGRAD_GROUP_CUS") ? atoi(getenv("ECAMP_WGRAD_GROUP_CUS")) : 0;
-    if (env > 0) return env < p8_num_cu() ? env : p8_num_cu();   // (the workspace is sized for at most one workgroup per CU)
-    int ncu = p8_num_cu();
-    if (g_p8_wgrad_reserve > 0 && ncu - g_p8_wgrad_reserve >= 64) ncu -= g_p8_wgrad_reserve;
-    const int q = p8_num_cu() * 3 / 4;
-    return ncu < q ? ncu : q;
+    const int env = ecamp_opt(OPT_WGRAD_GROUP_CUS), ncu = p8_num_cu();
+    if (env > 0) return env < ncu ? env : ncu;   // (the workspace is sized for at most one workgroup per CU)
+    const int bwd = p8_bwd_cus(), q = ncu * 3 / 4;
+    return bwd < q ? bwd : q;
 }
 // 1 if the group can run as one launch (otherwise the caller issues per-layer ecamp_gemm calls)
 extern "C" int ecamp_wgrad_group_supported(int32_t n, const int64_t* n_out, const int64_t* k_in, int64_t rows) {
     if (n < 1 || n > 4 || !n_out || !k_in || rows < 256) return 0;
-    long tiles = 0;
     for (int p = 0; p < n; ++p) {
         if (n_out[p] % 8 || k_in[p] % 8 || n_out[p] <= 0 || k_in[p] <= 0) return 0;
-        if (rows * n_out[p] * 2 > 0x7fffffffl || rows * k_in[p] * 2 > 0x7fffffffl) return 0;
-        tiles += (long)ceil_div(n_out[p], 256) * ceil_div(k_in[p], 256);
+        if (rows * n_out[p] * 2 > LIM_2GB || rows * k_in[p] * 2 > LIM_2GB) return 0;
     }
-    return tiles >= 16 ? 1 : 0;
+    return wg_tiles(n, n_out, k_in) >= 16 ? 1 : 0;
 }
 // bytes of `ws`: one 256 x 256 f32 slab per work item (0: not supported)
 extern "C" int64_t ecamp_wgrad_group_workspace_bytes(int32_t n, const int64_t* n_out, const int64_t* k_in, int64_t rows) {
     if (!ecamp_wgrad_group_supported(n, n_out, k_in, rows)) return 0;
-    long tiles = 0;
-    for (int p = 0; p < n; ++p) tiles += (long)ceil_div(n_out[p], 256) * ceil_div(k_in[p], 256);
-    return (tiles + p8_num_cu() + 1) * 262144;    // every workgroup boundary adds at most one piece
+    return (wg_tiles(n, n_out, k_in) + p8_num_cu() + 1) * 262144;    // every workgroup boundary adds at most one piece
 }
-static long g_wg_launches = 0;
-extern "C" int64_t ecamp_wgrad_group_launches(void) { return g_wg_launches; }
 // workgroups a grouped launch will use for the caller's `workgroups` argument (0 = the library's choice): part of the table's identity
 extern "C" int ecamp_wgrad_group_workgroups(int32_t workgroups) {
     if (workgroups > 0) return workgroups < p8_num_cu() ? workgroups : p8_num_cu();
@@ -1223,9 +1148,7 @@ extern "C" int ecamp_wgrad_group_workgroups(int32_t workgroups) {
 // upper bound of the item-table image for any workgroup count (0: group not supported)
 extern "C" int64_t ecamp_wgrad_group_table_bytes(int32_t n, const int64_t* n_out, const int64_t* k_in, int64_t rows) {
     if (!ecamp_wgrad_group_supported(n, n_out, k_in, rows)) return 0;
-    long tiles = 0;
-    for (int p = 0; p < n; ++p) tiles += (long)ceil_div(n_out[p], 256) * ceil_div(k_in[p], 256);
-    const long ncu = p8_num_cu();
+    const long tiles = wg_tiles(n, n_out, k_in), ncu = p8_num_cu();
     return (tiles + ncu + 1) * (long)sizeof(Q8ItemRec) + ((ncu + 2) * 4 + 31) / 32 * 32 + tiles * (long)sizeof(WgTile) + 64;
 }
 // fills `host_table` (HOST memory, ecamp_wgrad_group_table_bytes bytes) with the item table of this group for
@@ -1278,20 +1201,13 @@ extern "C" int ecamp_wgrad_group(int32_t n, const void* const* dy, const void* c
         R.p[p].C = gw[p]; R.p[p].ldc = k_in[p]; R.p[p].M = (int)n_out[p]; R.p[p].N = (int)k_in[p]; R.p[p].alpha = alpha; R.p[p].alpha_dev = alpha_dev;
         R.p[p].accumulate = accumulate[p];
     }
-    GemmArgs g;   // the item-table form takes operands and shapes from the group; these only keep the kernel's unused set-up code in range
-    memset(&g, 0, sizeof(g));
-    g.A = dy[0]; g.B = x[0]; g.C = ws; g.M = (int)n_out[0]; g.N = (int)k_in[0]; g.K = (int)rows; g.lda = n_out[0]; g.ldb = k_in[0]; g.ldc = k_in[0];
-    g.out_f32 = 1; g.alpha = 1.0f; g.alpha_out = alpha; g.nbm = 1; g.nbn = 1; g.nsplit = 1; g.k_per_split = (int)rows; g.wide = 1; g.partial = ws;
-    const size_t shm = 10 * Q8_HALF;
+    // the item-table form takes operands and shapes from the group; these only keep the kernel's unused set-up code in range
+    GemmArgs g = gemm_args(dy[0], x[0], ws, n_out[0], k_in[0], rows, n_out[0], k_in[0], k_in[0]);
+    g.out_f32 = 1; g.alpha_out = alpha; g.nbm = 1; g.nbn = 1; g.wide = 1; g.partial = ws;
     typedef void (*q8i_fn)(GemmArgs, Q8Group);
-    const bool lean = (q8_sch() & 8) != 0;
+    const bool lean = (ecamp_opt(OPT_Q8_SCH) & 8) != 0;
     const q8i_fn fn = any_bias ? (lean ? (q8i_fn)gemm_bf16_q8_items_kernel<true, 1> : (q8i_fn)gemm_bf16_q8_items_kernel<true, 0>)
                                : (lean ? (q8i_fn)gemm_bf16_q8_items_kernel<false, 1> : (q8i_fn)gemm_bf16_q8_items_kernel<false, 0>);
-    static bool attr[4] = {false, false, false, false};
-    if (!attr[any_bias + 2 * lean]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        attr[any_bias + 2 * lean] = true;
-    }
     double work = 0.0;
     for (int p = 0; p < n; ++p) work += 2.0 * (double)n_out[p] * (double)k_in[p] * (double)rows;
     const bool prof = ecamp_prof_active();
@@ -1300,7 +1216,7 @@ extern "C" int ecamp_wgrad_group(int32_t n, const void* const* dy, const void* c
         snprintf(tag, sizeof tag, "grp:w:n%d:%ld:%ld:%ld:wg%d", n, (long)rows, (long)n_out[0], (long)k_in[0], pl->nwg);
         ecamp_prof_begin(ECAMP_PROF_GEMM_BF16, work, stream, tag);
     }
-    hipLaunchKernelGGL(fn, dim3(pl->nwg), dim3(512), shm, stream, g, G);
+    launch_persistent(fn, (long)pl->nwg, (long)pl->nwg, 512, stream, g, G);   // the plan's workgroup count: each has its range of the table
     g_q8_launches += n;
     ++g_wg_launches;
     hipLaunchKernelGGL(wgrad_group_reduce_kernel, dim3(pl->ntiles * 16), dim3(256), 0, stream, R);

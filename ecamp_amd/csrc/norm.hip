@@ -413,7 +413,7 @@ static int ln_bwd_launch(const void* dy, const void* z, const float* mean, const
     // maximum of 2048 columns, inside the default dynamic-LDS limit (the gamma slice used to be requested for every form,
     // 72 KB at 2048 columns without the opt-in)
     size_t shm = (size_t)8 * cols * sizeof(float);
-    static const int variant = getenv("ECAMP_LN_BWD") ? atoi(getenv("ECAMP_LN_BWD")) : 0;   // development: 1 = 4-wide forms only
+    const int variant = ecamp_opt(OPT_LN_BWD);   // development: 1 = 4-wide forms only
     auto al16 = [](const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
 #define L(IT_, V_, W_, G_)                                                                                               \
     do {                                                                                                                 \

@@ -463,7 +463,7 @@ extern "C" int ecamp_ce_fwd_bwd(void* logits, const int64_t* labels, const float
     ECAMP_CHECK_ARG(logits && labels && weights && loss_sum && V % 4 == 0 && ld % 4 == 0, "ce_fwd_bwd: bad args");
     dim3 grid((unsigned)M), block(256);
     if (dtype == ECAMP_BF16 && V % 8 == 0 && ld % 8 == 0 && V <= 32768 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0) {
-        static const int ce_variant = getenv("ECAMP_CE_KERNEL") ? atoi(getenv("ECAMP_CE_KERNEL")) : 1;   // development A/B: 0 = the two-exp kernel of round 2
+        const int ce_variant = ecamp_opt(OPT_CE_KERNEL);   // development A/B: 0 = the two-exp kernel of round 2
         if (ce_variant == 0) {
             if (V <= 16384) hipLaunchKernelGGL(ce_fwd_bwd_reg_kernel<8>, grid, block, 0, stream, (bf16_t*)logits, (const long*)labels, weights, loss_sum, V, (long)ld, inv_count);
             else hipLaunchKernelGGL(ce_fwd_bwd_reg_kernel<16>, grid, block, 0, stream, (bf16_t*)logits, (const long*)labels, weights, loss_sum, V, (long)ld, inv_count);

@@ -1566,8 +1566,8 @@ extern "C" int ecamp_sr_bwd(const float* pred_img, const void* big, const float*
     if (mode == 1) {
         static int nbp = 0;
         if (nbp == 0) {
-            const char* nbe = getenv("ECAMP_SR_BLOCKS");   // development: grid override
-            nbp = nbe && atoi(nbe) > 0 ? atoi(nbe) : 512;  // two resident workgroups per CU
+            nbp = ecamp_opt(OPT_SR_BLOCKS);                 // development: grid override; the default is two resident workgroups per CU
+            if (nbp <= 0) nbp = ecamp_opt_default(OPT_SR_BLOCKS);
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sr_pair_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SRP_LDS_BYTES);
         }
         const int nb2 = (int)(tiles < nbp ? tiles : nbp);

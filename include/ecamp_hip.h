@@ -98,20 +98,27 @@ int64_t ecamp_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K, int32_t spli
 int64_t ecamp_attn_bwd_workspace_bytes(int32_t B, int32_t H, int32_t Tq);
 int64_t ecamp_sr_bwd_workspace_bytes(void);
 /* Process-wide switches with no reference counterpart (the "p8_" prefix is historical: the persistent one-workgroup-per-CU GEMM).
+ * One table holds them all (csrc/core.hip g_opts; INTEGRATION.md "Library options" lists every row, the environment-only ones
+ * included).  Where a switch has an environment variable it is read once, at first use, and a value set here wins over it.
+ * Returns 0, or -1 (ecamp_last_error) for a null or unknown name.  The option names:
  * "p8_wgrad" (default 1): 0 keeps weight-gradient GEMMs off the persistent kernel.  "p8_wgrad_reserve_cus" (default 0): launch the
  * backward-pass forms of that kernel with this many fewer workgroups than CUs -- set by the data-parallel wrapper, whose all-reduce
  * kernels share the CUs during backward.  "q8_bwd_grid" (default 0 = one workgroup per CU; env ECAMP_Q8_BWD_GRID): n > 0 launches the
  * data-gradient form on min(output tiles, n) workgroups -- with n past the tile count every workgroup computes ONE tile and the
  * hardware dispatcher deals the tiles to whichever CUs the communication kernels leave free (+0.15 ms per step alone on a GPU);
- * set by the data-parallel wrapper as well. */
+ * set by the data-parallel wrapper as well; n <= 0 back to the environment. */
 int ecamp_set_option(const char* name, int32_t value);
-/* "q8_mode" (ecamp_set_option): -1 automatic (default), 0 never, 2 whenever its alignment / size conditions hold -- the
- * persistent 256x256x64 kernel (csrc/gemm_q8.h) that serves the forward, data-gradient and weight-gradient forms. */
-/* "q16_mode" (ecamp_set_option; env ECAMP_Q16): the four-wave v_mfma_f32_16x16x32_bf16 kernel (csrc/gemm_q16.h; forward and data-gradient forms
+/* "q8_mode" (env ECAMP_GEMM_Q8): -1 automatic (default), 0 never, 2 whenever its alignment / size conditions hold -- the
+ * persistent 256x256x64 kernel (csrc/gemm_q8.h) that serves the forward, data-gradient and weight-gradient forms.  Any other value
+ * means -1; once this option has been set the environment variable is no longer consulted.
+ * "q8_sch" (env ECAMP_Q8_SCH, default 7): development A/B mask -- bits 0 / 1 / 2 put the forward / data-gradient / weight-gradient
+ * forms of that kernel on the lean operand stream, bit 3 the grouped weight gradients; negative back to the environment.
+ * "q16_mode" (env ECAMP_Q16): the four-wave v_mfma_f32_16x16x32_bf16 kernel (csrc/gemm_q16.h; forward and data-gradient forms
  * with a plain / bias / residual epilogue, 256 x 256 or 256 x 192 tiles).  0 never; 1 (default) where the 192-column tile removes idle
- * last-round time -- the model's 768-wide outputs; 2 every eligible call; 3 as 2 whatever the size (tests); -1 back to the environment */
-/* "attn_head" (ecamp_set_option): 1 (default; env ECAMP_ATTN_HEAD) one workgroup per (batch, head) with everything resident in LDS
- * for sequences that fit (<= 256 tokens here), 0 the 64-row streaming kernels for every length, -1 back to the environment's choice */
+ * last-round time -- the model's 768-wide outputs; 2 every eligible call; 3 as 2 whatever the size (tests); any other value back to
+ * the environment.
+ * "attn_head" (env ECAMP_ATTN_HEAD): 1 (default) one workgroup per (batch, head) with everything resident in LDS for sequences
+ * that fit (<= 256 tokens here), 0 the 64-row streaming kernels for every length, negative back to the environment's choice */
 
 /* ---- fp8 forward (BASELINE.json configs[4]: "fp8 MFMA forward (bf16 grads) for QKV/MLP GEMMs"; no reference counterpart -- the
  * reference runs these nn.Linear layers under torch.cuda.amp, main_pretrain.py:138).  Per-tensor scaling, OCP e4m3:
