@@ -155,7 +155,11 @@ __global__ void loss_scale_update_kernel(const float* __restrict__ sumsq, float*
         state[2] += 1.f;
     } else {
         const float ok = state[1] + 1.f;
-        if (ok == interval) { state[0] = scale * growth; state[1] = 0.f; } else state[1] = ok;
+        if (ok == interval) {
+            const float grown = scale * growth;   // like _amp_update_scale_: a growth step whose result is not finite keeps the scale
+            if (fabsf(grown) <= 3.402823466e+38f) state[0] = grown;
+            state[1] = 0.f;
+        } else state[1] = ok;
         const float step = opt_step[0] + 1.f;
         opt_step[0] = step;
         ctl[2] = (float)(1.0 - pow((double)b1, (double)step));
