@@ -547,85 +547,91 @@ static int attn_check(const AttnArgs& a, int hd, int dtype, bool bwd) {
     return 0;
 }
 
-// kernels that need more than the default 64 KiB of dynamic LDS opt in once per instantiation
-template <typename K>
-static void allow_lds(K kern, size_t bytes) {
-    if (bytes > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-#define LAUNCH_LDS(KERN, GRID, BLOCK, SHM, ST, ARGS)             \
-    do {                                                         \
-        static bool once_ = false;                               \
-        if (!once_) { allow_lds(KERN, SHM); once_ = true; }      \
-        hipLaunchKernelGGL(KERN, GRID, BLOCK, SHM, ST, ARGS);    \
-    } while (0)
-
-template <typename T, int HD>
-static void fwd_dispatch(const AttnArgs& a, hipStream_t st) {
-    if (a.Tk > 256) {   // f32 only (the bf16 path never comes here): one wave per query row
-        hipLaunchKernelGGL((attn_long_fwd_kernel<HD>), dim3((unsigned)(((long)a.B * a.H * a.Tq + 3) / 4)), dim3(256), 0, st, a);
-        return;
+template <int HD>
+static AttnLaunch select_f32(int B, int H, int Tq, int Tk, bool backward) {
+    AttnLaunch l = {};
+    l.family = ATTN_F32;
+    l.n = backward ? 2 : 1;
+    l.block = 256;
+    const int kch = attn_kch(Tk);
+    if (kch == 0) {   // more than 256 keys: one wave per query (dK / dV: key) row, static LDS
+        const dim3 qrows((unsigned)(((long)B * H * Tq + 3) / 4)), krows((unsigned)(((long)B * H * Tk + 3) / 4));
+        l.k[0] = {backward ? attn_long_bwd_dq_kernel<HD> : attn_long_fwd_kernel<HD>, qrows, 0, 0};
+        if (backward) l.k[1] = {attn_long_bwd_dkv_kernel<HD>, krows, 0, 0};
+        return l;
     }
-    dim3 grid(ceil_div(a.Tq, 64), a.B * a.H), block(256);
-    size_t shm = (size_t)(64 * (HD + 16) + 4 * 16 * PP) * sizeof(float);
-    if (a.Tk <= 64) LAUNCH_LDS((attn_fwd_kernel<T, HD, 1>), grid, block, shm, st, a);
-    else if (a.Tk <= 128) LAUNCH_LDS((attn_fwd_kernel<T, HD, 2>), grid, block, shm, st, a);
-    else LAUNCH_LDS((attn_fwd_kernel<T, HD, 4>), grid, block, shm, st, a);
-}
-template <typename T, int HD>
-static void bwd_dispatch(const AttnArgs& a, hipStream_t st) {
-    if (a.Tk > 256) {
-        hipLaunchKernelGGL((attn_long_bwd_dq_kernel<HD>), dim3((unsigned)(((long)a.B * a.H * a.Tq + 3) / 4)), dim3(256), 0, st, a);
-        hipLaunchKernelGGL((attn_long_bwd_dkv_kernel<HD>), dim3((unsigned)(((long)a.B * a.H * a.Tk + 3) / 4)), dim3(256), 0, st, a);
-        return;
+    const dim3 qgrid(ceil_div(Tq, 64), B * H), kgrid(ceil_div(Tk, 64), B * H);
+    const size_t fwd = (size_t)(64 * (HD + 16) + 4 * 16 * PP) * sizeof(float), dq = (size_t)(2 * 64 * (HD + 2) + 4 * 16 * PP) * sizeof(float),
+                 dkv = (size_t)(2 * 64 * (HD + 2) + 8 * 16 * PP) * sizeof(float);
+#define KCH_KERNEL(K) (kch == 1 ? K<float, HD, 1> : kch == 2 ? K<float, HD, 2> : K<float, HD, 4>)
+    if (backward) {
+        l.k[0] = {KCH_KERNEL(attn_bwd_dq_kernel), qgrid, dq, dq};
+        l.k[1] = {attn_bwd_dkv_kernel<float, HD>, kgrid, dkv, dkv};
+    } else {
+        l.k[0] = {KCH_KERNEL(attn_fwd_kernel), qgrid, fwd, fwd};
     }
-    dim3 grid(ceil_div(a.Tq, 64), a.B * a.H), block(256);
-    size_t shm = (size_t)(2 * 64 * (HD + 2) + 4 * 16 * PP) * sizeof(float);
-    if (a.Tk <= 64) LAUNCH_LDS((attn_bwd_dq_kernel<T, HD, 1>), grid, block, shm, st, a);
-    else if (a.Tk <= 128) LAUNCH_LDS((attn_bwd_dq_kernel<T, HD, 2>), grid, block, shm, st, a);
-    else LAUNCH_LDS((attn_bwd_dq_kernel<T, HD, 4>), grid, block, shm, st, a);
-    dim3 grid2(ceil_div(a.Tk, 64), a.B * a.H);
-    size_t shm2 = (size_t)(2 * 64 * (HD + 2) + 8 * 16 * PP) * sizeof(float);
-    LAUNCH_LDS((attn_bwd_dkv_kernel<T, HD>), grid2, block, shm2, st, a);
+#undef KCH_KERNEL
+    return l;
+}
+// Which kernel(s) serve a shape under the current options (ECAMP_ATTN_HEAD, ECAMP_ATTN_WAVES): no side effect, nothing is launched.
+// Only float instantiates the kernels of this file: every 16-bit shape has a kernel in attention_bf16.hip (any key length).
+static AttnLaunch attn_select(int B, int H, int Tq, int Tk, int hd, int dtype, bool mask_or_dropout, bool bits, bool backward) {
+    if (dtype == ECAMP_F32) return ATTN_HD_SWITCH(hd, select_f32, B, H, Tq, Tk, backward);
+    return attn16_select(B, H, Tq, Tk, hd, mask_or_dropout, bits, backward);
 }
 
-extern "C" int64_t ecamp_attn_mask_bytes(int32_t B, int32_t H, int32_t Tq, int32_t Tk, int32_t hd, int32_t dtype);
+static void stride3(long& sb, long& st, long& sh, const int64_t* s) {
+    if (s) { sb = s[0]; st = s[1]; sh = s[2]; }
+}
+// the kernels' argument block from the C arguments (forward: dout, delta, dq, dk, dv and their strides are null)
+static AttnArgs attn_args(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse, float* delta, void* dq,
+                          void* dk, void* dv, const int32_t* key_mask, int32_t B, int32_t H, int32_t Tq, int32_t Tk, const int64_t* q_strides,
+                          const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides, const int64_t* do_strides,
+                          const int64_t* dq_strides, const int64_t* dk_strides, const int64_t* dv_strides, float scale, float drop_p, uint64_t seed,
+                          uint64_t offset, const void* drop_bits) {
+    AttnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.q = q; a.k = k; a.v = v; a.o = const_cast<void*>(o); a.dout = dout; a.lse = const_cast<float*>(lse); a.delta = delta;
+    a.dq = dq; a.dk = dk; a.dv = dv; a.key_mask = key_mask;
+    stride3(a.q_sb, a.q_st, a.q_sh, q_strides);
+    stride3(a.k_sb, a.k_st, a.k_sh, k_strides);
+    stride3(a.v_sb, a.v_st, a.v_sh, v_strides);
+    stride3(a.o_sb, a.o_st, a.o_sh, o_strides);
+    stride3(a.do_sb, a.do_st, a.do_sh, do_strides);
+    stride3(a.dq_sb, a.dq_st, a.dq_sh, dq_strides);
+    stride3(a.dk_sb, a.dk_st, a.dk_sh, dk_strides);
+    stride3(a.dv_sb, a.dv_st, a.dv_sh, dv_strides);
+    a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.scale = scale; a.drop_p = drop_p; a.seed = seed; a.offset = offset;
+    a.drop_bits = reinterpret_cast<unsigned char*>(const_cast<void*>(drop_bits));
+    return a;
+}
+
+// Bytes of the optional `drop_mask` buffer (32 per query row and head): 0 when the FORWARD pass of the shape is not served by the
+// head-resident bf16 kernels under the current options -- the caller then passes NULL and every pass regenerates the mask from the Philox
+// counters.  (The backward pass of a shape with many more queries than keys may still not fit LDS with the bits: it then runs the streaming
+// kernels, which regenerate the mask and never read the buffer.)
+extern "C" int64_t ecamp_attn_mask_bytes(int32_t B, int32_t H, int32_t Tq, int32_t Tk, int32_t hd, int32_t dtype) {
+    if (dtype != ECAMP_BF16 || B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0 || Tk > 256) return 0;
+    if (hd != 32 && hd != 64 && hd != 128) return 0;
+    return ecamp_opt(OPT_ATTN_HEAD) != 0 && head_lds_bytes(Tq, Tk, hd, false, false) <= LDS_MAX ? (int64_t)B * H * Tq * 32 : 0;
+}
 extern "C" int ecamp_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* key_mask,
                               int32_t B, int32_t H, int32_t Tq, int32_t Tk, int32_t hd, const int64_t* q_strides,
                               const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides, float scale,
                               float drop_p, uint64_t seed, uint64_t offset, int32_t dtype, void* drop_mask, hipStream_t stream) {
     ECAMP_CHECK_ARG(q && k && v && o && lse && q_strides && k_strides && v_strides && o_strides, "attn_fwd: null pointer");
-    AttnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.q = q; a.k = k; a.v = v; a.o = o; a.lse = lse; a.key_mask = key_mask;
-    a.q_sb = q_strides[0]; a.q_st = q_strides[1]; a.q_sh = q_strides[2];
-    a.k_sb = k_strides[0]; a.k_st = k_strides[1]; a.k_sh = k_strides[2];
-    a.v_sb = v_strides[0]; a.v_st = v_strides[1]; a.v_sh = v_strides[2];
-    a.o_sb = o_strides[0]; a.o_st = o_strides[1]; a.o_sh = o_strides[2];
-    a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.scale = scale; a.drop_p = drop_p; a.seed = seed; a.offset = offset;
-    a.drop_bits = (dtype == ECAMP_BF16 && drop_p > 0.f && ecamp_attn_mask_bytes(B, H, Tq, Tk, hd, dtype) > 0) ? reinterpret_cast<unsigned char*>(drop_mask) : nullptr;
+    const bool bits = dtype == ECAMP_BF16 && drop_p > 0.f && ecamp_attn_mask_bytes(B, H, Tq, Tk, hd, dtype) > 0;
+    const AttnArgs a = attn_args(q, k, v, o, nullptr, lse, nullptr, nullptr, nullptr, nullptr, key_mask, B, H, Tq, Tk, q_strides, k_strides, v_strides,
+                                 o_strides, nullptr, nullptr, nullptr, nullptr, scale, drop_p, seed, offset, bits ? drop_mask : nullptr);
     if (int rc = attn_check(a, hd, dtype, false)) return rc;
     const bool prof = ecamp_prof_active();
     if (prof) ecamp_prof_begin(ECAMP_PROF_ATTN, 4.0 * B * H * (double)Tq * Tk * hd, stream);
-#define D(T_)                                                  \
-    do {                                                       \
-        if (hd == 32) fwd_dispatch<T_, 32>(a, stream);         \
-        else if (hd == 64) fwd_dispatch<T_, 64>(a, stream);    \
-        else fwd_dispatch<T_, 128>(a, stream);                 \
-    } while (0)
-    if (dtype == ECAMP_F32) D(float); else attn_bf16_fwd(a, hd, stream);
-#undef D
+    attn_launch(attn_select(B, H, Tq, Tk, hd, dtype, key_mask != nullptr || drop_p > 0.f, a.drop_bits != nullptr, false), a, stream);
     if (prof) ecamp_prof_end(stream);
     ECAMP_LAUNCH_CHECK();
     return 0;
 }
 
-// Bytes of the optional `drop_mask` buffer (32 per query row and head): 0 when the shape is not served by the head-resident bf16
-// kernels under the current options -- the caller then passes NULL and every pass regenerates the mask from the Philox counters.
-extern "C" int64_t ecamp_attn_mask_bytes(int32_t B, int32_t H, int32_t Tq, int32_t Tk, int32_t hd, int32_t dtype) {
-    if (dtype != ECAMP_BF16 || B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0 || Tk > 256) return 0;
-    if (hd != 32 && hd != 64 && hd != 128) return 0;
-    return attn_bf16_head_path(Tq, Tk, hd, false) ? (int64_t)B * H * Tq * 32 : 0;
-}
 // Workspace of ecamp_attn_bwd(..., delta_ws, ...): delta[b, h, i] = dO_i . O_i, one f32 per query row.
 extern "C" int64_t ecamp_attn_bwd_workspace_bytes(int32_t B, int32_t H, int32_t Tq) { return (int64_t)B * H * Tq * 4; }
 
@@ -635,32 +641,15 @@ extern "C" int ecamp_attn_bwd(const void* q, const void* k, const void* v, const
                               const int64_t* v_strides, const int64_t* o_strides, const int64_t* do_strides,
                               const int64_t* dq_strides, const int64_t* dk_strides, const int64_t* dv_strides, float scale,
                               float drop_p, uint64_t seed, uint64_t offset, int32_t dtype, const void* drop_mask, hipStream_t stream) {
-    ECAMP_CHECK_ARG(q && k && v && o && dout && lse && delta_ws && dq && dk && dv, "attn_bwd: null pointer");
-    AttnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.q = q; a.k = k; a.v = v; a.o = const_cast<void*>(o); a.dout = dout; a.lse = const_cast<float*>(lse); a.delta = delta_ws;
-    a.dq = dq; a.dk = dk; a.dv = dv; a.key_mask = key_mask;
-    a.q_sb = q_strides[0]; a.q_st = q_strides[1]; a.q_sh = q_strides[2];
-    a.k_sb = k_strides[0]; a.k_st = k_strides[1]; a.k_sh = k_strides[2];
-    a.v_sb = v_strides[0]; a.v_st = v_strides[1]; a.v_sh = v_strides[2];
-    a.o_sb = o_strides[0]; a.o_st = o_strides[1]; a.o_sh = o_strides[2];
-    a.do_sb = do_strides[0]; a.do_st = do_strides[1]; a.do_sh = do_strides[2];
-    a.dq_sb = dq_strides[0]; a.dq_st = dq_strides[1]; a.dq_sh = dq_strides[2];
-    a.dk_sb = dk_strides[0]; a.dk_st = dk_strides[1]; a.dk_sh = dk_strides[2];
-    a.dv_sb = dv_strides[0]; a.dv_st = dv_strides[1]; a.dv_sh = dv_strides[2];
-    a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.scale = scale; a.drop_p = drop_p; a.seed = seed; a.offset = offset;
-    a.drop_bits = (dtype == ECAMP_BF16 && drop_p > 0.f) ? reinterpret_cast<unsigned char*>(const_cast<void*>(drop_mask)) : nullptr;
+    ECAMP_CHECK_ARG(q && k && v && o && dout && lse && delta_ws && dq && dk && dv && q_strides && k_strides && v_strides && o_strides && do_strides &&
+                        dq_strides && dk_strides && dv_strides, "attn_bwd: null pointer");
+    const bool bits = dtype == ECAMP_BF16 && drop_p > 0.f;
+    const AttnArgs a = attn_args(q, k, v, o, dout, lse, delta_ws, dq, dk, dv, key_mask, B, H, Tq, Tk, q_strides, k_strides, v_strides, o_strides,
+                                 do_strides, dq_strides, dk_strides, dv_strides, scale, drop_p, seed, offset, bits ? drop_mask : nullptr);
     if (int rc = attn_check(a, hd, dtype, true)) return rc;
     const bool prof = ecamp_prof_active();
     if (prof) ecamp_prof_begin(ECAMP_PROF_ATTN, 8.0 * B * H * (double)Tq * Tk * hd, stream);
-#define D(T_)                                                  \
-    do {                                                       \
-        if (hd == 32) bwd_dispatch<T_, 32>(a, stream);         \
-        else if (hd == 64) bwd_dispatch<T_, 64>(a, stream);    \
-        else bwd_dispatch<T_, 128>(a, stream);                 \
-    } while (0)
-    if (dtype == ECAMP_F32) D(float); else attn_bf16_bwd(a, hd, stream);
-#undef D
+    attn_launch(attn_select(B, H, Tq, Tk, hd, dtype, key_mask != nullptr || drop_p > 0.f, a.drop_bits != nullptr, true), a, stream);
     if (prof) ecamp_prof_end(stream);
     ECAMP_LAUNCH_CHECK();
     return 0;

@@ -148,99 +148,6 @@ __device__ __forceinline__ void attn_drop4_col(const AttnArgs& a, uint64_t row0,
 }
 
 // =============================================================================================
-template <int HD, int KCH>
-__global__ __launch_bounds__(256) void attn16_fwd_kernel(AttnArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* KV = smem;                         // 64-row K (then V) chunk
-    unsigned char* PT = smem + TileCfg<HD>::BYTES;    // 4 per-wave P tiles
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, g = lane >> 4;
-    const int b = blockIdx.y / a.H, h = blockIdx.y % a.H;
-    const int q0 = blockIdx.x * 64 + wave * 16;
-    const long bh = (long)b * a.H + h;
-    const bf16_t* qb = reinterpret_cast<const bf16_t*>(a.q) + b * a.q_sb + h * a.q_sh;
-    const bf16_t* kb = reinterpret_cast<const bf16_t*>(a.k) + b * a.k_sb + h * a.k_sh;
-    const bf16_t* vb = reinterpret_cast<const bf16_t*>(a.v) + b * a.v_sb + h * a.v_sh;
-    bf16_t* ob = reinterpret_cast<bf16_t*>(a.o) + b * a.o_sb + h * a.o_sh;
-
-    bf16x8 qf[HD / 32];
-    load_row_frags<HD>(qf, qb, a.q_st, q0, a.Tq, lane);
-
-    f32x4 s[KCH * 4];  // s[c*4+jt][r] = S[i = q0+li][j = c*64 + jt*16 + 4g + r]
-#pragma unroll
-    for (int c = 0; c < KCH; ++c) {
-        __syncthreads();
-        stage_tile<HD>(KV, kb, a.k_st, c * 64, a.Tk, tid);
-        __syncthreads();
-#pragma unroll
-        for (int jt = 0; jt < 4; ++jt) {
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < HD / 32; ++ks) acc = MFMA(frag_rows<HD>(KV, jt * 16 + li, ks * 4 + g), qf[ks], acc);
-            s[c * 4 + jt] = acc;
-        }
-    }
-    float mx = NEG_BIG;
-#pragma unroll
-    for (int t = 0; t < KCH * 4; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            int j = t * 16 + 4 * g + r;
-            bool ok = j < a.Tk && (a.key_mask == nullptr || a.key_mask[(long)b * a.Tk + j] != 0);
-            s[t][r] = ok ? s[t][r] * a.scale : NEG_BIG;
-            mx = fmaxf(mx, s[t][r]);
-        }
-    mx = red4_max(mx);
-    float sum = 0.f;
-#pragma unroll
-    for (int t = 0; t < KCH * 4; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float p = s[t][r] > 0.5f * NEG_BIG ? __expf(s[t][r] - mx) : 0.f;
-            s[t][r] = p;
-            sum += p;
-        }
-    sum = red4_sum(sum);
-    const int qi = q0 + li;
-    if (g == 0 && qi < a.Tq) a.lse[bh * a.Tq + qi] = mx + __logf(sum);
-    const float inv = 1.0f / sum;
-    const float inv_keep = a.drop_p > 0.f ? 1.0f / (1.0f - a.drop_p) : 1.0f;
-
-    f32x4 o[HD / 16];  // o[dt][r] = O[i = q0+li][d = dt*16 + 4g + r]
-#pragma unroll
-    for (int dt = 0; dt < HD / 16; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    unsigned char* pt = PT + wave * 2048;
-#pragma unroll
-    for (int c = 0; c < KCH; ++c) {
-        __syncthreads();
-        stage_tile<HD>(KV, vb, a.v_st, c * 64, a.Tk, tid);
-#pragma unroll
-        for (int jt = 0; jt < 4; ++jt) {
-            float p[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) p[r] = s[c * 4 + jt][r] * inv;
-            if (a.drop_p > 0.f) {
-                float dm[4];
-                attn_drop4(a, (uint64_t)bh * a.Tq + qi, c * 64 + jt * 16 + 4 * g, inv_keep, dm);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) p[r] *= dm[r];
-            }
-            ptile_write4(pt, li, jt * 16 + 4 * g, p);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            bf16x8 pf = ptile_frag(pt, li, kk * 4 + g);
-#pragma unroll
-            for (int dt = 0; dt < HD / 16; ++dt) o[dt] = MFMA(frag_tr<HD>(KV, dt * 16, kk * 32, lane), pf, o[dt]);
-        }
-    }
-    if (qi < a.Tq) {
-#pragma unroll
-        for (int dt = 0; dt < HD / 16; ++dt) store4(ob + (long)qi * a.o_st + dt * 16 + 4 * g, o[dt], 1.0f);
-    }
-}
-
-// =============================================================================================
 // Forward for ANY key length: keys streamed in chunks of 64 with the online-softmax recurrence (running max m, running
 // sum l, O rescaled by exp(m_old - m_new)).  Used when Tk > 256 (ViT-L/16 at 448^2: decoder sequence 785).
 template <int HD, bool PART>
@@ -1139,31 +1046,12 @@ __global__ __launch_bounds__(256, (FLAGS == 0 && HD == 32) ? 5 : (FLAGS == 0 && 
     ATTN_STAMP(5);
 }
 
-template <typename K>
-static void lds_optin(K kern, size_t bytes) {
-    if (bytes > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-#define LAUNCH_R(KERN, GRID, SHM, ST, ARGS)                  \
-    do {                                                     \
-        static bool once_ = false;                           \
-        if (!once_) { lds_optin(KERN, SHM); once_ = true; }  \
-        hipLaunchKernelGGL(KERN, GRID, dim3(256), SHM, ST, ARGS); \
-    } while (0)
-
 // =============================================================================================
-// (the opt-in is for the largest size any later call of the same instantiation may ask for, not for this call's)
-#define LAUNCH_H(KERN, GRID, BLOCK, SHM, ST, ARGS)           \
-    do {                                                     \
-        static bool once_ = false;                           \
-        if (!once_) { lds_optin(KERN, LDS_MAX); once_ = true; }  \
-        hipLaunchKernelGGL(KERN, GRID, dim3(BLOCK), SHM, ST, ARGS); \
-    } while (0)
-#define LDS_MAX (160 * 1024)
-// ECAMP_ATTN_HEAD=0 keeps the 64-row streaming kernels (A/B measurements)
+// host side: which kernel serves a shape (attn16_select: no side effect), and the one launcher of the attention family (attn_launch)
+// =============================================================================================
 static long g_head_launches = 0;   // development ABI: launches of the head-resident kernels so far (tests assert that they really ran)
 extern "C" int64_t ecamp_attn_head_launches(void) { return g_head_launches; }
 void attn_set_head_mode(int on) { ecamp_opt_set("attn_head", on); }   // ecamp_set_option("attn_head", v): negative = the environment decides
-static bool head_enabled() { return ecamp_opt(OPT_ATTN_HEAD) != 0; }
 // workgroup size: one wave per 16-row tile up to `cap` waves (ECAMP_ATTN_WAVES overrides the cap: tuning)
 static int head_waves(int tiles, int cap) {
     const int env = ecamp_opt(OPT_ATTN_WAVES);
@@ -1171,87 +1059,72 @@ static int head_waves(int tiles, int cap) {
     return tiles < cap ? tiles : cap;
 }
 template <int HD>
-static bool head_fwd(const AttnArgs& a, hipStream_t st) {
-    const int nkp = ((a.Tk + 15) / 16 + 1) / 2, prow = nkp * 32;
-    const size_t shm = (size_t)2 * prow * HeadCfg<HD>::RB + (size_t)prow * sizeof(float);
-    if (!head_enabled() || shm > LDS_MAX) return false;
-    const dim3 grid(a.B * a.H);
-    const int nw = head_waves((a.Tq + 15) / 16, 8);
-    if (a.key_mask != nullptr || a.drop_p > 0.f) LAUNCH_H((attn_head_fwd_kernel<HD, 1>), grid, nw * 64, shm, st, a);
-    else LAUNCH_H((attn_head_fwd_kernel<HD, 0>), grid, nw * 64, shm, st, a);
-    ++g_head_launches;
-    return true;
-}
-template <int HD>
-static bool head_bwd(const AttnArgs& a, hipStream_t st) {
-    const int nkt = (a.Tk + 15) / 16, nqt = (a.Tq + 15) / 16, nkp = (nkt + 1) / 2, nqp = (nqt + 1) / 2, prow = (nkp > nqp ? nkp : nqp) * 32;
-    const bool bits = a.drop_bits != nullptr && a.drop_p > 0.f;
-    const size_t shm = (size_t)2 * prow * HeadCfg<HD>::RB + (size_t)3 * prow * sizeof(float) + (bits ? (size_t)32 * prow : 0);
-    if (!head_enabled() || shm > LDS_MAX) return false;
-    const dim3 grid(a.B * a.H);
-    // four waves: two (hd = 128: the register file) to five workgroups share a CU and one's staging overlaps another's tile loops
-    // (T = 197, hd = 32: 230 us against 260 us with eight; T = 128, hd = 128: 147 against 161)
-    const int nw = head_waves(nkt > nqt ? nkt : nqt, 4);
-    if (a.key_mask != nullptr || a.drop_p > 0.f) LAUNCH_H((attn_head_bwd_kernel<HD, 1>), grid, nw * 64, shm, st, a);
-    else LAUNCH_H((attn_head_bwd_kernel<HD, 0>), grid, nw * 64, shm, st, a);
-    ++g_head_launches;
-    return true;
-}
-template <int HD>
-static void fwd16(const AttnArgs& a, hipStream_t st) {
-    if (head_fwd<HD>(a, st)) return;
+static AttnLaunch select16(int B, int H, int Tq, int Tk, bool flags, bool bits, bool backward) {
+    static_assert(HeadCfg<HD>::RB == 2 * HD, "head_lds_bytes (attention.h) states the row size of the head images");
+    AttnLaunch l = {};
+    l.n = 1;
+    l.block = 256;
+    const int nqt = (Tq + 15) / 16, nkt = (Tk + 15) / 16;
+    const size_t head = head_lds_bytes(Tq, Tk, HD, backward, bits);
+    // ECAMP_ATTN_HEAD=0 keeps the 64-row streaming kernels (A/B measurements)
+    if (ecamp_opt(OPT_ATTN_HEAD) != 0 && head <= LDS_MAX) {
+        l.family = ATTN_HEAD;
+        // backward, four waves: two (hd = 128: the register file) to five workgroups share a CU and one's staging overlaps another's tile loops
+        // (T = 197, hd = 32: 230 us against 260 us with eight; T = 128, hd = 128: 147 against 161)
+        l.block = 64 * (backward ? head_waves(nkt > nqt ? nkt : nqt, 4) : head_waves(nqt, 8));
+        const AttnKernel fn = backward ? (flags ? attn_head_bwd_kernel<HD, 1> : attn_head_bwd_kernel<HD, 0>)
+                                       : (flags ? attn_head_fwd_kernel<HD, 1> : attn_head_fwd_kernel<HD, 0>);
+        l.k[0] = {fn, dim3(B * H), head, LDS_MAX};
+        return l;
+    }
+    const dim3 qgrid(ceil_div(Tq, 64), B * H), kgrid(ceil_div(Tk, 64), B * H);
+    const size_t stream = (size_t)2 * TileCfg<HD>::BYTES + 4 * 2048 + 64 * sizeof(int);   // K, V chunk + 4 per-wave tiles + key flags
+    const int kch = attn_kch(Tk);
+    if (backward) {
+        // The backward kernels run as 64-row workgroups streaming 64-key (dQ) / 64-query (dK, dV) chunks.  "Resident" variants that
+        // stage all of K/V (or Q/dO) once per (batch, head), like the forward below, were built and measured slower on MI355X: a quarter
+        // of the workgroups and 2-3x the LDS footprint cost more occupancy than the saved barriers return (rejected).
+        // They regenerate the dropout mask from the Philox counters: saved bits (drop_bits) are not read here.
+        l.family = ATTN_STREAM;
+        l.n = 2;
+        const AttnKernel dq = kch == 1 ? attn16_bwd_dq_kernel<HD, 1> : kch == 2 ? attn16_bwd_dq_kernel<HD, 2> : kch == 4 ? attn16_bwd_dq_kernel<HD, 4>
+                                                                                                                       : attn16_bwd_dq_kernel<HD, 0>;
+        l.k[0] = {dq, qgrid, stream, 0};
+        l.k[1] = {attn16_bwd_dkv_kernel<HD>, kgrid, (size_t)2 * TileCfg<HD>::BYTES + 8 * 2048 + 128 * sizeof(float), 0};
+        return l;
+    }
     // Tk > 128: the all-scores-in-registers kernels need 64 score registers per lane and spill (272 B/lane of scratch at 4 chunks);
     // the online-softmax kernel keeps one chunk of scores live and is faster from 129 keys up (decoder T=197, S=256, ViT-L T=785)
-    if (a.Tk > 128) {
-        dim3 grid(ceil_div(a.Tq, 64), a.B * a.H);
-        hipLaunchKernelGGL((attn16_fwd_long_kernel<HD>), grid, dim3(256), (size_t)2 * TileCfg<HD>::BYTES + 4 * 2048 + 64 * sizeof(int), st, a);
-        return;
+    if (Tk > 128) {
+        l.family = ATTN_LONG;
+        l.k[0] = {attn16_fwd_long_kernel<HD>, qgrid, stream, 0};
+        return l;
     }
-    {
-        const int kch = a.Tk <= 64 ? 1 : a.Tk <= 128 ? 2 : 4;
-        const size_t shm = (size_t)2 * kch * TileCfg<HD>::BYTES + 4 * 2048;
-        if (shm <= LDS_MAX) {
-            dim3 grid(a.B * a.H);
-            if (kch == 1) LAUNCH_R((attn16r_fwd_kernel<HD, 1>), grid, shm, st, a);
-            else if (kch == 2) LAUNCH_R((attn16r_fwd_kernel<HD, 2>), grid, shm, st, a);
-            else LAUNCH_R((attn16r_fwd_kernel<HD, 4>), grid, shm, st, a);
-            return;
+    // Tk <= 128 is kch 1 or 2, at most 2 * 2 * 64 * 288 + 8192 = 81920 B (hd 128) < LDS_MAX: the resident forward always fits, so there is
+    // neither a four-chunk instantiation of it nor a 64-row kernel behind it.
+    l.family = ATTN_RESIDENT_FWD;
+    const size_t shm = (size_t)2 * kch * TileCfg<HD>::BYTES + 4 * 2048;
+    l.k[0] = {kch == 1 ? attn16r_fwd_kernel<HD, 1> : attn16r_fwd_kernel<HD, 2>, dim3(B * H), shm, shm};
+    return l;
+}
+AttnLaunch attn16_select(int B, int H, int Tq, int Tk, int hd, bool mask_or_dropout, bool bits, bool backward) {
+    return ATTN_HD_SWITCH(hd, select16, B, H, Tq, Tk, mask_or_dropout, bits, backward);
+}
+
+// kernels that need more than 48 KB of dynamic LDS are allowed it once per function, at their first launch
+void attn_launch(const AttnLaunch& l, const AttnArgs& a, hipStream_t st) {
+    static const void* seen[64];
+    static int n_seen = 0;
+    for (int i = 0; i < l.n; ++i) {
+        const AttnLaunch::Kernel& k = l.k[i];
+        const void* fn = reinterpret_cast<const void*>(k.fn);
+        bool known = k.optin <= 48 * 1024;
+        for (int s = 0; s < n_seen && !known; ++s) known = seen[s] == fn;
+        if (!known) {
+            (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.optin);
+            if (n_seen < 64) seen[n_seen++] = fn;
         }
+        hipLaunchKernelGGL(k.fn, k.grid, dim3(l.block), k.lds, st, a);
     }
-    dim3 grid(ceil_div(a.Tq, 64), a.B * a.H), block(256);
-    size_t shm = TileCfg<HD>::BYTES + 4 * 2048;
-    if (a.Tk <= 64) hipLaunchKernelGGL((attn16_fwd_kernel<HD, 1>), grid, block, shm, st, a);
-    else if (a.Tk <= 128) hipLaunchKernelGGL((attn16_fwd_kernel<HD, 2>), grid, block, shm, st, a);
-    else hipLaunchKernelGGL((attn16_fwd_kernel<HD, 4>), grid, block, shm, st, a);
-}
-template <int HD>
-static void bwd16(const AttnArgs& a, hipStream_t st) {
-    // The backward kernels run as 64-row workgroups streaming 64-key (dQ) / 64-query (dK, dV) chunks.  "Resident" variants that
-    // stage all of K/V (or Q/dO) once per (batch, head), like the forward above, were built and measured slower on MI355X: a quarter
-    // of the workgroups and 2-3x the LDS footprint cost more occupancy than the saved barriers return (rejected).
-    if (head_bwd<HD>(a, st)) return;
-    dim3 block(256);
-    dim3 grid(ceil_div(a.Tq, 64), a.B * a.H);
-    size_t shm = 2 * TileCfg<HD>::BYTES + 4 * 2048 + 64 * sizeof(int);
-    if (a.Tk <= 64) hipLaunchKernelGGL((attn16_bwd_dq_kernel<HD, 1>), grid, block, shm, st, a);
-    else if (a.Tk <= 128) hipLaunchKernelGGL((attn16_bwd_dq_kernel<HD, 2>), grid, block, shm, st, a);
-    else if (a.Tk <= 256) hipLaunchKernelGGL((attn16_bwd_dq_kernel<HD, 4>), grid, block, shm, st, a);
-    else hipLaunchKernelGGL((attn16_bwd_dq_kernel<HD, 0>), grid, block, shm, st, a);
-    dim3 grid2(ceil_div(a.Tk, 64), a.B * a.H);
-    size_t shm2 = 2 * TileCfg<HD>::BYTES + 8 * 2048 + 128 * sizeof(float);
-    hipLaunchKernelGGL((attn16_bwd_dkv_kernel<HD>), grid2, block, shm2, st, a);
-}
-bool attn_bf16_head_path(int Tq, int Tk, int hd, bool backward) {
-    const int nkt = (Tk + 15) / 16, nqt = (Tq + 15) / 16, nkp = (nkt + 1) / 2, nqp = (nqt + 1) / 2;
-    const size_t rb = hd == 32 ? HeadCfg<32>::RB : hd == 64 ? HeadCfg<64>::RB : HeadCfg<128>::RB;
-    size_t shm;
-    if (backward) { const size_t prow = (size_t)(nkp > nqp ? nkp : nqp) * 32; shm = 2 * prow * rb + 3 * prow * sizeof(float) + 32 * prow; }
-    else { const size_t prow = (size_t)nkp * 32; shm = 2 * prow * rb + prow * sizeof(float); }
-    return head_enabled() && shm <= LDS_MAX;
-}
-void attn_bf16_fwd(const AttnArgs& a, int hd, hipStream_t st) {
-    if (hd == 32) fwd16<32>(a, st); else if (hd == 64) fwd16<64>(a, st); else fwd16<128>(a, st);
-}
-void attn_bf16_bwd(const AttnArgs& a, int hd, hipStream_t st) {
-    if (hd == 32) bwd16<32>(a, st); else if (hd == 64) bwd16<64>(a, st); else bwd16<128>(a, st);
+    if (l.family == ATTN_HEAD) ++g_head_launches;
 }

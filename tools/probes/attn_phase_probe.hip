@@ -34,13 +34,14 @@ static void run(const char* name, int B, int H, int T, int hd, bool flags) {
     a.o_sb = a.do_sb = (long)T * D; a.o_st = a.do_st = D; a.o_sh = a.do_sh = hd;
     a.B = B; a.H = H; a.Tq = T; a.Tk = T; a.scale = 1.0f / sqrtf((float)hd); a.drop_p = flags ? 0.1f : 0.f; a.seed = 1; a.offset = 2;
     a.drop_bits = flags ? bits : nullptr;
-    attn_bf16_fwd(a, hd, 0);
-    for (int it = 0; it < 3; ++it) attn_bf16_bwd(a, hd, 0);
+    const AttnLaunch fwd = attn16_select(B, H, T, T, hd, flags, false, false), bwd = attn16_select(B, H, T, T, hd, flags, flags, true);
+    attn_launch(fwd, a, 0);
+    for (int it = 0; it < 3; ++it) attn_launch(bwd, a, 0);
     hipDeviceSynchronize();
     hipEvent_t e0, e1;
     hipEventCreate(&e0); hipEventCreate(&e1);
     hipEventRecord(e0, 0);
-    for (int it = 0; it < 10; ++it) attn_bf16_bwd(a, hd, 0);
+    for (int it = 0; it < 10; ++it) attn_launch(bwd, a, 0);
     hipEventRecord(e1, 0);
     hipDeviceSynchronize();
     float ms;
