@@ -480,3 +480,156 @@ extern "C" int ecamp_ce_fwd_bwd(void* logits, const int64_t* labels, const float
     ECAMP_LAUNCH_CHECK();
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Held-out evaluation of the MLM head: the same weighted cross-entropy WITHOUT its gradient, plus what a validation pass reports --
+// how many rows were scored and whether the label ranks first / within the first five.  Read-only on the logits, one workgroup per row:
+//   label outside [0, V) (ignore_index -100): the workgroup returns after reading the label -- the row's logits are never touched
+//   xl = logit[label]      loss_sum += w (logsumexp(row) - xl)      rank = #{ j : logit[j] > xl }  (strictly: a label tied with the
+//   maximum is correct)    counts[0] += 1    counts[1] += rank == 0    counts[2] += rank < 5       (64-bit integer atomics: exact)
+// Against ecamp_ce_fwd_bwd: no write of [M, V], and at the reference's masking rate only the ~15 % of rows that carry a label are read.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ void ce_eval_flush(float* loss_sum, unsigned long long* counts, float loss, int rank) {
+    atomicAdd(loss_sum, loss);
+    atomicAdd(counts, 1ull);
+    if (rank == 0) atomicAdd(counts + 1, 1ull);
+    if (rank < 5) atomicAdd(counts + 2, 1ull);
+}
+// 16-bit rows of up to 32768 logits, the row held in registers as in ce_fwd_bwd_row_kernel (NT threads, NG 16-B loads per thread, lanes
+// past the row hold -inf): maximum and the strictly-greater count from the registers, then ONE exp2 per logit for the sum.
+template <int NG, int NT>
+__global__ __launch_bounds__(NT) void ce_eval_row_kernel(const bf16_t* __restrict__ logits, const long* __restrict__ labels,
+                                                         const float* __restrict__ weights, float* __restrict__ loss_sum,
+                                                         unsigned long long* __restrict__ counts, int V, long ld) {
+    constexpr int NWV = NT / 64;
+    __shared__ float shm_[2 * NWV];
+    __shared__ int shc_[NWV];
+    const long row = blockIdx.x;
+    const long label = labels[row];
+    if (label < 0 || label >= (long)V) return;   // uniform over the workgroup, ahead of every barrier
+    const bf16_t* x = logits + row * ld;
+    const int nv8 = V >> 3, wave = threadIdx.x >> 6;
+    uint4 q[NG];
+#pragma unroll
+    for (int j = 0; j < NG; ++j) {
+        const int c = threadIdx.x + NT * j;
+        q[j] = c < nv8 ? *reinterpret_cast<const uint4*>(x + c * 8) : make_uint4(H16_NEG_INF_X2, H16_NEG_INF_X2, H16_NEG_INF_X2, H16_NEG_INF_X2);
+    }
+    const float xl = to_f<bf16_t>(x[label]);   // one address for the whole wave: a single broadcast load
+    float mx = -INFINITY;
+    int cnt = 0;
+#pragma unroll
+    for (int j = 0; j < NG; ++j) {
+        const uint32_t w[4] = {q[j].x, q[j].y, q[j].z, q[j].w};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float a = h16_lo(w[r]), b = h16_hi(w[r]);
+            mx = fmaxf(mx, fmaxf(a, b));
+            cnt += (a > xl ? 1 : 0) + (b > xl ? 1 : 0);
+        }
+    }
+    mx = wave_max(mx);
+    cnt = wave_sum_i(cnt);
+    if ((threadIdx.x & 63) == 0) {
+        shm_[wave] = mx;
+        shc_[wave] = cnt;
+    }
+    __syncthreads();
+    float gmx = shm_[0];
+#pragma unroll
+    for (int k = 1; k < NWV; ++k) gmx = fmaxf(gmx, shm_[k]);
+    constexpr float LOG2E = 1.4426950408889634f;
+    const float nb = -gmx * LOG2E;
+    float sm = 0.f;
+#pragma unroll
+    for (int j = 0; j < NG; ++j) {
+        const uint32_t w[4] = {q[j].x, q[j].y, q[j].z, q[j].w};
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            sm += __builtin_amdgcn_exp2f(fmaf(h16_lo(w[r]), LOG2E, nb)) + __builtin_amdgcn_exp2f(fmaf(h16_hi(w[r]), LOG2E, nb));
+    }
+    sm = wave_sum(sm);
+    if ((threadIdx.x & 63) == 0) shm_[NWV + wave] = sm;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float gsm = 0.f;
+        int rank = 0;
+#pragma unroll
+        for (int k = 0; k < NWV; ++k) {
+            gsm += shm_[NWV + k];
+            rank += shc_[k];
+        }
+        ce_eval_flush(loss_sum, counts, weights[row] * (gmx + __logf(gsm) - xl), rank);
+    }
+}
+// everything else (f32; 16-bit rows the kernel above refuses: V > 32768, V % 8 != 0, a base that is not 16-B aligned): one pass with a
+// running (maximum, sum) per lane as in ce_fwd_bwd_kernel -- the label's logit is known before the pass, so the count rides along.
+template <typename T>
+__global__ __launch_bounds__(256) void ce_eval_kernel(const T* __restrict__ logits, const long* __restrict__ labels,
+                                                      const float* __restrict__ weights, float* __restrict__ loss_sum,
+                                                      unsigned long long* __restrict__ counts, int V, long ld) {
+    __shared__ float shm_[8];
+    __shared__ int shc_[4];
+    const long row = blockIdx.x;
+    const long label = labels[row];
+    if (label < 0 || label >= (long)V) return;
+    const T* x = logits + row * ld;
+    const int nv = V >> 2;
+    const float xl = to_f<T>(x[label]);
+    float mx = -INFINITY, sm = 0.f;
+    int cnt = 0;
+    for (int c = threadIdx.x; c < nv; c += 256) {
+        float p[4];
+        ld4<T>(x + c * 4, p);
+        const float m4 = fmaxf(fmaxf(p[0], p[1]), fmaxf(p[2], p[3]));
+        if (m4 > mx) {
+            sm *= __expf(mx - m4);
+            mx = m4;
+        }
+        sm += __expf(p[0] - mx) + __expf(p[1] - mx) + __expf(p[2] - mx) + __expf(p[3] - mx);
+        cnt += (p[0] > xl ? 1 : 0) + (p[1] > xl ? 1 : 0) + (p[2] > xl ? 1 : 0) + (p[3] > xl ? 1 : 0);
+    }
+    const float wm = wave_max(mx);
+    sm = mx == -INFINITY ? 0.f : sm * __expf(mx - wm);   // a lane (or a whole wave) without elements: exp(-inf + inf) would be NaN
+    sm = wave_sum(sm);
+    cnt = wave_sum_i(cnt);
+    if ((threadIdx.x & 63) == 0) {
+        shm_[threadIdx.x >> 6] = wm;
+        shm_[4 + (threadIdx.x >> 6)] = sm;
+        shc_[threadIdx.x >> 6] = cnt;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float gmx = fmaxf(fmaxf(shm_[0], shm_[1]), fmaxf(shm_[2], shm_[3]));
+        float gsm = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) gsm += shm_[k] == -INFINITY ? 0.f : shm_[4 + k] * __expf(shm_[k] - gmx);
+        ce_eval_flush(loss_sum, counts, weights[row] * (gmx + __logf(gsm) - xl), shc_[0] + shc_[1] + shc_[2] + shc_[3]);
+    }
+}
+extern "C" int ecamp_ce_eval(const void* logits, const int64_t* labels, const float* weights, float* loss_sum, int64_t* counts, int64_t M,
+                             int32_t V, int64_t ld, int32_t dtype, hipStream_t stream) {
+    ECAMP_CHECK_ARG(logits && labels && weights && loss_sum && counts, "ce_eval: null pointer");
+    ECAMP_CHECK_ARG(V > 0 && V % 4 == 0 && ld % 4 == 0 && ld >= V, "ce_eval: V=%d and ld=%ld must be multiples of 4 (ld >= V > 0)", V, (long)ld);
+    ECAMP_CHECK_ARG(M >= 0 && M <= 0x7fffffffLL, "ce_eval: M=%ld rows do not fit one launch", (long)M);
+    ECAMP_CHECK_ARG(dtype == ECAMP_F32 || dtype == ECAMP_BF16, "ce_eval: dtype %d", dtype);
+    if (M == 0) return 0;
+    dim3 grid((unsigned)M);
+    unsigned long long* cn = reinterpret_cast<unsigned long long*>(counts);
+    if (dtype == ECAMP_BF16 && V % 8 == 0 && ld % 8 == 0 && V <= 32768 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0) {
+#define CE_EVAL(NG_, NT_) hipLaunchKernelGGL((ce_eval_row_kernel<NG_, NT_>), grid, dim3(NT_), 0, stream, (const bf16_t*)logits, (const long*)labels, weights, loss_sum, cn, V, (long)ld)
+        if (V <= 4096) CE_EVAL(1, 512); else if (V <= 8192) CE_EVAL(2, 512); else if (V <= 16384) CE_EVAL(4, 512); else CE_EVAL(4, 1024);
+#undef CE_EVAL
+    } else if (dtype == ECAMP_F32) {
+        hipLaunchKernelGGL(ce_eval_kernel<float>, grid, dim3(256), 0, stream, (const float*)logits, (const long*)labels, weights, loss_sum, cn, V, (long)ld);
+    } else {
+        hipLaunchKernelGGL(ce_eval_kernel<bf16_t>, grid, dim3(256), 0, stream, (const bf16_t*)logits, (const long*)labels, weights, loss_sum, cn, V, (long)ld);
+    }
+    ECAMP_LAUNCH_CHECK();
+    return 0;
+}

@@ -7,12 +7,17 @@ the reference calls `.item()` x3 + `torch.cuda.synchronize()` + three scalar all
 (:143-145,155,164-166); here the three losses stay on the device, are all-reduced as ONE 3-float message, and
 are only read back when a meter is printed (every `print_freq` steps) or averaged at the end of the epoch.
 Gradient all-reduce runs once per optimizer step (not per micro-step), overlapped with backward.
+
+`evaluate` (no reference counterpart: the reference has no validation loop) is the held-out pass: `ECAMP.forward_eval` over a loader,
+the three losses and the masked-token top-1 / top-5 accuracy summed on the device, one all-reduce and one read-back at the end.
 """
 import contextlib
 import ctypes
 import math
+import random
 from typing import Iterable
 
+import numpy as np
 import torch
 
 from .util import lr_sched, misc
@@ -122,3 +127,77 @@ def train_one_epoch(model: torch.nn.Module, data_loader: Iterable, optimizer: to
     metric_logger.synchronize_between_processes()
     print("Averaged stats:", metric_logger)
     return {k: meter.global_avg for k, meter in metric_logger.meters.items()}
+
+
+# --------------------------------------------------------------------------------------------- held-out evaluation
+EVAL_SEED = 0x45434D50   # the masking noise (and the host-side draws of a validation dataset) of every evaluation pass: the same at every epoch
+EVAL_KEYS = ("val_mim_loss", "val_res_loss", "val_mlm_loss", "val_mlm_top1", "val_mlm_top5", "val_mlm_tokens")
+
+
+def eval_noise_key(rank, batch_index):
+    """(seed, offset) of the Philox stream that masks the images of batch `batch_index` on rank `rank` in an evaluation pass."""
+    return EVAL_SEED, (int(rank) << 32) | int(batch_index)
+
+
+def eval_batch_sums(losses, counts, n):
+    """One batch's contribution to the sums of an evaluation pass, f64[7]: [n, n * mim, n * res, n * mlm, tokens scored, top-1, top-5] --
+    `losses` the three batch means, `counts` the head's int64[3], `n` the batch's samples (a short last batch counts by its size).
+    Sums of such vectors -- over batches, then over ranks -- are what `eval_stats` reads; f64 keeps the counts exact below 2^53."""
+    losses = losses.to(torch.float64)
+    return torch.cat([losses.new_full((1,), float(n)), losses * float(n), counts.to(torch.float64)])
+
+
+def eval_stats(sums):
+    """The sums of `eval_batch_sums` over the whole loader and every rank (7 numbers) -> the `val_*` dict: sample-weighted mean losses,
+    accuracies as pooled counts (sum of hits / sum of scored tokens; 0.0 when no token was scored) and the token count."""
+    n, mim, res, mlm, tok, top1, top5 = (float(v) for v in sums)
+    per = lambda v: v / n if n > 0 else 0.0
+    acc = lambda v: v / tok if tok > 0 else 0.0
+    return {"val_mim_loss": per(mim), "val_res_loss": per(res), "val_mlm_loss": per(mlm), "val_mlm_top1": acc(top1), "val_mlm_top5": acc(top5),
+            "val_mlm_tokens": int(round(tok))}
+
+
+def evaluate(model, data_loader, device, epoch, log_writer=None, args=None):
+    """One pass of `ECAMP.forward_eval` over `data_loader` (held-out data) -> {val_mim_loss, val_res_loss, val_mlm_loss, val_mlm_top1,
+    val_mlm_top5, val_mlm_tokens}; TensorBoard scalars under the same names at `epoch * 1000`.
+
+    Comparable across epochs: batch i on rank r is masked with `ops.uniform` noise keyed by `eval_noise_key(r, i)`, handed over as
+    `noise=`; a loader with a generator of its own has it re-seeded, and the host generators a dataset may draw from (`random`, NumPy,
+    torch) are seeded for the loop.  Without effect on training: on return the model's mode, its Philox counter, those three host
+    generators, the gradient arena and every `.grad` are what they were."""
+    from . import hip_ops as ops
+    m = model.module if hasattr(model, "module") else model   # parallel.DistributedDataParallel: evaluation needs no reducer
+    mask_ratio = getattr(args, "mask_ratio", 0.75)
+    rank = misc.get_rank()
+    m.prepare()
+    saved = (m._rng_ctr, m._rng_trace, random.getstate(), np.random.get_state(), torch.get_rng_state())
+    try:
+        m._rng_trace = None
+        random.seed(EVAL_SEED + rank)
+        np.random.seed((EVAL_SEED + rank) & 0xFFFFFFFF)
+        torch.default_generator.manual_seed(EVAL_SEED + rank)
+        if getattr(data_loader, "generator", None) is not None:
+            data_loader.generator.manual_seed(EVAL_SEED + rank)
+        if torch.device(device).type == "cuda" and getattr(args, "prefetch", True):
+            from .data import DevicePrefetcher
+            data_loader = DevicePrefetcher(data_loader, device)
+        dev = m.arena.device
+        total = torch.zeros(7, dtype=torch.float64, device=dev)
+        for i, batch in enumerate(data_loader):
+            n = batch["labels"].shape[0] if batch["labels"].dim() > 1 else 1
+            noise = ops.uniform((n, m.num_patches), dev, *eval_noise_key(rank, i))
+            out = m.forward_eval(batch, mask_ratio=mask_ratio, noise=noise)
+            total += eval_batch_sums(torch.stack([out["mim_loss"], out["res_loss"], out["mlm_loss"]]), out["mlm_counts"], n)
+        if misc.get_world_size() > 1:
+            torch.distributed.all_reduce(total)
+        stats = eval_stats(total.tolist())   # the pass's one read-back
+    finally:
+        m._rng_ctr, m._rng_trace = saved[0], saved[1]
+        random.setstate(saved[2])
+        np.random.set_state(saved[3])
+        torch.set_rng_state(saved[4])
+    if log_writer is not None:
+        for k in EVAL_KEYS:
+            log_writer.add_scalar(k, stats[k], epoch * 1000)
+    print("Evaluation [{}]: {}".format(epoch, "  ".join(("{} {:d}" if isinstance(stats[k], int) else "{} {:.4f}").format(k, stats[k]) for k in EVAL_KEYS)))
+    return stats

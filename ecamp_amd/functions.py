@@ -670,28 +670,52 @@ class FusionFn(torch.autograd.Function):
 
 
 # =============================================================================================
+def _mlm_transform(m, h, pr):
+    """The MLM head's transform (dense + GELU + LayerNorm, bert_modeling.py:209) -> (t1, pre, mean, rstd, t, t8).  fp8 forward with
+    model.fp8_head: the dense layer runs on the e4m3 kernel and the LayerNorm quantises its own output for the decoder (`t8`, else None)."""
+    ln = pr.transform.LayerNorm
+    if m.fp8_forward and m.fp8_head:
+        t1, pre = _dense(m, h, pr.transform.dense.weight, pr.transform.dense.bias.data, act=1, save_pre=True)
+        t, _, mean, rstd, t8 = _ln_q8(m, t1, ln, pr.decoder.weight)
+        return t1, pre, mean, rstd, t, t8
+    t1, pre = ops.linear_fwd(h, m.arena.w(pr.transform.dense.weight), pr.transform.dense.bias.data, act=1, save_pre=True)
+    t, _, mean, rstd = ops.layernorm_fwd(t1, ln.weight.data, ln.bias.data, ln.eps)
+    return t1, pre, mean, rstd, t, None
+
+
+def _mlm_decoder(m, t, t8, pr):
+    """The 30000-way decoder on the transform's output -> logits [M, V]."""
+    if m.fp8_forward and m.fp8_head:
+        return _dense(m, t, pr.decoder.weight, pr.bias.data, x8=t8)
+    return ops.linear_fwd(t, m.arena.w(pr.decoder.weight), pr.bias.data)
+
+
+def mlm_head_eval(h, labels, weights, cls, m):
+    """The head of a held-out pass: MlmHeadFn's forward with `ce_eval` in place of `ce_fwd_bwd_` -- the logits are read, for the rows
+    that carry a label only, and never written -> (loss: the scalar MlmHeadFn returns, counts int64[3] = [tokens scored, label ranks
+    first, label within the first five]).  No gradient exists on this path: call it under torch.no_grad()."""
+    pr = cls.predictions
+    _, _, _, _, t, t8 = _mlm_transform(m, h, pr)
+    logits = _mlm_decoder(m, t, t8, pr)
+    if m.keep_aux:
+        m._aux_logits = logits      # nothing overwrites them here: no copy
+    s, counts = ops.ce_eval(logits, labels.view(-1), weights.view(-1))
+    return s * (1.0 / logits.shape[0]), counts
+
+
 class MlmHeadFn(torch.autograd.Function):
     """transform(dense+GELU+LN) -> 30000-way decoder -> weighted CE, mean over ALL B*S rows (bert_modeling.py:209-217).
     The CE kernel overwrites the logits with d loss / d logits, so the largest activation of the model exists once."""
 
     @staticmethod
     def forward(ctx, h, labels, weights, cls, m):
-        A = m.arena
         pr = cls.predictions
         # (fp8 forward, model.fp8_head: the transform dense layer and the 30000-way decoder on the e4m3 kernel as well; the decoder's input
         # is quantised inside the transform LayerNorm)
-        if m.fp8_forward and m.fp8_head:
-            t1, pre = _dense(m, h, pr.transform.dense.weight, pr.transform.dense.bias.data, act=1, save_pre=True)
-            ln = pr.transform.LayerNorm
-            t, _, mean, rstd, t8 = _ln_q8(m, t1, ln, pr.decoder.weight)
-            logits = _dense(m, t, pr.decoder.weight, pr.bias.data, x8=t8)
-        else:
-            t1, pre = ops.linear_fwd(h, A.w(pr.transform.dense.weight), pr.transform.dense.bias.data, act=1, save_pre=True)
-            ln = pr.transform.LayerNorm
-            t, _, mean, rstd = ops.layernorm_fwd(t1, ln.weight.data, ln.bias.data, ln.eps)
-            if _MLM_CHUNK_ROWS > 0 and t.shape[0] > _MLM_CHUNK_ROWS and ctx.needs_input_grad[0] and not m.keep_aux:
-                return MlmHeadFn._chunked(ctx, h, labels, weights, cls, m, t1, pre, mean, rstd, t, _MLM_CHUNK_ROWS)
-            logits = ops.linear_fwd(t, A.w(pr.decoder.weight), pr.bias.data)
+        t1, pre, mean, rstd, t, t8 = _mlm_transform(m, h, pr)
+        if not (m.fp8_forward and m.fp8_head) and _MLM_CHUNK_ROWS > 0 and t.shape[0] > _MLM_CHUNK_ROWS and ctx.needs_input_grad[0] and not m.keep_aux:
+            return MlmHeadFn._chunked(ctx, h, labels, weights, cls, m, t1, pre, mean, rstd, t, _MLM_CHUNK_ROWS)
+        logits = _mlm_decoder(m, t, t8, pr)
         if m.keep_aux:
             m._aux_logits = logits.clone()
         s = ops.zeros((1,), h.device)

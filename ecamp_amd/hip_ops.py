@@ -584,6 +584,18 @@ def ce_fwd_bwd_(logits, labels, weights, loss_sum, gain=1.0):
     return logits
 
 
+def ce_eval(logits, labels, weights):
+    """Evaluation form of the head's loss (read-only on `logits` [M, V]): -> (loss_sum f32[1] = sum_i w_i CE_i over the rows whose label
+    lies in [0, V), counts int64[3] = [rows scored, label ranks first, label within the first five]); rank = logits strictly above the
+    label's.  Rows with an ignored label are never read."""
+    _chk(logits, labels, weights)
+    M, V = logits.shape
+    assert logits.stride(1) == 1 and labels.numel() == M and weights.numel() == M
+    loss_sum, counts = zeros((1,), logits.device), zeros((3,), logits.device, torch.int64)
+    call("ecamp_ce_eval", ptr(logits), ptr(labels), ptr(weights), ptr(loss_sum), ptr(counts), M, V, logits.stride(0), code(logits.dtype), stream())
+    return loss_sum, counts
+
+
 # --------------------------------------------------------------------------------------------- optimizer side
 def sumsq(x, out):
     call("ecamp_sumsq", ptr(x), x.numel(), ptr(out), stream())

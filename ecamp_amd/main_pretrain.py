@@ -3,7 +3,8 @@ unchanged), on the MI355X-native model / optimizer / data-parallel reducer.
 
     python -m torch.distributed.run --nproc_per_node=8 -m ecamp_amd.main_pretrain --batch_size 256 --accum_iter 8 ...
 
-Extra flags (all optional): --compute_dtype {bf16,fp16,fp32} (--amp fp16), --max_caption_length, --synthetic, --synthetic_len, --print_freq, --profile, --no_prefetch.
+Extra flags (all optional): --compute_dtype {bf16,fp16,fp32} (--amp fp16), --max_caption_length, --synthetic, --synthetic_len, --print_freq, --profile, --no_prefetch,
+--eval_freq / --val_data_path / --val_batch_size / --eval_only (held-out evaluation, engine_pretrain.evaluate; off by default).
 When `--data_path` holds the MIMIC-CXR CSVs the `ContextBertDataset` of module/pretrain_datasets.py is used (batched
 entity-aware masker, bit-exact against the reference loop).  A missing CSV is an error (as in the reference) unless `--synthetic`
 asks for the synthetic stand-in with the same batch schema.  `--profile` puts roctx ranges around every step and its phases
@@ -25,7 +26,7 @@ from torch.utils.data import DataLoader, DistributedSampler
 
 from . import optim as optim_factory
 from .data import SyntheticContextBertDataset
-from .engine_pretrain import train_one_epoch  # noqa: F401  (re-exported: the reference defines it in this module)
+from .engine_pretrain import evaluate, train_one_epoch  # noqa: F401  (re-exported: the reference defines it in this module)
 from .module import model_ecamp
 from .parallel import DistributedDataParallel
 from .util import misc
@@ -96,6 +97,13 @@ def get_args_parser():
     p.add_argument("--no_prefetch", action="store_false", dest="prefetch", help="copy each batch inside forward like the reference does")
     p.set_defaults(prefetch=True)
     p.add_argument("--print_freq", default=20, type=int)
+    p.add_argument("--eval_freq", default=0, type=int, help="held-out evaluation (forward only: the three losses and the masked-token top-1 / top-5 "
+                   "accuracy, val_* keys in log.txt) after every N-th epoch and after the last; 0 (default) = never, the run is what it is without the flag")
+    p.add_argument("--val_data_path", default="", type=str, help="a directory laid out like --data_path (the same three file names) holding the "
+                   "held-out rows; required with --eval_freq > 0 or --eval_only unless --synthetic")
+    p.add_argument("--val_batch_size", default=None, type=int, help="batch size per GPU of the evaluation pass (default: --batch_size)")
+    p.add_argument("--eval_only", action="store_true", help="with --resume: load the checkpoint, run one evaluation pass, print and log its val_* "
+                   "dict and exit; no optimizer is built")
     p.add_argument("--snapshot_code", action="store_true", help="copy ./ into output_dir/job_dir like the reference does")
     return p
 
@@ -112,8 +120,61 @@ def build_model(args):
                                             f32_residual=args.f32_residual)
 
 
+def check_eval_args(args):
+    """The evaluation flags against each other -- before any device work, so a bad command line costs nothing."""
+    if args.eval_freq < 0:
+        raise SystemExit("--eval_freq must be >= 0")
+    if args.eval_only and not args.resume:
+        raise SystemExit("--eval_only needs --resume <checkpoint>")
+    if (args.eval_freq > 0 or args.eval_only) and not (args.val_data_path or args.synthetic):
+        raise SystemExit("--eval_freq / --eval_only need --val_data_path <held-out dataset directory> (or --synthetic)")
+
+
+def build_val_loader(args):
+    """The held-out set and its loader: rank-strided without shuffling, every sample once (drop_last=False), a generator of its own --
+    creating its iterator draws nothing from torch's global generator, so the training stream is what it is without evaluation."""
+    if args.synthetic:
+        dataset_val = SyntheticContextBertDataset(min(args.synthetic_len, 1024), args.max_caption_length, args.input_size, seed=args.seed + 1,
+                                                  image_u8=args.image_u8)
+    else:
+        csv = os.path.join(args.val_data_path, "mimic-cxr-2.0.0-entity-llm.csv")
+        if not os.path.exists(csv):
+            raise FileNotFoundError("%s not found: check --val_data_path (laid out like --data_path)" % csv)
+        from .module.pretrain_datasets import ContextBertDataset
+        state = (random.getstate(), np.random.get_state(), torch.get_rng_state())
+        try:
+            dataset_val = ContextBertDataset(args.val_data_path, max_caption_length=args.max_caption_length, image_u8=args.image_u8)
+        finally:   # (whatever building it draws is given back: the training stream does not depend on --eval_freq)
+            random.setstate(state[0])
+            np.random.set_state(state[1])
+            torch.set_rng_state(state[2])
+    sampler_val = DistributedSampler(dataset_val, num_replicas=misc.get_world_size(), rank=misc.get_rank(), shuffle=False)
+    return DataLoader(dataset_val, sampler=sampler_val, batch_size=args.val_batch_size or args.batch_size, num_workers=args.num_workers,
+                      pin_memory=args.pin_mem, drop_last=False, collate_fn=dataset_val.collate_fn, generator=torch.Generator())
+
+
+def eval_only(args, device):
+    """--eval_only --resume <checkpoint>: score a saved model on the held-out set -- no training data, no optimizer."""
+    args.data = "synthetic" if args.synthetic else "mimic-cxr"
+    data_loader_val = build_val_loader(args)
+    model = build_model(args)
+    model.to(device)
+    model.prepare()
+    args.eval = True   # (misc.load_model: the weights alone, whatever the checkpoint's path)
+    misc.load_model(args=args, model_without_ddp=model, optimizer=None, loss_scaler=None)
+    stats = evaluate(model, data_loader_val, device, args.start_epoch, args=args)
+    print(json.dumps(stats))
+    if args.output_dir and misc.is_main_process():
+        with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
+            f.write(json.dumps(dict(stats, eval_only=args.resume, data=args.data)) + "\n")
+    return stats
+
+
 def main(args):
+    check_eval_args(args)
     misc.init_distributed_mode(args)
+    if args.eval_only:
+        return eval_only(args, torch.device("cuda"))
     if args.lr is None:
         raise SystemExit("--lr is required (absolute learning rate), as in the reference")
     device = torch.device("cuda")
@@ -161,6 +222,7 @@ def main(args):
 
     data_loader_train = DataLoader(dataset_train, sampler=sampler_train, batch_size=args.batch_size, num_workers=args.num_workers,
                                    pin_memory=args.pin_mem, drop_last=True, collate_fn=dataset_train.collate_fn)
+    data_loader_val = build_val_loader(args) if args.eval_freq > 0 else None
 
     model = build_model(args)
     model.to(device)
@@ -199,6 +261,8 @@ def main(args):
             if (epoch == 0) or (60 <= epoch < 100 and epoch % 10 == 0) or (epoch >= 100 and (epoch % 5 == 0 or epoch + 1 == args.epochs)):
                 misc.save_model(args=args, model=model, model_without_ddp=model_without_ddp, optimizer=optimizer, loss_scaler=loss_scaler, epoch=epoch)
         log_stats = {**{f"train_{k}": v for k, v in train_stats.items()}, "epoch": epoch}
+        if data_loader_val is not None and ((epoch + 1) % args.eval_freq == 0 or epoch + 1 == args.epochs):
+            log_stats.update(evaluate(model, data_loader_val, device, epoch, log_writer=log_writer, args=args))
         if args.output_dir and misc.is_main_process():
             if log_writer is not None:
                 log_writer.flush()

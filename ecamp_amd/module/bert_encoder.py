@@ -10,5 +10,5 @@ class MultiModalBertEncoder(nn.Module):
         super().__init__()
         self.model = MultimodalBertMaskedLM(config if config is not None else BertConfig())
 
-    def forward(self, latent, gap_token, ids, labels, attn_mask, token_type, weights, owner, B, T):
-        return self.model(latent, gap_token, ids, attn_mask, token_type, weights, labels, owner, B, T)
+    def forward(self, latent, gap_token, ids, labels, attn_mask, token_type, weights, owner, B, T, eval_head=False):
+        return self.model(latent, gap_token, ids, attn_mask, token_type, weights, labels, owner, B, T, eval_head=eval_head)

@@ -47,8 +47,13 @@ class MultimodalBertMaskedLM(nn.Module):
         self.bert = MultimodalBertModel(config, add_pooling_layer=False)
         self.cls = BertOnlyMLMHead(config)
 
-    def forward(self, latent, gap_token, input_ids, attention_mask, token_type_ids, weights, labels, owner, B, T):
-        from ..functions import MlmHeadFn
+    def forward(self, latent, gap_token, input_ids, attention_mask, token_type_ids, weights, labels, owner, B, T, eval_head=False):
+        """eval_head (ECAMP.forward_eval, under no_grad): the head scores the logits without forming their gradient and the result also
+        carries `counts` -- int64[3]: tokens scored, label ranked first, label within the first five."""
+        from ..functions import MlmHeadFn, mlm_head_eval
         seq = self.bert(latent, gap_token, input_ids, attention_mask, token_type_ids, owner, B, T)
+        if eval_head:
+            loss, counts = mlm_head_eval(seq, labels, weights, self.cls, owner)
+            return types.SimpleNamespace(loss=loss[0], counts=counts, logits=None, hidden_states=None, attentions=None)
         loss = MlmHeadFn.apply(seq, labels, weights, self.cls, owner)
         return types.SimpleNamespace(loss=loss[0], logits=None, hidden_states=None, attentions=None)

@@ -317,8 +317,9 @@ class ECAMP(nn.Module):
         out = PixelLossFn.apply(full, f32(imgs), f32(big_imgs), f32(mask), i64(column), i64(row), self, B)
         return out[0], out[1]
 
-    def forward_report_decoder(self, latent, ids_keep, caption_ids, labels, attention_mask, token_type_ids, weights, B=None, T=None):
-        """model_ecamp.py:267-273 (`ids_keep` is unused there too).  `latent` is [B, T, D] as in the reference, or [B*T, D] with B, T."""
+    def forward_report_decoder(self, latent, ids_keep, caption_ids, labels, attention_mask, token_type_ids, weights, B=None, T=None, eval_head=False):
+        """model_ecamp.py:267-273 (`ids_keep` is unused there too).  `latent` is [B, T, D] as in the reference, or [B*T, D] with B, T.
+        eval_head (under no_grad, `forward_eval`): -> (loss, counts int64[3]) from the evaluation form of the head."""
         from ..functions import ReportStemFn
         if latent.dim() == 3:
             B, T = latent.shape[:2]
@@ -328,14 +329,19 @@ class ECAMP(nn.Module):
             caption_ids, labels, attention_mask, token_type_ids = (mv(t, torch.int64) for t in (caption_ids, labels, attention_mask, token_type_ids))
             weights = mv(weights, torch.float32)
         lat, gap = ReportStemFn.apply(latent, self, B, T)
-        out = self.bert_encoder(lat, gap, caption_ids, labels, attention_mask, token_type_ids, weights, self, B, T)
-        return out.loss
+        out = self.bert_encoder(lat, gap, caption_ids, labels, attention_mask, token_type_ids, weights, self, B, T, eval_head=eval_head)
+        return (out.loss, out.counts) if eval_head else out.loss
 
     def forward(self, batch, mask_ratio=0.75, noise=None, image_side_only=False):
         """batch: dict with the schema of pretrain_datasets.py:228-237 (CPU or device tensors).
         noise: optional [B, L] masking noise standing in for torch.rand at model_ecamp.py:177 (parity tests).
         image_side_only (measurement aid, bench.py `vit_*`): stem -> encoder -> decoder -> image losses (model_ecamp.py:218-264,276-300),
         i.e. the "ViT-B/16 forward+backward" the north-star target is quoted on, without the report side -> (mim_loss, res_loss, None)."""
+        return self._run(batch, mask_ratio, noise, image_side_only, False)[:3]
+
+    def _run(self, batch, mask_ratio, noise, image_side_only, eval_head):
+        """The stages of one pass, shared by `forward` and `forward_eval` -> (mim_loss, res_loss, mlm_loss, mlm_counts or None).
+        eval_head: the MLM head ends in the evaluation kernel (no gradient of the logits) and also returns its counts."""
         from ..functions import DecStemFn, ImgLossFn, NormFn, StemFn, VitBlockFn
         A = self.prepare()
         dev = A.device
@@ -383,7 +389,7 @@ class ECAMP(nn.Module):
         from .. import hip_ops as ops
         if image_side_only:
             img_losses = image_decoder()
-            return img_losses[0], img_losses[1], None
+            return img_losses[0], img_losses[1], None, None
         if ops.OVERLAP_BRANCHES and latent.is_cuda:
             # the two consumers of `latent` on two streams (see hip_ops.branch_stream)
             main, bs = torch.cuda.current_stream(dev), ops.branch_stream(dev)
@@ -392,18 +398,35 @@ class ECAMP(nn.Module):
                 img_losses = image_decoder()
             for t in (latent, imgs, big, mask, ids_restore, ids_keep, column, row):
                 t.record_stream(bs)   # (not hip_ops.hold: the branch's BACKWARD nodes read these again on `bs`, later than any fence taken here)
-            mlm_loss = self.forward_report_decoder(latent, ids_keep, ids, labels, attention_mask, type_ids, weights, B, T)
+            mlm_loss = self.forward_report_decoder(latent, ids_keep, ids, labels, attention_mask, type_ids, weights, B, T, eval_head=eval_head)
             main.wait_stream(bs)
             for t in img_losses:   # three scalars allocated on the branch stream and read by the CALLER on the main one, later than any point this
                 t.record_stream(main)   # function could fence: the allocator's own bookkeeping (no effect on its steady state at this size)
         else:
             img_losses = image_decoder()
-            mlm_loss = self.forward_report_decoder(latent, ids_keep, ids, labels, attention_mask, type_ids, weights, B, T)
+            mlm_loss = self.forward_report_decoder(latent, ids_keep, ids, labels, attention_mask, type_ids, weights, B, T, eval_head=eval_head)
+        mlm_loss, mlm_counts = mlm_loss if eval_head else (mlm_loss, None)
         if self.keep_aux:
             self._aux = dict(self._aux or {}, imgs=imgs, mask=mask, ids_restore=ids_restore, ids_keep=ids_keep,
                              latent=latent.view(B, T, -1), logits=self._aux_logits, **(getattr(self, "_aux_text", None) or {}))
-        return img_losses[0], img_losses[1], mlm_loss
+        return img_losses[0], img_losses[1], mlm_loss, mlm_counts
 
+    @torch.no_grad()
+    def forward_eval(self, batch, mask_ratio=0.75, noise=None):
+        """Held-out evaluation of one batch (no reference counterpart: the reference has no validation loop): the stages of `forward` --
+        every fused kernel, both image schemas, `--image_shard` batches, the same `batch` layout and `keep_aux` -- without a gradient, the
+        MLM head ending in `ce_eval`, which reads the logits of the rows that carry a label and writes nothing.  Evaluation semantics
+        (no dropout) whatever `self.training` is, which is left as it was.
+        -> dict of device tensors: `mim_loss`, `res_loss`, `mlm_loss` (the scalars `forward` returns) and `mlm_counts`, int64[3] =
+        [tokens scored, label ranked first, label within the first five]; a label tied with the largest logit counts as first."""
+        modes = [(mod, mod.training) for mod in self.modules()]
+        self.train(False)
+        try:
+            mim, res, mlm, counts = self._run(batch, mask_ratio, noise, False, True)
+        finally:
+            for mod, mode in modes:
+                mod.training = mode
+        return {"mim_loss": mim, "res_loss": res, "mlm_loss": mlm, "mlm_counts": counts}
 
     @torch.no_grad()
     def forward_visualization(self, imgs, text_ids, attention_mask, type_ids, mask_ratio=0, noise=None):

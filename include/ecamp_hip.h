@@ -29,7 +29,8 @@ typedef struct ihipStream_t* ecampStream_t; /* == hipStream_t */
  * ecamp_layernorm_fwd_x32, ecamp_layernorm_bwd_z32, ecamp_assemble_tokens_x32, ecamp_unshuffle_fwd_x32).  ecamp_abi_version()
  * returns the value the library was BUILT with; a consumer compares it with the header it was compiled against -- the Python binding
  * (ecamp_amd/_lib.py) refuses a library of another version, which is what protects an A/B of two builds (ECAMP_LIB, tools/ab_lib.sh)
- * from calling an older build with a newer argument list. */
+ * from calling an older build with a newer argument list.  ecamp_ce_eval was ADDED at version 5 without touching an existing
+ * signature: a build that lacks it is refused by the binding all the same, which resolves every declared symbol when it loads. */
 #define ECAMP_ABI_VERSION 5
 int ecamp_abi_version(void);
 const char* ecamp_last_error(void);
@@ -287,6 +288,14 @@ int ecamp_bert_embed_bwd(const void* de, const void* z, const float* mean, const
                          uint64_t offset, int32_t dtype, ecampStream_t stream);
 int ecamp_ce_fwd_bwd(void* logits, const int64_t* labels, const float* weights, float* loss_sum, int64_t M, int32_t V, int64_t ld,
                      float inv_count, int32_t dtype, ecampStream_t stream); /* bert_modeling.py:213-217 */
+/* Held-out evaluation of the same head (no reference counterpart: the reference has no validation loop).  Read-only on `logits`
+ * [M, V] (row stride ld; V and ld multiples of 4).  A row whose label lies outside [0, V) (ignore_index -100) is skipped without a
+ * read of its logits; for every other row, with xl = logit[label] and rank = #{ j : logit[j] > xl } (strictly greater: a label tied
+ * with the maximum ranks first):  loss_sum += w * (logsumexp(row) - xl) -- the quantity ecamp_ce_fwd_bwd accumulates; the caller
+ * divides by M --, counts[0] += 1, counts[1] += rank == 0, counts[2] += rank < 5.  counts is int64[3] (integer atomics: exact);
+ * the caller zeroes loss_sum and counts. */
+int ecamp_ce_eval(const void* logits, const int64_t* labels, const float* weights, float* loss_sum, int64_t* counts, int64_t M,
+                  int32_t V, int64_t ld, int32_t dtype, ecampStream_t stream);
 
 /* ---- optimizer side ---- */
 /* optimizer.zero_grad() (main_pretrain.py:169) without touching the weight matrices: zero the 64-element blocks of the gradient arena
