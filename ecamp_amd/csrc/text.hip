@@ -633,3 +633,171 @@ extern "C" int ecamp_ce_eval(const void* logits, const int64_t* labels, const fl
     ECAMP_LAUNCH_CHECK();
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Row compaction in front of the evaluation head: a held-out pass scores 15-30 % of the B*S positions (the [MASK]ed ones), and the
+// transform, the 30000-way decoder and ce_eval need only those rows.  Row m is SCORED iff 0 <= labels[m] < V and (ids == NULL or
+// ids[m] == mask_id); the scored rows of x (with label, weight and source index) move to the front of the outputs in increasing m,
+// output rows [count, cap) are padding (zeros, label -100, weight 0, index -1) and nothing at or beyond row `cap` is written.
+// Deterministic and order-preserving without atomics and without one workgroup waiting for another: three launches over segments of
+// COMPACT_SEG rows --
+//   1  compact_count_kernel   counts[s]  = scored rows of segment s (one ballot + popcount per wave)
+//   2  compact_sums_kernel    sums[u]    = sum of the COMPACT_SUP counts of super-segment u (64-bit: M reaches 2^31 - 1)
+//   3  compact_gather_kernel  workgroup s < nseg: base = sums before its super-segment + counts before it inside it, then its scored
+//                             rows move in 16-byte pieces, consecutive lanes on consecutive pieces of one row;
+//                             workgroups from nseg on: the padding, in pieces of 64 output rows; the first of them writes count_out
+// ws: int32 counts[nseg] (padded to 16 bytes), int64 sums[nsup].
+// ---------------------------------------------------------------------------------------------
+constexpr int COMPACT_SEG = 256, COMPACT_SUP = 1024, COMPACT_FILL = 64;
+__device__ __forceinline__ long wave_sum_l(long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// block sum for blockDim.x == 256; `sh` holds 4 longs.  All threads get the sum.
+__device__ __forceinline__ long block_sum_l_256(long v, long* sh) {
+    v = wave_sum_l(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return sh[0] + sh[1] + sh[2] + sh[3];
+}
+__device__ __forceinline__ bool compact_scored(const long* __restrict__ labels, const long* __restrict__ ids, long mask_id, long m, long M, int V) {
+    if (m >= M) return false;
+    const long label = labels[m];
+    return label >= 0 && label < (long)V && (ids == nullptr || ids[m] == mask_id);
+}
+__global__ __launch_bounds__(256) void compact_count_kernel(const long* __restrict__ labels, const long* __restrict__ ids, long mask_id,
+                                                            long M, int V, int* __restrict__ counts) {
+    __shared__ int shc_[4];
+    const long m = (long)blockIdx.x * COMPACT_SEG + threadIdx.x;
+    const unsigned long long b = __ballot(compact_scored(labels, ids, mask_id, m, M, V));
+    if ((threadIdx.x & 63) == 0) shc_[threadIdx.x >> 6] = __popcll(b);
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = shc_[0] + shc_[1] + shc_[2] + shc_[3];
+}
+__global__ __launch_bounds__(256) void compact_sums_kernel(const int* __restrict__ counts, long nseg, long* __restrict__ sums) {
+    __shared__ long shl_[4];
+    const long s0 = (long)blockIdx.x * COMPACT_SUP;
+    long v = 0;
+    for (int k = threadIdx.x; k < COMPACT_SUP; k += 256)
+        if (s0 + k < nseg) v += counts[s0 + k];
+    v = block_sum_l_256(v, shl_);
+    if (threadIdx.x == 0) sums[blockIdx.x] = v;
+}
+// 16-byte pieces [0, n * nchunk) of n rows over 256 threads: thread t starts at piece t and advances by 256, kept as (row, piece in row)
+// so that no index is formed that a long row could overflow
+struct CompactCursor {
+    int r, c, dr, dc;
+    __device__ __forceinline__ CompactCursor(int nchunk) : r(threadIdx.x / nchunk), c(threadIdx.x % nchunk), dr(256 / nchunk), dc(256 % nchunk) {}
+    __device__ __forceinline__ void next(int nchunk) {
+        r += dr;
+        c += dc;
+        if (c >= nchunk) {
+            c -= nchunk;
+            ++r;
+        }
+    }
+};
+__global__ __launch_bounds__(256) void compact_gather_kernel(const char* __restrict__ x, long row_bytes_in, const long* __restrict__ labels,
+                                                             const float* __restrict__ weights, const long* __restrict__ ids, long mask_id,
+                                                             long M, int V, int nchunk, long cap, long nseg, long nsup,
+                                                             const int* __restrict__ counts, const long* __restrict__ sums,
+                                                             char* __restrict__ x_out, long* __restrict__ labels_out,
+                                                             float* __restrict__ weights_out, int* __restrict__ rows_out,
+                                                             long* __restrict__ count_out) {
+    __shared__ long shl_[4];
+    __shared__ int shc_[4];
+    __shared__ int src_[COMPACT_SEG];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long row_bytes = (long)nchunk * 16;
+    if ((long)blockIdx.x >= nseg) {
+        // padding: the total is the sum of every super-segment
+        long v = 0;
+        for (long u = threadIdx.x; u < nsup; u += 256) v += sums[u];
+        const long count = block_sum_l_256(v, shl_);
+        if ((long)blockIdx.x == nseg && threadIdx.x == 0) count_out[0] = count;
+        const long nfill = (cap + COMPACT_FILL - 1) / COMPACT_FILL;
+        for (long j = (long)blockIdx.x - nseg; j < nfill; j += (long)gridDim.x - nseg) {
+            const long first = j * COMPACT_FILL;
+            const long lo = count > first ? count : first, hi = first + COMPACT_FILL < cap ? first + COMPACT_FILL : cap;
+            if (lo >= hi) continue;
+            const int n = (int)(hi - lo);
+            if ((int)threadIdx.x < n) {
+                labels_out[lo + threadIdx.x] = -100;
+                weights_out[lo + threadIdx.x] = 0.f;
+                rows_out[lo + threadIdx.x] = -1;
+            }
+            for (CompactCursor p(nchunk); p.r < n; p.next(nchunk))
+                *reinterpret_cast<uint4*>(x_out + (lo + p.r) * row_bytes + (long)p.c * 16) = make_uint4(0u, 0u, 0u, 0u);
+        }
+        return;
+    }
+    const long seg = blockIdx.x, sup = seg / COMPACT_SUP;
+    long v = 0;
+    for (long u = threadIdx.x; u < sup; u += 256) v += sums[u];
+    for (long s = sup * COMPACT_SUP + threadIdx.x; s < seg; s += 256) v += counts[s];
+    const long base = block_sum_l_256(v, shl_);
+    if (base >= cap) return;   // uniform over the workgroup: every row of this segment lies beyond the capacity
+    const long m = seg * COMPACT_SEG + threadIdx.x;
+    const bool scored = compact_scored(labels, ids, mask_id, m, M, V);
+    const unsigned long long b = __ballot(scored);
+    if (lane == 0) shc_[wave] = __popcll(b);
+    __syncthreads();
+    int before = __popcll(b & ((1ull << lane) - 1ull));   // scored rows in front of this one: in its wave, then in the waves before it
+    for (int k = 0; k < wave; ++k) before += shc_[k];
+    const int total = shc_[0] + shc_[1] + shc_[2] + shc_[3];
+    const int n = base + total <= cap ? total : (int)(cap - base);   // rows of this segment that fit
+    if (scored && before < n) {
+        src_[before] = threadIdx.x;
+        labels_out[base + before] = labels[m];
+        weights_out[base + before] = weights[m];
+        rows_out[base + before] = (int)m;
+    }
+    __syncthreads();
+    for (CompactCursor p(nchunk); p.r < n; p.next(nchunk)) {
+        const long from = seg * COMPACT_SEG + src_[p.r];
+        *reinterpret_cast<uint4*>(x_out + (base + p.r) * row_bytes + (long)p.c * 16) =
+            *reinterpret_cast<const uint4*>(x + from * row_bytes_in + (long)p.c * 16);
+    }
+}
+static void compact_layout(int64_t M, int64_t* nseg, int64_t* nsup, int64_t* counts_bytes) {
+    *nseg = (M + COMPACT_SEG - 1) / COMPACT_SEG;
+    *nsup = (*nseg + COMPACT_SUP - 1) / COMPACT_SUP;
+    if (*nsup < 1) *nsup = 1;
+    *counts_bytes = (*nseg * 4 + 15) / 16 * 16;
+}
+extern "C" int64_t ecamp_compact_rows_workspace_bytes(int64_t M) {
+    if (M < 0 || M > 0x7fffffffLL) return ecamp_set_error(-1, "compact_rows_workspace_bytes: M=%ld outside [0, 2^31 - 1]", (long)M);
+    int64_t nseg, nsup, cb;
+    compact_layout(M, &nseg, &nsup, &cb);
+    return cb + nsup * 8;
+}
+extern "C" int ecamp_compact_rows(const void* x, int64_t ldx, const int64_t* labels, const float* weights, const int64_t* ids,
+                                  int64_t mask_id, int64_t M, int32_t cols, int32_t V, int64_t cap, void* x_out, int64_t* labels_out,
+                                  float* weights_out, int32_t* rows_out, int64_t* count_out, void* ws, int32_t dtype, hipStream_t stream) {
+    ECAMP_CHECK_ARG(x && labels && weights && x_out && labels_out && weights_out && rows_out && count_out && ws, "compact_rows: null pointer");
+    ECAMP_CHECK_ARG(dtype == ECAMP_F32 || dtype == ECAMP_BF16, "compact_rows: dtype %d", dtype);
+    ECAMP_CHECK_ARG(M >= 0 && M <= 0x7fffffffLL && cap >= 0 && cap <= 0x7fffffffLL, "compact_rows: M=%ld, cap=%ld outside [0, 2^31 - 1]", (long)M, (long)cap);
+    ECAMP_CHECK_ARG(cols > 0 && V > 0 && ldx >= cols, "compact_rows: cols=%d, V=%d, ldx=%ld (ldx >= cols > 0, V > 0)", cols, V, (long)ldx);
+    const int64_t es = dtype == ECAMP_F32 ? 4 : 2;
+    ECAMP_CHECK_ARG((cols * es) % 16 == 0 && (ldx * es) % 16 == 0, "compact_rows: cols=%d, ldx=%ld of %d-byte elements: a row and the row stride must be multiples of 16 bytes", cols, (long)ldx, (int)es);
+    ECAMP_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(x_out) | reinterpret_cast<uintptr_t>(ws)) & 15) == 0, "compact_rows: x, x_out and ws must be 16-byte aligned");
+    int64_t nseg, nsup, cb;
+    compact_layout(M, &nseg, &nsup, &cb);
+    int* counts = reinterpret_cast<int*>(ws);
+    long* sums = reinterpret_cast<long*>(reinterpret_cast<char*>(ws) + cb);
+    if (nseg > 0) {
+        hipLaunchKernelGGL(compact_count_kernel, dim3((unsigned)nseg), dim3(256), 0, stream, (const long*)labels, (const long*)ids, (long)mask_id, (long)M, V, counts);
+        ECAMP_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(compact_sums_kernel, dim3((unsigned)nsup), dim3(256), 0, stream, counts, (long)nseg, sums);
+    ECAMP_LAUNCH_CHECK();
+    int64_t nfill = (cap + COMPACT_FILL - 1) / COMPACT_FILL;   // padding workgroups stride over the 64-row pieces: the grid stays below 2^32 threads
+    nfill = nfill < 1 ? 1 : nfill > 4096 ? 4096 : nfill;        // (at least one: the first of them also writes count_out)
+    hipLaunchKernelGGL(compact_gather_kernel, dim3((unsigned)(nseg + nfill)), dim3(256), 0, stream, (const char*)x, (long)(ldx * es), (const long*)labels,
+                       weights, (const long*)ids, (long)mask_id, (long)M, V, (int)(cols * es / 16), (long)cap, (long)nseg, (long)nsup, counts, sums,
+                       (char*)x_out, (long*)labels_out, weights_out, (int*)rows_out, (long*)count_out);
+    ECAMP_LAUNCH_CHECK();
+    return 0;
+}

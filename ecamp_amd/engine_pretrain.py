@@ -9,7 +9,8 @@ are only read back when a meter is printed (every `print_freq` steps) or average
 Gradient all-reduce runs once per optimizer step (not per micro-step), overlapped with backward.
 
 `evaluate` (no reference counterpart: the reference has no validation loop) is the held-out pass: `ECAMP.forward_eval` over a loader,
-the three losses and the masked-token top-1 / top-5 accuracy summed on the device, one all-reduce and one read-back at the end.
+the three losses and the top-1 / top-5 accuracy of the MLM head summed on the device, one all-reduce and one read-back at the end; over every
+labelled position, or (`args.eval_score = "masked"`) over the [MASK]ed ones with the head run on those rows alone.
 """
 import contextlib
 import ctypes
@@ -157,9 +158,37 @@ def eval_stats(sums):
             "val_mlm_tokens": int(round(tok))}
 
 
+def eval_scored_rows(batch, score, vocab):
+    """The positions of `batch` that `ECAMP.forward_eval(batch, score=score)` scores, as a plain int: labels in [0, vocab), for
+    score "masked" only where the input token is [MASK].  On CPU tensors this is host arithmetic -- `evaluate` carries it in the batch
+    as `"mlm_rows"`, the row count of the compacted head, which the GEMMs need on the host; on device tensors it synchronises."""
+    from .data import MASK
+    if score not in ("all", "masked"):
+        raise ValueError("score must be 'all' or 'masked', got %r" % (score,))
+    labels = batch["labels"]
+    scored = (labels >= 0) & (labels < vocab)
+    if score == "masked":
+        scored &= batch["ids"] == MASK
+    return int(scored.sum())
+
+
+def _with_row_hints(loader, score, vocab):
+    """The loader's batches, each host-resident one carrying its scored-row count under "mlm_rows" (a device-resident batch goes through
+    as it is: `forward_eval` reads the count back itself)."""
+    for batch in loader:
+        if batch["labels"].device.type == "cpu":
+            batch = dict(batch, mlm_rows=eval_scored_rows(batch, score, vocab))
+        yield batch
+
+
 def evaluate(model, data_loader, device, epoch, log_writer=None, args=None):
     """One pass of `ECAMP.forward_eval` over `data_loader` (held-out data) -> {val_mim_loss, val_res_loss, val_mlm_loss, val_mlm_top1,
     val_mlm_top5, val_mlm_tokens}; TensorBoard scalars under the same names at `epoch * 1000`.
+
+    `args.eval_score` ("all", the default, or "masked") is `forward_eval`'s `score`: the same keys in both scopes, `val_mlm_tokens` says
+    which ran.  "masked" runs the head on the scored rows alone; their count per batch is formed on the host before the batch is staged
+    (`eval_scored_rows`) and checked at the pass's read-back against what the device found -- a short count would drop rows.
+    `args.eval_compact` (absent = None: compact exactly when the scope is "masked") is `forward_eval`'s `compact`, for measurements.
 
     Comparable across epochs: batch i on rank r is masked with `ops.uniform` noise keyed by `eval_noise_key(r, i)`, handed over as
     `noise=`; a loader with a generator of its own has it re-seeded, and the host generators a dataset may draw from (`random`, NumPy,
@@ -168,6 +197,9 @@ def evaluate(model, data_loader, device, epoch, log_writer=None, args=None):
     from . import hip_ops as ops
     m = model.module if hasattr(model, "module") else model   # parallel.DistributedDataParallel: evaluation needs no reducer
     mask_ratio = getattr(args, "mask_ratio", 0.75)
+    score = getattr(args, "eval_score", "all")
+    compact = getattr(args, "eval_compact", None)
+    compact = (score == "masked") if compact is None else bool(compact)
     rank = misc.get_rank()
     m.prepare()
     saved = (m._rng_ctr, m._rng_trace, random.getstate(), np.random.get_state(), torch.get_rng_state())
@@ -178,19 +210,31 @@ def evaluate(model, data_loader, device, epoch, log_writer=None, args=None):
         torch.default_generator.manual_seed(EVAL_SEED + rank)
         if getattr(data_loader, "generator", None) is not None:
             data_loader.generator.manual_seed(EVAL_SEED + rank)
+        if compact:
+            data_loader = _with_row_hints(data_loader, score, m.bert_config.vocab_size)
         if torch.device(device).type == "cuda" and getattr(args, "prefetch", True):
             from .data import DevicePrefetcher
-            data_loader = DevicePrefetcher(data_loader, device)
+            data_loader = DevicePrefetcher(data_loader, device)   # (passes the hint, a non-tensor, through)
         dev = m.arena.device
         total = torch.zeros(7, dtype=torch.float64, device=dev)
+        found = torch.zeros(1, dtype=torch.float64, device=dev)   # rows the gathers found in the hinted batches, against the hints' sum
+        hinted = 0
         for i, batch in enumerate(data_loader):
             n = batch["labels"].shape[0] if batch["labels"].dim() > 1 else 1
             noise = ops.uniform((n, m.num_patches), dev, *eval_noise_key(rank, i))
-            out = m.forward_eval(batch, mask_ratio=mask_ratio, noise=noise)
+            out = m.forward_eval(batch, mask_ratio=mask_ratio, noise=noise, score=score, compact=compact)
             total += eval_batch_sums(torch.stack([out["mim_loss"], out["res_loss"], out["mlm_loss"]]), out["mlm_counts"], n)
+            if batch.get("mlm_rows") is not None and "mlm_rows_found" in out:
+                hinted += int(batch["mlm_rows"])
+                found += out["mlm_rows_found"]
+        sums = torch.cat([total, found, found.new_full((1,), float(hinted))])
         if misc.get_world_size() > 1:
-            torch.distributed.all_reduce(total)
-        stats = eval_stats(total.tolist())   # the pass's one read-back
+            torch.distributed.all_reduce(sums)
+        sums = sums.tolist()   # the pass's one read-back
+        if sums[7] != sums[8]:
+            raise RuntimeError("evaluate: the batches' \"mlm_rows\" hints sum to %d scored rows, the device found %d -- a hint below the true "
+                               "count drops rows from the compacted head (engine_pretrain.eval_scored_rows gives the count)" % (sums[8], sums[7]))
+        stats = eval_stats(sums[:7])
     finally:
         m._rng_ctr, m._rng_trace = saved[0], saved[1]
         random.setstate(saved[2])

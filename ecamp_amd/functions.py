@@ -690,17 +690,46 @@ def _mlm_decoder(m, t, t8, pr):
     return ops.linear_fwd(t, m.arena.w(pr.decoder.weight), pr.bias.data)
 
 
-def mlm_head_eval(h, labels, weights, cls, m):
+def mlm_head_eval(h, labels, weights, cls, m, ids=None, rows_hint=None, compact=False):
     """The head of a held-out pass: MlmHeadFn's forward with `ce_eval` in place of `ce_fwd_bwd_` -- the logits are read, for the rows
     that carry a label only, and never written -> (loss: the scalar MlmHeadFn returns, counts int64[3] = [tokens scored, label ranks
-    first, label within the first five]).  No gradient exists on this path: call it under torch.no_grad()."""
+    first, label within the first five]).  No gradient exists on this path: call it under torch.no_grad().
+
+    ids (int64, the head's input tokens): only the positions holding [MASK] (ecamp_amd.data.MASK) are scored, the others count as
+    label -100.  compact: the scored rows of `h` are gathered in front of the transform (`ops.compact_rows`), so transform, decoder and
+    `ce_eval` run on `cap` rows -- the scored count rounded up to ops.COMPACT_GRANULE -- instead of all of them; the fp8 head needs
+    nothing of its own, the gather comes first.  The loss keeps its normalisation, sum / all rows of `h`, so both forms of one scope
+    agree.  rows_hint: the scored count, known on the host (engine_pretrain.eval_scored_rows); without it the count is read back from
+    the device once per call.  A hint below the true count would drop rows: `m._eval_found` holds the true count (int64[1] on the
+    device, None without compaction) for the caller to check.  With keep_aux the logits kept are the [cap, V] ones and
+    `m._aux_mlm_rows` lists the row of `h` behind each (int32[cap], -1 = padding)."""
+    from .data import MASK
     pr = cls.predictions
+    M = h.shape[0]
+    labels, weights = labels.view(-1), weights.view(-1)
+    ids = ids.view(-1) if ids is not None else None
+    m._eval_found = m._aux_mlm_rows = None
+    if compact:
+        V = pr.decoder.weight.shape[0]
+        if rows_hint is None:
+            # every row's worth of capacity, the count read back, the granules in use kept: one synchronisation
+            h, labels, weights, rows, found = ops.compact_rows(h, labels, weights, ids, MASK, V, cap=M)
+            cap = ops.compact_cap(found.item())
+            if cap <= M:
+                h, labels, weights, rows = h[:cap], labels[:cap], weights[:cap], rows[:cap]
+        else:
+            h, labels, weights, rows, found = ops.compact_rows(h, labels, weights, ids, MASK, V, cap=ops.compact_cap(rows_hint))
+        m._eval_found = found
+        if m.keep_aux:
+            m._aux_mlm_rows = rows
+    elif ids is not None:
+        labels = torch.where(ids == MASK, labels, torch.full_like(labels, -100))
     _, _, _, _, t, t8 = _mlm_transform(m, h, pr)
     logits = _mlm_decoder(m, t, t8, pr)
     if m.keep_aux:
         m._aux_logits = logits      # nothing overwrites them here: no copy
-    s, counts = ops.ce_eval(logits, labels.view(-1), weights.view(-1))
-    return s * (1.0 / logits.shape[0]), counts
+    s, counts = ops.ce_eval(logits, labels, weights)
+    return s * (1.0 / M), counts
 
 
 class MlmHeadFn(torch.autograd.Function):

@@ -596,6 +596,38 @@ def ce_eval(logits, labels, weights):
     return loss_sum, counts
 
 
+COMPACT_GRANULE = 256   # rows: the capacity of a compacted head is a multiple of it (whole GEMM tiles; equal-sized batches reuse allocator blocks)
+
+
+def compact_cap(count):
+    """Capacity for `count` scored rows: rounded up to COMPACT_GRANULE, one granule of padding when nothing is scored."""
+    return max(1, -(-int(count) // COMPACT_GRANULE)) * COMPACT_GRANULE
+
+
+def compact_rows(x, labels, weights, ids=None, mask_id=3, vocab=None, cap=None):
+    """The scored rows of x [M, cols] in front (ecamp_compact_rows): row m is scored iff 0 <= labels[m] < vocab and (ids is None or
+    ids[m] == mask_id; 3 = [MASK], ecamp_amd.data.MASK) -> (x_c [cap, cols], labels_c int64[cap], weights_c f32[cap], rows int32[cap],
+    count int64[1]): the scored rows in their order, `rows` their indices in x; rows [count, cap) are padding (zeros, -100, 0, -1).
+    `count` is the true number of scored rows, on the device, also where it exceeds `cap` (then the first `cap` were written).
+    cap=None: M, which always suffices."""
+    _chk(x, labels, weights, ids)
+    M, cols = x.shape
+    assert vocab is not None and x.stride(1) == 1 and labels.numel() == M and weights.numel() == M and (ids is None or ids.numel() == M)
+    assert labels.dtype == torch.int64 and weights.dtype == torch.float32 and (ids is None or ids.dtype == torch.int64)
+    assert labels.is_contiguous() and weights.is_contiguous() and (ids is None or ids.is_contiguous())
+    cap = M if cap is None else int(cap)
+    dev = x.device
+    x_c = torch.empty((cap, cols), device=dev, dtype=x.dtype)
+    labels_c = torch.empty((cap,), device=dev, dtype=torch.int64)
+    weights_c = torch.empty((cap,), device=dev, dtype=torch.float32)
+    rows = torch.empty((cap,), device=dev, dtype=torch.int32)
+    count = torch.empty((1,), device=dev, dtype=torch.int64)
+    ws = torch.empty((int(_lib.load().ecamp_compact_rows_workspace_bytes(M)),), device=dev, dtype=torch.uint8)
+    call("ecamp_compact_rows", ptr(x), x.stride(0), ptr(labels), ptr(weights), ptr(ids), int(mask_id), M, cols, int(vocab), cap, ptr(x_c),
+         ptr(labels_c), ptr(weights_c), ptr(rows), ptr(count), ptr(ws), code(x.dtype), stream())
+    return x_c, labels_c, weights_c, rows, count
+
+
 # --------------------------------------------------------------------------------------------- optimizer side
 def sumsq(x, out):
     call("ecamp_sumsq", ptr(x), x.numel(), ptr(out), stream())

@@ -4,7 +4,7 @@ unchanged), on the MI355X-native model / optimizer / data-parallel reducer.
     python -m torch.distributed.run --nproc_per_node=8 -m ecamp_amd.main_pretrain --batch_size 256 --accum_iter 8 ...
 
 Extra flags (all optional): --compute_dtype {bf16,fp16,fp32} (--amp fp16), --max_caption_length, --synthetic, --synthetic_len, --print_freq, --profile, --no_prefetch,
---eval_freq / --val_data_path / --val_batch_size / --eval_only (held-out evaluation, engine_pretrain.evaluate; off by default).
+--eval_freq / --val_data_path / --val_batch_size / --eval_only / --eval_score (held-out evaluation, engine_pretrain.evaluate; off by default).
 When `--data_path` holds the MIMIC-CXR CSVs the `ContextBertDataset` of module/pretrain_datasets.py is used (batched
 entity-aware masker, bit-exact against the reference loop).  A missing CSV is an error (as in the reference) unless `--synthetic`
 asks for the synthetic stand-in with the same batch schema.  `--profile` puts roctx ranges around every step and its phases
@@ -97,8 +97,13 @@ def get_args_parser():
     p.add_argument("--no_prefetch", action="store_false", dest="prefetch", help="copy each batch inside forward like the reference does")
     p.set_defaults(prefetch=True)
     p.add_argument("--print_freq", default=20, type=int)
-    p.add_argument("--eval_freq", default=0, type=int, help="held-out evaluation (forward only: the three losses and the masked-token top-1 / top-5 "
-                   "accuracy, val_* keys in log.txt) after every N-th epoch and after the last; 0 (default) = never, the run is what it is without the flag")
+    p.add_argument("--eval_freq", default=0, type=int, help="held-out evaluation (forward only: the three losses and the MLM head's top-1 / top-5 "
+                   "accuracy, val_* keys in log.txt) after every N-th epoch and after the last; 0 (default) = never, the run is what it is without the "
+                   "flag.  Which positions the MLM figures cover is --eval_score")
+    p.add_argument("--eval_score", default="all", choices=["all", "masked"], help="positions the MLM head scores in an evaluation pass: all (default) = "
+                   "every position that carries a label -- the dataset labels each position with its original token, so visible tokens and the PAD "
+                   "tail are pooled in; masked = only the positions whose input token is [MASK]: the masked-token accuracy, the head run on those "
+                   "rows alone.  val_mlm_tokens tells which scope ran; val_mlm_loss stays the scored rows' sum over all positions")
     p.add_argument("--val_data_path", default="", type=str, help="a directory laid out like --data_path (the same three file names) holding the "
                    "held-out rows; required with --eval_freq > 0 or --eval_only unless --synthetic")
     p.add_argument("--val_batch_size", default=None, type=int, help="batch size per GPU of the evaluation pass (default: --batch_size)")
@@ -126,6 +131,10 @@ def check_eval_args(args):
         raise SystemExit("--eval_freq must be >= 0")
     if args.eval_only and not args.resume:
         raise SystemExit("--eval_only needs --resume <checkpoint>")
+    if args.eval_score not in ("all", "masked"):
+        raise SystemExit("--eval_score must be all or masked")
+    if args.eval_score != "all" and not (args.eval_freq > 0 or args.eval_only):
+        raise SystemExit("--eval_score has no effect without --eval_freq N or --eval_only")
     if (args.eval_freq > 0 or args.eval_only) and not (args.val_data_path or args.synthetic):
         raise SystemExit("--eval_freq / --eval_only need --val_data_path <held-out dataset directory> (or --synthetic)")
 

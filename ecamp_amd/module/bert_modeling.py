@@ -49,11 +49,14 @@ class MultimodalBertMaskedLM(nn.Module):
 
     def forward(self, latent, gap_token, input_ids, attention_mask, token_type_ids, weights, labels, owner, B, T, eval_head=False):
         """eval_head (ECAMP.forward_eval, under no_grad): the head scores the logits without forming their gradient and the result also
-        carries `counts` -- int64[3]: tokens scored, label ranked first, label within the first five."""
+        carries `counts` -- int64[3]: tokens scored, label ranked first, label within the first five.  True, or a dict of
+        functions.mlm_head_eval's options: `masked` (score the [MASK] positions of `input_ids` only), `compact`, `rows_hint`."""
         from ..functions import MlmHeadFn, mlm_head_eval
         seq = self.bert(latent, gap_token, input_ids, attention_mask, token_type_ids, owner, B, T)
         if eval_head:
-            loss, counts = mlm_head_eval(seq, labels, weights, self.cls, owner)
+            opt = eval_head if isinstance(eval_head, dict) else {}
+            loss, counts = mlm_head_eval(seq, labels, weights, self.cls, owner, ids=input_ids if opt.get("masked") else None,
+                                         rows_hint=opt.get("rows_hint"), compact=bool(opt.get("compact")))
             return types.SimpleNamespace(loss=loss[0], counts=counts, logits=None, hidden_states=None, attentions=None)
         loss = MlmHeadFn.apply(seq, labels, weights, self.cls, owner)
         return types.SimpleNamespace(loss=loss[0], logits=None, hidden_states=None, attentions=None)

@@ -319,7 +319,8 @@ class ECAMP(nn.Module):
 
     def forward_report_decoder(self, latent, ids_keep, caption_ids, labels, attention_mask, token_type_ids, weights, B=None, T=None, eval_head=False):
         """model_ecamp.py:267-273 (`ids_keep` is unused there too).  `latent` is [B, T, D] as in the reference, or [B*T, D] with B, T.
-        eval_head (under no_grad, `forward_eval`): -> (loss, counts int64[3]) from the evaluation form of the head."""
+        eval_head (under no_grad, `forward_eval`; True or the options dict of MultimodalBertMaskedLM.forward): -> (loss, counts int64[3])
+        from the evaluation form of the head."""
         from ..functions import ReportStemFn
         if latent.dim() == 3:
             B, T = latent.shape[:2]
@@ -341,7 +342,8 @@ class ECAMP(nn.Module):
 
     def _run(self, batch, mask_ratio, noise, image_side_only, eval_head):
         """The stages of one pass, shared by `forward` and `forward_eval` -> (mim_loss, res_loss, mlm_loss, mlm_counts or None).
-        eval_head: the MLM head ends in the evaluation kernel (no gradient of the logits) and also returns its counts."""
+        eval_head (True, or the options dict of MultimodalBertMaskedLM.forward): the MLM head ends in the evaluation kernel (no gradient
+        of the logits) and also returns its counts."""
         from ..functions import DecStemFn, ImgLossFn, NormFn, StemFn, VitBlockFn
         A = self.prepare()
         dev = A.device
@@ -409,24 +411,45 @@ class ECAMP(nn.Module):
         if self.keep_aux:
             self._aux = dict(self._aux or {}, imgs=imgs, mask=mask, ids_restore=ids_restore, ids_keep=ids_keep,
                              latent=latent.view(B, T, -1), logits=self._aux_logits, **(getattr(self, "_aux_text", None) or {}))
+            if eval_head and getattr(self, "_aux_mlm_rows", None) is not None:   # a compacted head: the row of the batch behind each row of `logits`
+                self._aux["mlm_rows"] = self._aux_mlm_rows
         return img_losses[0], img_losses[1], mlm_loss, mlm_counts
 
     @torch.no_grad()
-    def forward_eval(self, batch, mask_ratio=0.75, noise=None):
+    def forward_eval(self, batch, mask_ratio=0.75, noise=None, score="all", compact=None):
         """Held-out evaluation of one batch (no reference counterpart: the reference has no validation loop): the stages of `forward` --
         every fused kernel, both image schemas, `--image_shard` batches, the same `batch` layout and `keep_aux` -- without a gradient, the
         MLM head ending in `ce_eval`, which reads the logits of the rows that carry a label and writes nothing.  Evaluation semantics
         (no dropout) whatever `self.training` is, which is left as it was.
+
+        score: "all" -- every position whose label lies in [0, V) (the datasets label every position with its original token, visible
+        tokens and the PAD tail included); "masked" -- of those, the positions whose input token is [MASK] (ecamp_amd.data.MASK): the
+        masked-token loss share and accuracy.  compact: gather the scored rows in front of the head, so that transform, decoder and
+        `ce_eval` run on them alone (functions.mlm_head_eval); None = exactly when score is "masked"; True with "all" serves batches
+        whose labels are -100 outside the scored positions.  The row count of the compacted head must be known on the host: it is
+        `batch["mlm_rows"]` (a plain int, the scored count of THIS scope: engine_pretrain.eval_scored_rows) where the batch carries
+        one, else it is read back from the device once per call -- a synchronisation; `evaluate` supplies the hint.
+        `mlm_loss` is the sum over the scored rows / all B*S rows in either form, so the scopes are parts of one sum.
         -> dict of device tensors: `mim_loss`, `res_loss`, `mlm_loss` (the scalars `forward` returns) and `mlm_counts`, int64[3] =
-        [tokens scored, label ranked first, label within the first five]; a label tied with the largest logit counts as first."""
+        [tokens scored, label ranked first, label within the first five]; a label tied with the largest logit counts as first.  With
+        compaction also `mlm_rows_found`, int64[1]: the scored rows the gather found -- more than the hint's capacity means rows were
+        dropped.  keep_aux then keeps the compacted logits [cap, V] and `mlm_rows`, the batch row behind each (-1 = padding)."""
+        if score not in ("all", "masked"):
+            raise ValueError("score must be 'all' or 'masked', got %r" % (score,))
+        compact = (score == "masked") if compact is None else bool(compact)
+        hint = batch.get("mlm_rows") if compact else None
+        head = {"masked": score == "masked", "compact": compact, "rows_hint": int(hint) if hint is not None else None}
         modes = [(mod, mod.training) for mod in self.modules()]
         self.train(False)
         try:
-            mim, res, mlm, counts = self._run(batch, mask_ratio, noise, False, True)
+            mim, res, mlm, counts = self._run(batch, mask_ratio, noise, False, head if (compact or score == "masked") else True)
         finally:
             for mod, mode in modes:
                 mod.training = mode
-        return {"mim_loss": mim, "res_loss": res, "mlm_loss": mlm, "mlm_counts": counts}
+        out = {"mim_loss": mim, "res_loss": res, "mlm_loss": mlm, "mlm_counts": counts}
+        if compact:
+            out["mlm_rows_found"] = self._eval_found
+        return out
 
     @torch.no_grad()
     def forward_visualization(self, imgs, text_ids, attention_mask, type_ids, mask_ratio=0, noise=None):

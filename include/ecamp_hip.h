@@ -296,6 +296,19 @@ int ecamp_ce_fwd_bwd(void* logits, const int64_t* labels, const float* weights, 
  * the caller zeroes loss_sum and counts. */
 int ecamp_ce_eval(const void* logits, const int64_t* labels, const float* weights, float* loss_sum, int64_t* counts, int64_t M,
                   int32_t V, int64_t ld, int32_t dtype, ecampStream_t stream);
+/* Row compaction in front of that head (no reference counterpart): a held-out pass scores a fraction of the B*S positions, and the
+ * head needs those rows only.  Row m of x [M, cols] (row stride ldx; f32 or the build's 16-bit format) is SCORED iff
+ * 0 <= labels[m] < V and (ids == NULL or ids[m] == mask_id).  The scored rows are written in increasing order of m -- the row to
+ * x_out [cap, cols] (contiguous), its label, its weight and rows_out[i] = m; output rows [count, cap) are padding: zeros, label -100,
+ * weight 0, rows_out -1 (the head and ecamp_ce_eval run over them unchanged).  count_out[0] receives the true number of scored rows
+ * even where it exceeds cap; nothing is written at or beyond row cap.  Deterministic: counts per segment, sums of counts, a gather
+ * in which every workgroup derives its own offset -- no atomics, no workgroup waits for another.  A row and the row stride must be
+ * multiples of 16 bytes, x / x_out / ws 16-byte aligned; M and cap at most 2^31 - 1.  ws: ecamp_compact_rows_workspace_bytes(M)
+ * bytes of device memory, scratch (added at version 5 like ecamp_ce_eval: no existing signature changes). */
+int64_t ecamp_compact_rows_workspace_bytes(int64_t M);
+int ecamp_compact_rows(const void* x, int64_t ldx, const int64_t* labels, const float* weights, const int64_t* ids, int64_t mask_id,
+                       int64_t M, int32_t cols, int32_t V, int64_t cap, void* x_out, int64_t* labels_out, float* weights_out,
+                       int32_t* rows_out, int64_t* count_out, void* ws, int32_t dtype, ecampStream_t stream);
 
 /* ---- optimizer side ---- */
 /* optimizer.zero_grad() (main_pretrain.py:169) without touching the weight matrices: zero the 64-element blocks of the gradient arena

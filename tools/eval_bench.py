@@ -5,8 +5,11 @@
      HIP events around each launch, the two kernels alternating in one loop, the logits restored (untimed) in front of every launch.
   2  one `engine_pretrain.evaluate` pass at B = 256, S = 128 over batches resident in HBM, in pairs/s, beside the forward-only protocol
      of `bench.py --full` (`forward` under no_grad, training mode, the same batch) and `forward_eval` on its own.
+  3  masked-token evaluation (profiles/eval_compact.txt; `--leg compact` runs this leg alone): `ecamp_compact_rows` on the head's input
+     [32768, 768] against a plain copy of the bytes it moves, and one `evaluate` pass at B = 256, S = 128 on `synthetic_batch` data with
+     score "masked", the head compacted and uncompacted, beside the default scope (the pass of part 2) -- the three alternating in one process.
 
-    python tools/eval_bench.py [--iters 20] [--batches 12] [--dtype bf16|fp16]
+    python tools/eval_bench.py [--iters 20] [--batches 12] [--dtype bf16|fp16] [--leg all|pass|compact]
 """
 import argparse
 import os
@@ -112,11 +115,80 @@ def bench_pass(dev, dtype, nb, B=256, S=128):
     print("   evaluate() returned", stats)
 
 
+def bench_compact(dev, dtype, iters, nb, rounds=5, B=256, S=128, H=768, V=30000):
+    from ecamp_amd import hip_ops as ops
+    from ecamp_amd.data import MASK, synthetic_batch
+    from ecamp_amd.engine_pretrain import eval_scored_rows, evaluate
+    from ecamp_amd.module import model_ecamp as me
+    host = [synthetic_batch(B, S, 448, seed=s) for s in (0, 1)]
+    hints = [eval_scored_rows(b, "masked", V) for b in host]
+    M = B * S
+    print("3  masked-token evaluation: synthetic_batch data, B = %d, S = %d: %s of %d positions hold [MASK] under a label" % (B, S, hints, M))
+    # a) the gather alone against a copy of the bytes it moves
+    g = torch.Generator().manual_seed(3)
+    h = torch.randn(M, H, generator=g).to(dev, dtype)
+    labels, weights, ids = (host[0][k].to(dev).view(-1) for k in ("labels", "weights", "ids"))
+    cap = ops.compact_cap(hints[0])
+    src, dst = h[:cap].clone(), torch.empty((cap, H), device=dev, dtype=dtype)
+    t = {"compact_rows": [], "copy": []}
+    for i in range(iters + 3):
+        for kind in ("compact_rows", "copy"):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            if kind == "copy":
+                dst.copy_(src)
+            else:
+                out = ops.compact_rows(h, labels, weights, ids, MASK, V, cap=cap)   # (its output and workspace allocations are inside the bracket)
+            b.record()
+            if i >= 3:
+                t[kind].append((a, b))
+    torch.cuda.synchronize()
+    assert int(out[4].item()) == hints[0]
+    nbytes = cap * H * h.element_size()
+    print("   a) %d scored rows of [%d, %d] %s -> [%d, %d] = %.2f MB written (three launches; reads %d labels, ids and the scored rows)"
+          % (hints[0], M, H, str(dtype).split(".")[-1], cap, H, nbytes / 1e6, M))
+    print("   %-34s %10s %10s %10s" % ("call", "median us", "min us", "max us"))
+    for kind in ("compact_rows", "copy"):
+        us = [1e3 * v for v in ms_of(t[kind])]
+        print("   %-34s %10.1f %10.1f %10.1f" % (kind if kind != "copy" else "copy_ of the same [%d, %d]" % (cap, H), statistics.median(us), min(us), max(us)))
+    # b) the pass
+    torch.manual_seed(0)
+    model = me.ecamp(compute_dtype=dtype).to(dev)
+    model.train()
+    two = [dict({k: v.to(dev) for k, v in b.items()}, mlm_rows=n) for b, n in zip(host, hints)]   # resident in HBM, the row count known on the host
+    loader = [two[i % 2] for i in range(nb)]
+    modes = [("score all (the default: the pass of part 2)", dict(eval_score="all")),
+             ("score masked, head on every row (compact=False)", dict(eval_score="masked", eval_compact=False)),
+             ("score masked, head on the gathered rows", dict(eval_score="masked", eval_compact=True))]
+    ns = [argparse.Namespace(mask_ratio=0.75, prefetch=False, **kw) for _, kw in modes]
+    import contextlib
+    import io
+    times, stats = [[] for _ in modes], [None] * len(modes)
+    for r in range(rounds + 1):
+        for k, a in enumerate(ns):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            with contextlib.redirect_stdout(io.StringIO()):
+                stats[k] = evaluate(model, loader, dev, 0, args=a)      # ends in its own read-back
+            if r >= 1:
+                times[k].append((time.perf_counter() - t0) / nb)
+    print("   b) evaluate(): %d batches resident in HBM, %d rounds of the three modes in turn after one untimed (host clock, each pass ends in its read-back)" % (nb, rounds))
+    print("   %-58s %10s %10s %10s %10s" % ("", "median ms", "min ms", "max ms", "pairs/s"))
+    for (name, _), ts in zip(modes, times):
+        med = statistics.median(ts)
+        print("   %-58s %10.3f %10.3f %10.3f %10.0f" % (name, 1e3 * med, 1e3 * min(ts), 1e3 * max(ts), B / med))
+    for (name, _), st in zip(modes, stats):
+        print("   %s -> %s" % (name.split(" (")[0], st))
+    base, comp = statistics.median(times[1]), statistics.median(times[2])
+    print("   -> compacting the head takes %.3f ms off the %.3f ms masked pass per batch (%.3fx)" % (1e3 * (base - comp), 1e3 * base, comp / base))
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--batches", type=int, default=12)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16"])
+    ap.add_argument("--leg", default="all", choices=["all", "pass", "compact"], help="pass: parts 1 and 2; compact: part 3 alone")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/eval_bench.py measures on an MI355X; there is nothing to time without one")
@@ -125,6 +197,10 @@ if __name__ == "__main__":
     _lib.set_half(dt)
     d = torch.device("cuda:0")
     print("device:", torch.cuda.get_device_name(0))
-    bench_kernel(d, dt, a.iters)
-    torch.cuda.empty_cache()
-    bench_pass(d, dt, a.batches)
+    if a.leg in ("all", "pass"):
+        bench_kernel(d, dt, a.iters)
+        torch.cuda.empty_cache()
+        bench_pass(d, dt, a.batches)
+        torch.cuda.empty_cache()
+    if a.leg in ("all", "compact"):
+        bench_compact(d, dt, a.iters, a.batches)
