@@ -14,6 +14,9 @@ Reference restated per stage (paths relative to ECAMP/Pre-training/):
   FusionFn      context_fusion.py:21-72                                                  K16-K19
   BertLayerFn   HF BertLayer (bert_modeling.py:131)                                      K16,K17,K19
   MlmHeadFn     bert_modeling.py:209-217                                                 K20,K21
+Linear probe (paths relative to ECAMP/Fine-tuning/Classification/; module/classifier.py):
+  ClsHeadFn     timm VisionTransformer.head, call site train.py:441
+  ClsLossFn     train.py:200-202,423-425
 """
 import math
 
@@ -814,3 +817,38 @@ class MlmHeadFn(torch.autograd.Function):
         A.ready(pr.decoder.weight, pr.bias, ln.weight, ln.bias, td.weight, td.bias)
         ctx.s = None
         return (dh,) + _none(4)
+
+
+# =============================================================================================
+# Linear probe (ECAMP/Fine-tuning/Classification; module/classifier.py): the head and its loss behind the frozen encoder.
+class ClsHeadFn(torch.autograd.Function):
+    """logits = feat . weight^T + bias (timm's `self.head(x)`, call site train.py:441), f32.  The features come from the frozen encoder
+    and get no gradient; backward is one `cls_head_wgrad` whose two results autograd adds into the head's `.grad`."""
+
+    @staticmethod
+    def forward(ctx, feat, weight, bias):
+        ctx.feat = feat
+        return ops.cls_head_fwd(feat, weight.data, bias.data)
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        dw, db = ops.cls_head_wgrad(dlogits.contiguous(), ctx.feat)
+        ctx.feat = None
+        return None, dw, db
+
+
+class ClsLossFn(torch.autograd.Function):
+    """BCEWithLogitsLoss (kind 0) / CrossEntropyLoss (kind 1) of train.py:200-202,423-425 -> (loss scalar, counts int64[2], bad int32[1]).
+    The forward kernel leaves the gradient of the mean; backward scales it by the upstream scalar."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, kind):
+        loss, dlogits, counts, bad = ops.cls_loss(logits, targets, kind)
+        ctx.dlogits = dlogits
+        ctx.mark_non_differentiable(counts, bad)
+        return loss.view(()), counts, bad
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        d, ctx.dlogits = ctx.dlogits, None
+        return d * g, None, None

@@ -628,6 +628,75 @@ def compact_rows(x, labels, weights, ids=None, mask_id=3, vocab=None, cap=None):
     return x_c, labels_c, weights_c, rows, count
 
 
+# --------------------------------------------------------------------------------------------- linear probe (csrc/classify.hip)
+def pool_norm(x, t0, t1, gamma=None, beta=None, eps=1e-6):
+    """x [B, T, D] (16-bit or f32) -> (pooled, feat), both f32 [B, D]: the mean over tokens t0 <= t < t1 and its LayerNorm (gamma / beta
+    f32, both None = identity affine), in one pass with f32 means (ecamp_pool_norm)."""
+    _chk(x, gamma, beta)
+    B, T, D = x.shape
+    assert x.is_contiguous() and (gamma is None) == (beta is None)
+    assert gamma is None or (gamma.dtype == torch.float32 and beta.dtype == torch.float32 and gamma.numel() == D and beta.numel() == D)
+    pooled = torch.empty((B, D), device=x.device, dtype=torch.float32)
+    feat = torch.empty((B, D), device=x.device, dtype=torch.float32)
+    dt = code(x.dtype)
+    ws = torch.empty((max(16, int(_lib.load().ecamp_pool_norm_workspace_bytes(B, T, D, int(t0), int(t1), dt))),), device=x.device, dtype=torch.uint8)
+    call("ecamp_pool_norm", ptr(x), ptr(gamma), ptr(beta), ptr(pooled), ptr(feat), B, T, D, int(t0), int(t1), float(eps), ptr(ws), dt, stream())
+    return pooled, feat
+
+
+def cls_head_fwd(feat, w, bias):
+    """logits f32 [B, C] = feat [B, D] . w [C, D]^T + bias [C], all f32, C <= 64."""
+    _chk(feat, w, bias)
+    B, D = feat.shape
+    C = w.shape[0]
+    assert feat.dtype == w.dtype == bias.dtype == torch.float32 and feat.is_contiguous() and w.is_contiguous() and bias.is_contiguous()
+    assert w.shape == (C, D) and bias.numel() == C
+    logits = torch.empty((B, C), device=feat.device, dtype=torch.float32)
+    call("ecamp_cls_head_fwd", ptr(feat), ptr(w), ptr(bias), ptr(logits), B, C, D, stream())
+    return logits
+
+
+def cls_loss(logits, targets, kind, check=False):
+    """kind 0: BCE with logits against f32 targets [B, C] (mean over B*C); kind 1: cross entropy against int64 labels [B] (mean over B)
+    -> (loss f32[1], dlogits f32 [B, C] = gradient of that mean, counts int64[2] = [rows seen, rows predicted right], bad int32[1] = 1 if
+    a kind-1 label lies outside [0, C)).  `bad` stays on the device for the caller to read where it synchronises anyway
+    (`cls_check_labels`); check=True reads it here -- a synchronisation -- and raises."""
+    _chk(logits, targets)
+    B, C = logits.shape
+    assert logits.dtype == torch.float32 and logits.is_contiguous() and targets.is_contiguous()
+    if kind == 0:
+        assert targets.dtype == torch.float32 and tuple(targets.shape) == (B, C), "kind 0: f32 targets [B, C]"
+    else:
+        assert targets.dtype == torch.int64 and targets.numel() == B, "kind 1: int64 labels [B]"
+    dev = logits.device
+    loss = torch.empty((1,), device=dev, dtype=torch.float32)
+    dlogits = torch.empty((B, C), device=dev, dtype=torch.float32)
+    counts = torch.empty((2,), device=dev, dtype=torch.int64)
+    bad = torch.empty((1,), device=dev, dtype=torch.int32)
+    call("ecamp_cls_loss", ptr(logits), ptr(targets), int(kind), ptr(loss), ptr(dlogits), ptr(counts), ptr(bad), B, C, stream())
+    if check:
+        cls_check_labels(bad, C)
+    return loss, dlogits, counts, bad
+
+
+def cls_check_labels(bad, C):
+    """Raise if the flag of a `cls_loss` call says that a label lay outside [0, C).  Reads the device: call it where the loss is read."""
+    if int(bad.item()) != 0:
+        raise _lib.EcampHipError("cls_loss: a class label lies outside [0, %d)" % C)
+
+
+def cls_head_wgrad(dlogits, feat):
+    """-> (dW f32 [C, D] = dlogits^T . feat, db f32 [C] = column sums of dlogits); fixed summation order over B."""
+    _chk(dlogits, feat)
+    B, C = dlogits.shape
+    D = feat.shape[1]
+    assert dlogits.dtype == feat.dtype == torch.float32 and dlogits.is_contiguous() and feat.is_contiguous() and feat.shape[0] == B
+    dw = torch.empty((C, D), device=feat.device, dtype=torch.float32)
+    db = torch.empty((C,), device=feat.device, dtype=torch.float32)
+    call("ecamp_cls_head_wgrad", ptr(dlogits), ptr(feat), ptr(dw), ptr(db), B, C, D, stream())
+    return dw, db
+
+
 # --------------------------------------------------------------------------------------------- optimizer side
 def sumsq(x, out):
     call("ecamp_sumsq", ptr(x), x.numel(), ptr(out), stream())

@@ -1,0 +1,165 @@
+"""Linear-probe classification on a frozen pre-trained encoder -- drop-in for `python train.py --mode LinearProbe` of
+ECAMP/Fine-tuning/Classification (run_lp.sh), on one MI355X:
+
+    python -m ecamp_amd.main_linprobe --name ecamp --stage train --model vit_base_patch16 --task ChestX-ray14 --num_classes 14 \
+        --pretrained_path <pre-training checkpoint> --dataset_path <images> --list_dir <directory of the list files> \
+        --output_dir output/ChestX-ray14/1/ --data_volume 1 --num_steps 3000 --eval_batch_size 1024 --img_size 224 \
+        --learning_rate 3e-2 --warmup_steps 50 --train_batch_size 96 --mode LinearProbe
+    python -m ecamp_amd.main_linprobe --name ecamp --stage test ... (scores <output_dir>/<name>_best{auc,acc}_checkpoint.bin)
+
+The reference's flag names are kept.  Added: --list_dir (the reference hard-codes ./datasets/<task>), --compute_dtype {bf16,fp16,fp32}
+(--fp16 is --compute_dtype fp16; --fp16_opt_level is accepted and ignored), --pool {avg,cls}, --f32_residual, --synthetic,
+--synthetic_len, --num_workers, --print_freq.  `--stage train` trains, then tests the best checkpoint, as the reference does.
+
+NOT implemented here, and refused with a message: `--mode Finetune` (and with it stochastic depth), data-parallel probing
+(`--local_rank` other than -1); segmentation and detection fine-tuning have no counterpart in this project.
+"""
+import argparse
+import os
+import random
+
+import numpy as np
+import torch
+
+TASKS = ["ChestX-ray14", "CheXpert", "RSNA", "SIIM", "COVIDx", "Aptos", "SpineXR", "ODIR5K", "MURED"]
+SINGLE_LABEL_TASKS = ("COVIDx", "Aptos")   # train.py:118-121: everything else is multilabel
+
+
+def get_args_parser():
+    p = argparse.ArgumentParser("ECAMP linear probe", add_help=True)
+    p.add_argument("--model", choices=["vit_tiny_patch16", "vit_base_patch16", "vit_large_patch16"], default="vit_large_patch16", type=str)
+    p.add_argument("--name", required=True, help="name of this run (prefix of the checkpoint files)")
+    p.add_argument("--stage", type=str, default="train", choices=["train", "test"])
+    p.add_argument("--task", choices=TASKS, default="ChestX-ray14")
+    p.add_argument("--num_classes", default=14, type=int)
+    p.add_argument("--pretrained_path", type=str, default="", help="pre-training checkpoint ({'model': ...}) whose encoder is probed (--stage train)")
+    p.add_argument("--output_dir", default="output", type=str)
+    p.add_argument("--img_size", default=384, type=int)
+    p.add_argument("--train_batch_size", default=512, type=int)
+    p.add_argument("--eval_batch_size", default=64, type=int)
+    p.add_argument("--eval_every", default=100, type=int, help="accepted as in the reference, which does not use it either: validation runs after every pass")
+    p.add_argument("--learning_rate", default=3e-2, type=float)
+    p.add_argument("--weight_decay", default=0, type=float)
+    p.add_argument("--num_steps", default=10000, type=int)
+    p.add_argument("--data_volume", type=str, default="100", help="1, 10 or 100: train_list_1.txt, train_list_10.txt or train_list.txt")
+    p.add_argument("--gpu", type=str, default="", help="accepted and ignored (the reference does not use it either)")
+    p.add_argument("--decay_type", choices=["cosine", "linear"], default="cosine")
+    p.add_argument("--warmup_steps", default=500, type=int)
+    p.add_argument("--max_grad_norm", default=1.0, type=float)
+    p.add_argument("--local_rank", type=int, default=-1)
+    p.add_argument("--seed", type=int, default=42)
+    p.add_argument("--gradient_accumulation_steps", type=int, default=1)
+    p.add_argument("--fp16", action="store_true", help="the same as --compute_dtype fp16")
+    p.add_argument("--fp16_opt_level", type=str, default="O2", help="accepted and ignored (apex)")
+    p.add_argument("--loss_scale", type=float, default=0, help="accepted and ignored: the head and its gradient are f32")
+    p.add_argument("--dataset_path", type=str, default="")
+    p.add_argument("--ratio", type=float, default=1)
+    p.add_argument("--mode", type=str, default="Finetune", help="LinearProbe; Finetune (the reference's default) is not implemented here")
+    # additions
+    p.add_argument("--list_dir", type=str, default="", help="directory of train_list*.txt / val_list.txt / test_list.txt (default ./datasets/<task>)")
+    p.add_argument("--compute_dtype", choices=["bf16", "fp16", "fp32"], default=None, help="format of the frozen encoder (default bf16)")
+    p.add_argument("--f32_residual", action="store_true", help="keep the encoder's residual stream in f32 (16-bit formats)")
+    p.add_argument("--pool", choices=["avg", "cls"], default="avg", help="avg: mean of the patch tokens + fc_norm (the reference's global_pool=True)")
+    p.add_argument("--synthetic", action="store_true", help="random images whose label is a function of the image, instead of a dataset")
+    p.add_argument("--synthetic_len", default=64, type=int, help="samples of the synthetic training set (validation and test: half)")
+    p.add_argument("--num_workers", default=8, type=int)
+    p.add_argument("--print_freq", default=50, type=int, help="steps between two reads of the training loss")
+    return p
+
+
+def check_args(args):
+    """Refuse what is not implemented before any device or dataset is touched."""
+    if args.mode != "LinearProbe":
+        raise SystemExit("--mode %s is not implemented here: this driver trains the linear probe only (--mode LinearProbe); fine-tuning the "
+                         "encoder needs stochastic depth, SGD and clipping over the parameter arena and an unmasked encoder backward" % args.mode)
+    if args.local_rank != -1:
+        raise SystemExit("--local_rank %d: data-parallel probing is not implemented here; run on one device (--local_rank -1)" % args.local_rank)
+    if args.gradient_accumulation_steps != 1:
+        raise SystemExit("--gradient_accumulation_steps other than 1 is not implemented here")
+    if not 1 <= args.num_classes <= 64:
+        raise SystemExit("--num_classes must lie in [1, 64]")
+    if args.fp16 and args.compute_dtype not in (None, "fp16"):
+        raise SystemExit("--fp16 contradicts --compute_dtype %s" % args.compute_dtype)
+    args.compute_dtype = "fp16" if args.fp16 else (args.compute_dtype or "bf16")
+    args.is_multilabel = args.task not in SINGLE_LABEL_TASKS
+    if args.stage == "train" and not (args.pretrained_path or args.synthetic):
+        raise SystemExit("--stage train needs --pretrained_path <pre-training checkpoint> (or --synthetic, which probes a random encoder)")
+    if not args.synthetic and not args.dataset_path:
+        raise SystemExit("--dataset_path is required (or --synthetic)")
+    if not args.list_dir:
+        args.list_dir = os.path.join("datasets", args.task)
+    return args
+
+
+def build_model(args):
+    from .module.classifier import build_classifier
+    dtype = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}[args.compute_dtype]
+    return build_classifier(args.model, args.num_classes, args.is_multilabel, img_size=args.img_size, pool=args.pool, compute_dtype=dtype,
+                            f32_residual=args.f32_residual)
+
+
+def build_loader(args, split):
+    from torch.utils.data import DataLoader
+
+    from .module import finetune_datasets as fd
+    train = split == "train"
+    if args.synthetic:
+        n = args.synthetic_len if train else max(1, args.synthetic_len // 2)
+        ds = fd.SyntheticClassificationDataset(n, args.img_size, args.num_classes, args.is_multilabel, seed=args.seed + {"train": 0, "val": 1, "test": 2}[split])
+    else:
+        tf = fd.train_transform(args.img_size) if train else fd.eval_transform(args.img_size, args.ratio)
+        ds = fd.ListDataset(args.dataset_path, args.list_dir, split, data_volume=args.data_volume, transform=tf)
+    print("%s set: %d samples" % (split, len(ds)))
+    return DataLoader(ds, shuffle=train, batch_size=args.train_batch_size if train else args.eval_batch_size, num_workers=args.num_workers,
+                      pin_memory=True)
+
+
+def main(args):
+    args = check_args(args)
+    if not torch.cuda.is_available():
+        raise SystemExit("an MI355X is required: the encoder and the head are HIP kernels, there is no CPU path")
+    from . import engine_linprobe as engine
+    device = torch.device("cuda")
+    os.makedirs(args.output_dir, exist_ok=True)
+    log_path = os.path.join(args.output_dir, "log.txt")
+
+    def log(msg):
+        print(msg, flush=True)
+        with open(log_path, mode="a", encoding="utf-8") as f:
+            f.write(str(msg) + "\n")
+
+    random.seed(args.seed)
+    np.random.seed(args.seed)
+    torch.manual_seed(args.seed)
+    if args.synthetic:
+        log("WARNING: --synthetic: probing on RANDOM images (no dataset is read); the numbers are meaningless")
+    if args.stage == "train":
+        writer = None
+        try:
+            from torch.utils.tensorboard import SummaryWriter
+            writer = SummaryWriter(log_dir=os.path.join(args.output_dir, "logs"))
+        except Exception:   # tensorboard is optional
+            print("tensorboard not available: scalars go to log.txt only")
+        model = build_model(args)
+        if args.pretrained_path:
+            loaded = model.load_pretrained(args.pretrained_path)
+            log("loaded %d tensors from %s" % (len(loaded), args.pretrained_path))
+        model.to(device)
+        log("Training parameters %s" % args)
+        log("Total Parameter: \t%2.4fM" % (sum(p.numel() for p in engine.head_parameters(model)) / 1e6))
+        engine.train(model, build_loader(args, "train"), build_loader(args, "val"), args, log=log, writer=writer)
+        if writer is not None:
+            writer.close()
+        del model
+    # test the best checkpoint (train.py:616-618: also after training)
+    path = engine.checkpoint_path(args, args.is_multilabel)
+    if not os.path.exists(path):
+        raise SystemExit("%s not found: --stage test scores the best checkpoint of a --stage train run with the same --name and --output_dir" % path)
+    model = build_model(args)
+    model.load_pretrained(path)
+    model.to(device)
+    return engine.test(model, build_loader(args, "test"), args, log=log)
+
+
+if __name__ == "__main__":
+    main(get_args_parser().parse_args())

@@ -1,0 +1,175 @@
+"""Linear-probe classifier on the frozen pre-trained image encoder -- the `--mode LinearProbe` share of
+ECAMP/Fine-tuning/Classification (models_vit.py:61-97, train.py:115-166), MI355X-native.
+
+`ECAMPClassifier` wraps an `ECAMP` instance and runs ITS encoder stages (StemFn, VitBlockFn, NormFn over the model's parameter arena)
+forward only, with every patch kept; what it adds sits behind the last block: token mean + `fc_norm` in one kernel
+(`ecamp_pool_norm`), the head (`ecamp_cls_head_fwd` / `ecamp_cls_head_wgrad`) and its loss (`ecamp_cls_loss`).  `fc_norm` and `head` are
+plain f32 parameters of this module, outside the wrapped model's arena and state dict.  Fine-tuning the encoder is not implemented.
+"""
+import os
+
+import torch
+import torch.nn as nn
+
+ENCODER_PREFIXES = ("cls_token", "pos_embed", "patch_embed.proj.", "blocks.", "norm.")
+
+
+def _is_encoder_key(k):
+    return k in ("cls_token", "pos_embed") or k.startswith(ENCODER_PREFIXES[2:])
+
+
+class ECAMPClassifier(nn.Module):
+    def __init__(self, encoder, num_classes, multilabel=True, pool="avg"):
+        super().__init__()
+        if pool not in ("avg", "cls"):
+            raise ValueError("pool must be 'avg' (the reference's global_pool=True) or 'cls', got %r" % (pool,))
+        if not 1 <= int(num_classes) <= 64:
+            raise ValueError("num_classes must lie in [1, 64] (the head kernels' range), got %r" % (num_classes,))
+        self.encoder = encoder
+        self.num_classes, self.multilabel, self.pool = int(num_classes), bool(multilabel), pool
+        D = encoder.embed_dim
+        self.fc_norm = nn.LayerNorm(D, eps=1e-6)          # models_vit.py:69-71 (identity initialisation)
+        self.head = nn.Linear(D, self.num_classes)
+        nn.init.trunc_normal_(self.head.weight, std=2e-5)   # train.py:148
+        nn.init.zeros_(self.head.bias)
+        self.last_counts = None    # int64[2] on the device after `loss`: [rows seen, rows predicted right]
+        self.bad_label = None      # int32[1] on the device: 1 once ANY `loss` call since the last `check_labels` saw a label outside [0, C)
+        self._noise = {}
+
+    # ---------------------------------------------------------------------------------------------
+    def _identity_noise(self, B, dev):
+        """Ascending masking noise: argsort is the identity, every patch is kept in place -- and the model's Philox counter is not
+        advanced, so a pre-training run that probes between epochs draws the masks it would have drawn."""
+        L = self.encoder.num_patches
+        key = (B, L, str(dev))
+        if key not in self._noise:
+            self._noise = {key: (torch.arange(L, dtype=torch.float32, device=dev) / L).expand(B, L).contiguous()}
+        return self._noise[key]
+
+    @torch.no_grad()
+    def forward_features(self, imgs, pool=None):
+        """imgs f32 [B, 3, R, R] -> f32 [B, D] (models_vit.py:78-97).  "avg": the mean of the patch tokens of the last block's output,
+        then `fc_norm` (global_pool=True; the encoder's own `norm` is not applied); "cls": `norm(x)[:, 0]`.  No gradient, and nothing
+        of the encoder depends on `training` (its blocks have no dropout; the reference's stochastic depth is not implemented), so
+        the modes, the Philox counter, the gradient arena and every `.grad` are left as they were."""
+        from .. import hip_ops as ops
+        from ..functions import NormFn, StemFn, VitBlockFn, f32_stream
+        pool = self.pool if pool is None else pool
+        if pool not in ("avg", "cls"):
+            raise ValueError("pool must be 'avg' or 'cls', got %r" % (pool,))
+        m = self.encoder
+        A = m.prepare()
+        imgs = imgs.to(A.device, dtype=torch.float32, non_blocking=True).contiguous()
+        if imgs.dim() != 4 or imgs.shape[1:] != (3, m.img_size, m.img_size):
+            raise ValueError("imgs must be [B,3,%d,%d], got %s" % (m.img_size, m.img_size, tuple(imgs.shape)))
+        B = imgs.shape[0]
+        x, _, _, _, ids_keep = StemFn.apply(imgs, self._identity_noise(B, A.device), m, 0.0, m.cls_token)
+        T = ids_keep.shape[1] + 1
+        for blk in m.blocks:
+            x = VitBlockFn.apply(x, blk, m, B, T, m.num_heads)
+        if pool == "cls":
+            return NormFn.apply(x, m.norm, m).view(B, T, -1)[:, 0].float().contiguous()
+        if m.f32_residual:
+            x = f32_stream(x)
+        return ops.pool_norm(x.view(B, T, -1), 1, T, self.fc_norm.weight.data, self.fc_norm.bias.data, self.fc_norm.eps)[1]
+
+    def forward(self, imgs):
+        """-> logits f32 [B, C], differentiable with respect to `head` only."""
+        from ..functions import ClsHeadFn
+        return ClsHeadFn.apply(self.forward_features(imgs), self.head.weight, self.head.bias)
+
+    def loss(self, logits, y):
+        """BCEWithLogitsLoss against multi-hot y [B, C] (multilabel) or CrossEntropyLoss against class indices y [B] / [B, 1]
+        (train.py:118-121,422-425,442-447) -> scalar.  `last_counts` keeps the kernel's counts; its label flag is folded into
+        `bad_label`, which stays set until `check_labels` has reported it."""
+        from ..functions import ClsLossFn
+        y = y.to(logits.device, non_blocking=True)
+        if self.multilabel:
+            y = y.to(torch.float32).reshape(logits.shape).contiguous()
+        else:
+            y = y.reshape(-1).to(torch.int64).contiguous()
+        loss, self.last_counts, bad = ClsLossFn.apply(logits, y, 0 if self.multilabel else 1)
+        self.bad_label = bad if self.bad_label is None else torch.maximum(self.bad_label, bad)   # (4 bytes on the device, no read-back)
+        return loss
+
+    def check_labels(self):
+        """Raise if any `loss` call since the last check saw a class index outside [0, C) (such a row got a zero loss and gradient), and
+        clear the flag.  Reads the device: call it where the loss is read."""
+        from .. import hip_ops as ops
+        bad, self.bad_label = self.bad_label, None
+        if bad is not None:
+            ops.cls_check_labels(bad, self.num_classes)
+
+    # ---------------------------------------------------------------------------------------------
+    def load_pretrained(self, path_or_state):
+        """Takes (a) a pre-training checkpoint `{"model": state}` of this project or of the reference (train.py:131-142): the encoder's
+        keys are loaded, the rest of the wrapped model keeps its initialisation and goes unused; (b) a flat timm-keyed state dict as
+        the reference's save_model_auc / save_model_acc write it (train.py:84-95): encoder keys plus `fc_norm.*` / `head.*`.  A
+        `head` of another shape is dropped with a message (train.py:136-139).  -> the list of keys that were loaded."""
+        sd = path_or_state
+        if isinstance(sd, (str, os.PathLike)):
+            # (weights_only=False as util/misc.load_model: a pre-training checkpoint also holds its argparse.Namespace and optimizer state)
+            sd = torch.load(sd, map_location="cpu", weights_only=False)
+        if isinstance(sd, dict) and isinstance(sd.get("model"), dict):
+            sd = sd["model"]
+        enc = {k: v for k, v in sd.items() if _is_encoder_key(k)}
+        if not any(k.startswith("blocks.") for k in enc):
+            raise ValueError("load_pretrained: no image-encoder keys (cls_token, pos_embed, patch_embed.proj.*, blocks.*) in the checkpoint")
+        want = {k for k in self.encoder.state_dict() if _is_encoder_key(k)}
+        unknown = sorted(set(enc) - want)
+        if unknown:
+            raise ValueError("load_pretrained: encoder keys this model does not have: %s" % ", ".join(unknown[:8]))
+        missing = sorted(k for k in want - set(enc) if not (k.startswith("norm.") and self.pool == "avg"))   # global_pool deletes `norm`
+        if missing:
+            raise ValueError("load_pretrained: the checkpoint lacks encoder keys: %s" % ", ".join(missing[:8]))
+        self.encoder.load_state_dict(enc, strict=False)
+        loaded = sorted(enc)
+        own = self.state_dict()
+        for k in ("fc_norm.weight", "fc_norm.bias", "head.weight", "head.bias"):
+            if k not in sd:
+                continue
+            if k.startswith("head.") and tuple(sd[k].shape) != tuple(own[k].shape):
+                print("Removing key %s from pretrained checkpoint (shape %s, this head has %s)" % (k, tuple(sd[k].shape), tuple(own[k].shape)))
+                continue
+            with torch.no_grad():
+                own[k].copy_(sd[k].to(torch.float32))
+            loaded.append(k)
+        return loaded
+
+    def reference_state_dict(self):
+        """The flat timm-keyed layout of the reference's classifier (models_vit.VisionTransformer: cls_token, pos_embed,
+        patch_embed.proj.*, blocks.*, head.*, and fc_norm.* with global pooling / norm.* without), f32 on the CPU: what the
+        reference's `--stage test` loads (train.py:98-112)."""
+        out = {}
+        for k, v in self.encoder.state_dict().items():
+            if _is_encoder_key(k) and not (k.startswith("norm.") and self.pool == "avg"):
+                out[k] = v.detach().to("cpu", torch.float32).clone()
+        if self.pool == "avg":
+            for k, v in self.fc_norm.state_dict().items():
+                out["fc_norm." + k] = v.detach().to("cpu", torch.float32).clone()
+        for k, v in self.head.state_dict().items():
+            out["head." + k] = v.detach().to("cpu", torch.float32).clone()
+        return out
+
+
+# the encoders of model_ecamp's factories (ecamp_tiny / ecamp / ecamp_large_448) under the reference's `--model` names (train.py:514;
+# models_vit.py:117-143).  vit_tiny_patch16 keeps this project's 3 heads of 64: the reference's 12 heads of 16 are below the attention
+# kernels' head widths, and no pre-trained tiny checkpoint of the reference exists.
+_ENCODERS = {"vit_tiny_patch16": dict(embed_dim=192, depth=12, num_heads=3), "vit_base_patch16": dict(embed_dim=768, depth=12, num_heads=12),
+             "vit_large_patch16": dict(embed_dim=1024, depth=24, num_heads=16)}
+
+
+def build_classifier(model_name, num_classes, multilabel, img_size=224, pool="avg", **kwargs):
+    """The reference's `--model` name -> an ECAMPClassifier around an ECAMP with that encoder at `img_size` (decoder and report side
+    as the pre-training factories build them, so a pre-training checkpoint's encoder keys fit)."""
+    from functools import partial
+
+    from .bert_config import BertConfig
+    from .model_ecamp import ECAMP
+    if model_name not in _ENCODERS:
+        raise ValueError("--model must be one of %s, got %r" % (", ".join(sorted(_ENCODERS)), model_name))
+    if model_name == "vit_tiny_patch16":
+        kwargs.setdefault("bert_config", BertConfig(num_hidden_layers=2))
+    enc = ECAMP(img_size=img_size, patch_size=16, in_chans=3, decoder_embed_dim=512, decoder_depth=4, decoder_num_heads=16, mlp_ratio=4,
+                norm_layer=partial(nn.LayerNorm, eps=1e-6), **_ENCODERS[model_name], **kwargs)
+    return ECAMPClassifier(enc, num_classes, multilabel=multilabel, pool=pool)

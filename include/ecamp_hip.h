@@ -310,6 +310,37 @@ int ecamp_compact_rows(const void* x, int64_t ldx, const int64_t* labels, const 
                        int64_t M, int32_t cols, int32_t V, int64_t cap, void* x_out, int64_t* labels_out, float* weights_out,
                        int32_t* rows_out, int64_t* count_out, void* ws, int32_t dtype, ecampStream_t stream);
 
+/* ---- linear-probe classification behind the frozen encoder (ECAMP/Fine-tuning/Classification; csrc/classify.hip).  Added at version 5
+ * like ecamp_ce_eval: no existing signature changes.  All arithmetic f32; every sum has one fixed order (no float atomics, no workgroup
+ * waits for another), so two calls on the same input give the same bits; no grid grows with B beyond a cap (the kernels loop).  A null
+ * pointer, C outside [1, 64], D % 4 != 0 or t0 >= t1 is refused before the device is touched. ---- */
+/* x [B, T, D] (the build's 16-bit format, dtype 1, or f32, dtype 0: the f32 residual stream) -> pooled f32 [B, D] = mean over tokens
+ * t0 <= t < t1 (t0 = 1: `x[:, 1:, :].mean(dim=1)`, models_vit.py:92) and feat f32 [B, D] = LayerNorm(pooled) with f32 gamma / beta and
+ * eps (`self.fc_norm(x)`, models_vit.py:93); gamma == beta == NULL: identity affine.  One pass over x with f32 means, where
+ * ecamp_seq_sum + ecamp_layernorm_fwd round the mean to 16 bits in between.  x, pooled, feat and ws 16-byte aligned;
+ * ws: ecamp_pool_norm_workspace_bytes(...) bytes of device memory, scratch (f32 partial sums of the token chunks). */
+int64_t ecamp_pool_norm_workspace_bytes(int64_t B, int32_t T, int32_t D, int32_t t0, int32_t t1, int32_t dtype);
+int ecamp_pool_norm(const void* x, const float* gamma, const float* beta, float* pooled, float* feat, int64_t B, int32_t T, int32_t D,
+                    int32_t t0, int32_t t1, float eps, void* ws, int32_t dtype, ecampStream_t stream);
+/* logits f32 [B, C] = feat [B, D] . W [C, D]^T + bias [C], all f32, 1 <= C <= 64 (`self.head(x)` of timm's VisionTransformer.forward,
+ * call site train.py:441; the datasets have 1..20 classes, shapes the MFMA GEMMs refuse). */
+int ecamp_cls_head_fwd(const float* feat, const float* W, const float* bias, float* logits, int64_t B, int32_t C, int32_t D,
+                       ecampStream_t stream);
+/* kind 0: targets f32 [B, C], BCEWithLogitsLoss, mean over B*C (train.py:200,423) as max(x,0) - x y + log1p(exp(-|x|));
+ * kind 1: targets int64 [B], CrossEntropyLoss, mean over B (train.py:202,425) with the row maximum subtracted.
+ * loss f32 [1]; dlogits f32 [B, C] = gradient of that mean; counts int64 [2] = {rows seen, rows predicted right}: kind 1, the first
+ * maximum is the label (torch.argmax, train.py:222); kind 0, every class on its target's side of 0 (train.py:220).  bad_label int32 [1]
+ * on the device: 1 if a kind-1 label lies outside [0, C) (that row reads no logit and gets a zero loss and gradient), else 0 -- the
+ * caller reads it where it synchronises anyway.  Meant for a head's batch -- B up to a few thousand rows, B * C a few 10^4 values: the
+ * kernel is ONE 1024-thread workgroup (the ordered sum needs no workspace that way) in which a thread walks whole rows, so its time
+ * grows linearly with B / 1024 on a single CU; larger B is accepted (below 2^31) and correct, but not what it is built for. */
+int ecamp_cls_loss(const float* logits, const void* targets, int32_t kind, float* loss, float* dlogits, int64_t* counts,
+                   int32_t* bad_label, int64_t B, int32_t C, ecampStream_t stream);
+/* dW [C, D] = dlogits^T . feat and db [C] = column sums of dlogits, f32, overwriting (the head's share of `loss.backward()`,
+ * train.py:454); the summation order over B is fixed. */
+int ecamp_cls_head_wgrad(const float* dlogits, const float* feat, float* dW, float* db, int64_t B, int32_t C, int32_t D,
+                         ecampStream_t stream);
+
 /* ---- optimizer side ---- */
 /* optimizer.zero_grad() (main_pretrain.py:169) without touching the weight matrices: zero the 64-element blocks of the gradient arena
  * whose flag byte is non-zero (n = arena length, a multiple of 64).  The weight-gradient GEMMs of the next backward pass overwrite
