@@ -4,6 +4,7 @@
 // is fused: the Philox keep-mask is regenerated from (seed, offset, element index) in the backward pass,
 // so no mask tensor is stored; `z = dropout(x) + residual` is written once because backward needs it.
 #include "common.h"
+#include <initializer_list>
 
 // VEC elements per lane access: 4 (16 B of f32, 8 B of bf16) or, for bf16 rows whose length is a multiple of 8, 8 (16 B -- the
 // streaming optimum of this chip; a 768-column row is 96 such chunks = one full wave access and one half-filled one, instead of three
@@ -372,24 +373,83 @@ __global__ __launch_bounds__(LN_BWD_WAVES * 64) void ln_bwd_kernel(const T* __re
     }
 }
 
-template <typename T>
-static int ln_fwd_launch(const void* x, const void* res, void* z, const float* gamma, const float* beta, void* y, float* mean,
-                         float* rstd, long rows, int cols, float eps, float p, uint64_t seed, uint64_t off, hipStream_t st,
-                         void* q8 = nullptr, const float* q8_scale = nullptr, float* q8_amax = nullptr) {
-    dim3 grid(ceil_div(rows, 4)), block(256);
-    auto al16 = [](const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-#define L(IT_, V_) hipLaunchKernelGGL((ln_fwd_kernel<T, IT_, V_>), grid, block, 0, st, (const T*)x, (const T*)res, (T*)z, gamma, beta, (T*)y, mean, rstd, rows, cols, eps, p, seed, off, (unsigned char*)q8, q8_scale, q8_amax)
-    if constexpr (sizeof(T) == 2) {
-        if (cols % 8 == 0 && al16(x) && al16(res) && al16(z) && al16(y)) {   // 16-B lane accesses
-            const int it8 = ceil_div(cols / 8, 64);
-            if (it8 <= 1) L(1, 8); else if (it8 <= 2) L(2, 8); else L(4, 8);
-            return 0;
-        }
+// ---- host side: ln_select says which layout a call gets, ln_fwd_launch / ln_bwd_launch turn that into the one launch of their
+// direction, the five entries check their arguments and call them.
+struct LnLayout {
+    int vec;       // elements per lane access: 4, or 8 (16-bit rows only)
+    int chunks;    // accesses per lane and row (the kernels' IT)
+    int waves;     // rows per workgroup, one wave each
+    bool greg;     // backward: gamma in registers; false: staged into LDS behind the reduction slices
+    size_t lds;    // dynamic LDS bytes
+    int grid_cap;  // most workgroups launched (their waves stride over the rows); 0: one wave per row, no cap
+};
+
+// every row pointer a kernel reads or writes (nullptr: that row is not used) on a 16-byte boundary
+static bool ln_al16(std::initializer_list<const void*> ptrs) {
+    for (const void* q : ptrs)
+        if (reinterpret_cast<uintptr_t>(q) & 15) return false;
+    return true;
+}
+
+// No side effects.  rows16: the rows are 16-bit (bf16_t and the f32-stream form ln_z32<bf16_t>; f32 rows have the 4-wide forms only);
+// al16: ln_al16 of the call's row pointers; opt_bwd: OPT_LN_BWD (development: 1 = the 4-wide backward forms only, 2 = the two-chunk
+// 8-wide backward form wherever it applies).
+static LnLayout ln_select(bool backward, bool rows16, int cols, bool al16, int opt_bwd) {
+    const bool wide = rows16 && cols % 8 == 0 && al16;   // 16-B lane accesses
+    const int it8 = ceil_div(cols / 8, 64), it4 = ceil_div(cols / 4, 64);
+    const int chunks4 = it4 <= 1 ? 1 : it4 <= 4 ? it4 : 8;
+    // forward: a wave per row, four rows per workgroup, no LDS
+    if (!backward) return {wide ? 8 : 4, !wide ? chunks4 : it8 <= 1 ? 1 : it8 <= 2 ? 2 : 4, 4, true, 0, 0};
+    // backward: at most 256 workgroups.  Eight reduction slices (+ gamma for the !greg form, which only serves <= 1024 columns):
+    // 8 * 2048 * 4 = 64 KB at the documented maximum of 2048 columns, inside the default dynamic-LDS limit (the gamma
+    // slice used to be requested for every form, 72 KB at 2048 columns without the opt-in)
+    const size_t slices = (size_t)8 * cols * sizeof(float);
+    if (wide && opt_bwd != 1 && cols <= 1024) {
+        // measured inside the step (profiles/r04_ln_variants.txt): one 16-B chunk per lane (<= 512 columns) beats two 8-B ones
+        // (37.2 vs 38.3 us), the 1024-column row needs the two-chunk 16-B form (27.6 vs 62 us: the 4-wide form spills), and the
+        // 768-column row is better off 4-wide with sixteen waves (32.4 vs 34.5 us)
+        if (it8 <= 1) return {8, 1, 16, true, slices, 256};
+        if (opt_bwd == 2 || cols > 768) return {8, 2, 12, false, (size_t)9 * cols * sizeof(float), 256};
     }
-    const int it = ceil_div(cols / 4, 64);
-    if (it <= 1) L(1, 4); else if (it <= 2) L(2, 4); else if (it <= 3) L(3, 4); else if (it <= 4) L(4, 4); else L(8, 4);
-#undef L
-    return 0;
+    return {4, chunks4, 16, true, slices, 256};
+}
+
+// The launchers name every instantiation: f32 rows have the 4-wide forms only.  (vec, chunks) identifies one: waves and greg are
+// template parameters of the backward kernel, and each (vec, chunks) exists with one pair of them.
+template <typename T> constexpr bool ln_rows16 = sizeof(typename LnRow<T>::io) == 2;
+
+template <typename T>
+static void ln_fwd_launch(const void* x, const void* res, void* z, const float* gamma, const float* beta, void* y, float* mean,
+                          float* rstd, long rows, int cols, float eps, float p, uint64_t seed, uint64_t off, hipStream_t st,
+                          void* q8 = nullptr, const float* q8_scale = nullptr, float* q8_amax = nullptr) {
+    const LnLayout l = ln_select(false, ln_rows16<T>, cols, ln_al16({x, res, z, y}), 0);
+    auto k = ln_fwd_kernel<T, 8, 4>;
+    if (l.vec == 4) {
+        k = l.chunks == 1 ? ln_fwd_kernel<T, 1, 4> : l.chunks == 2 ? ln_fwd_kernel<T, 2, 4> : l.chunks == 3 ? ln_fwd_kernel<T, 3, 4>
+          : l.chunks == 4 ? ln_fwd_kernel<T, 4, 4> : k;
+    } else if constexpr (ln_rows16<T>) {
+        k = l.chunks == 1 ? ln_fwd_kernel<T, 1, 8> : l.chunks == 2 ? ln_fwd_kernel<T, 2, 8> : ln_fwd_kernel<T, 4, 8>;
+    }
+    hipLaunchKernelGGL(k, dim3(ceil_div(rows, l.waves)), dim3(l.waves * 64), l.lds, st, (const T*)x, (const T*)res, (T*)z, gamma, beta, (T*)y,
+                       mean, rstd, rows, cols, eps, p, seed, off, (unsigned char*)q8, q8_scale, q8_amax);
+}
+
+template <typename T>
+static void ln_bwd_launch(const void* dy, const void* z, const float* mean, const float* rstd, const float* gamma, const void* dres,
+                          void* dz, void* dxdrop, float* dgamma, float* dbeta, long rows, int cols, float p, uint64_t seed,
+                          uint64_t off, int opt_bwd, hipStream_t st) {
+    const LnLayout l = ln_select(true, ln_rows16<T>, cols, ln_al16({dy, z, dres, dz, dxdrop}), opt_bwd);
+    auto k = ln_bwd_kernel<T, 8, 4, 16, true>;
+    if (l.vec == 4) {
+        k = l.chunks == 1 ? ln_bwd_kernel<T, 1, 4, 16, true> : l.chunks == 2 ? ln_bwd_kernel<T, 2, 4, 16, true>
+          : l.chunks == 3 ? ln_bwd_kernel<T, 3, 4, 16, true> : l.chunks == 4 ? ln_bwd_kernel<T, 4, 4, 16, true> : k;
+    } else if constexpr (ln_rows16<T>) {
+        k = l.chunks == 1 ? ln_bwd_kernel<T, 1, 8, 16, true> : ln_bwd_kernel<T, 2, 8, 12, false>;
+    }
+    int nb = ceil_div(rows, l.waves);
+    if (nb > l.grid_cap) nb = l.grid_cap;
+    hipLaunchKernelGGL(k, dim3(nb), dim3(l.waves * 64), l.lds, st, (const T*)dy, (const T*)z, mean, rstd, gamma, (const T*)dres, (T*)dz,
+                       (T*)dxdrop, dgamma, dbeta, rows, cols, p, seed, off);
 }
 
 extern "C" int ecamp_layernorm_fwd(const void* x, const void* residual, void* z_out, const float* gamma, const float* beta,
@@ -402,39 +462,6 @@ extern "C" int ecamp_layernorm_fwd(const void* x, const void* residual, void* z_
     else if (dtype == ECAMP_BF16) ln_fwd_launch<bf16_t>(x, residual, z_out, gamma, beta, y, mean, rstd, rows, cols, eps, drop_p, seed, offset, stream);
     else return ecamp_set_error(-1, "layernorm_fwd: bad dtype %d", dtype);
     ECAMP_LAUNCH_CHECK();
-    return 0;
-}
-
-template <typename T>
-static int ln_bwd_launch(const void* dy, const void* z, const float* mean, const float* rstd, const float* gamma,
-                         const void* dres, void* dz, void* dxdrop, float* dgamma, float* dbeta, long rows, int cols, float p,
-                         uint64_t seed, uint64_t off, hipStream_t st) {
-    // eight reduction slices (+ gamma for the !GREG form, which only serves <= 1024 columns): 8 * 2048 * 4 = 64 KB at the documented
-    // maximum of 2048 columns, inside the default dynamic-LDS limit (the gamma slice used to be requested for every form,
-    // 72 KB at 2048 columns without the opt-in)
-    size_t shm = (size_t)8 * cols * sizeof(float);
-    const int variant = ecamp_opt(OPT_LN_BWD);   // development: 1 = 4-wide forms only
-    auto al16 = [](const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-#define L(IT_, V_, W_, G_)                                                                                               \
-    do {                                                                                                                 \
-        int nb = ceil_div(rows, W_);                                                                                     \
-        if (nb > 256) nb = 256;                                                                                          \
-        hipLaunchKernelGGL((ln_bwd_kernel<T, IT_, V_, W_, G_>), dim3(nb), dim3(W_ * 64), shm, st, (const T*)dy, (const T*)z, mean, rstd, gamma, \
-                           (const T*)dres, (T*)dz, (T*)dxdrop, dgamma, dbeta, rows, cols, p, seed, off);      \
-    } while (0)
-    if constexpr (sizeof(T) == 2) {
-        if (variant != 1 && cols % 8 == 0 && cols <= 1024 && al16(dy) && al16(z) && al16(dres) && al16(dz) && al16(dxdrop)) {   // 16-B lane accesses
-            const int it8 = ceil_div(cols / 8, 64);
-            // measured inside the step (profiles/r04_ln_variants.txt): one 16-B chunk per lane (<= 512 columns) beats two 8-B ones
-            // (37.2 vs 38.3 us), the 1024-column row needs the two-chunk 16-B form (27.6 vs 62 us: the 4-wide form spills), and the
-            // 768-column row is better off 4-wide with sixteen waves (32.4 vs 34.5 us)
-            if (it8 <= 1) { L(1, 8, 16, true); return 0; }
-            if (variant == 2 || cols > 768) { shm = (size_t)9 * cols * sizeof(float); L(2, 8, 12, false); return 0; }
-        }
-    }
-    const int it = ceil_div(cols / 4, 64);
-    if (it <= 1) L(1, 4, 16, true); else if (it <= 2) L(2, 4, 16, true); else if (it <= 3) L(3, 4, 16, true); else if (it <= 4) L(4, 4, 16, true); else L(8, 4, 16, true);
-#undef L
     return 0;
 }
 
@@ -460,8 +487,9 @@ extern "C" int ecamp_layernorm_bwd(const void* dy, const void* z, const float* m
     ECAMP_CHECK_ARG(dy && z && mean && rstd && gamma && dz && dgamma && dbeta, "layernorm_bwd: null pointer");
     ECAMP_CHECK_ARG(cols % 4 == 0 && cols <= 2048 && rows > 0, "layernorm_bwd: cols=%d must be a multiple of 4 and <= 2048", cols);
     ECAMP_CHECK_ARG(rows * (int64_t)cols < (1ll << 30), "layernorm_bwd: rows * cols must stay below 2^30 (32-bit element offsets)");
-    if (dtype == ECAMP_F32) ln_bwd_launch<float>(dy, z, mean, rstd, gamma, dres_in, dz, dx_drop, dgamma, dbeta, rows, cols, drop_p, seed, offset, stream);
-    else if (dtype == ECAMP_BF16) ln_bwd_launch<bf16_t>(dy, z, mean, rstd, gamma, dres_in, dz, dx_drop, dgamma, dbeta, rows, cols, drop_p, seed, offset, stream);
+    const int opt = ecamp_opt(OPT_LN_BWD);
+    if (dtype == ECAMP_F32) ln_bwd_launch<float>(dy, z, mean, rstd, gamma, dres_in, dz, dx_drop, dgamma, dbeta, rows, cols, drop_p, seed, offset, opt, stream);
+    else if (dtype == ECAMP_BF16) ln_bwd_launch<bf16_t>(dy, z, mean, rstd, gamma, dres_in, dz, dx_drop, dgamma, dbeta, rows, cols, drop_p, seed, offset, opt, stream);
     else return ecamp_set_error(-1, "layernorm_bwd: bad dtype %d", dtype);
     ECAMP_LAUNCH_CHECK();
     return 0;
@@ -469,57 +497,27 @@ extern "C" int ecamp_layernorm_bwd(const void* dy, const void* z, const float* m
 
 // ---- the f32 residual stream (ECAMP(f32_residual=True)): the LayerNorms that read it (timm Block norm1 / norm2, the encoder's `norm`, the
 // decoder's `decoder_norm`: model_ecamp.py:69,84,233-235,254-256) take f32 rows and leave a 16-bit y; their backward reads the f32 z.
-// The kernels above with T = ln_z32<bf16_t>, in the layouts ln_fwd_launch / ln_bwd_launch pick for 16-bit rows; no residual, dropout or e4m3 copy.
+// The kernels above with T = ln_z32<bf16_t>, in the layouts ln_select picks for 16-bit rows; no residual, dropout or e4m3 copy.
 extern "C" int ecamp_layernorm_fwd_x32(const float* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int64_t rows,
                                        int32_t cols, float eps, int32_t dtype, hipStream_t stream) {
-    typedef ln_z32<bf16_t> T;
     ECAMP_CHECK_ARG(x && gamma && beta && y && mean && rstd, "layernorm_fwd_x32: null pointer");
     ECAMP_CHECK_ARG(cols % 4 == 0 && cols <= 2048 && rows > 0, "layernorm_fwd_x32: cols=%d must be a multiple of 4 and <= 2048", cols);
     ECAMP_CHECK_ARG(dtype == ECAMP_BF16, "layernorm_fwd_x32: the output is 16-bit (dtype 1), got %d", dtype);
     ECAMP_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 7) == 0, "layernorm_fwd_x32: x 16-B, y 8-B aligned");
-    dim3 grid(ceil_div(rows, 4)), block(256);
-#define L(IT_, V_) hipLaunchKernelGGL((ln_fwd_kernel<T, IT_, V_>), grid, block, 0, stream, (const T*)x, (const T*)nullptr, (T*)nullptr, gamma, beta, (T*)y, \
-                                      mean, rstd, (long)rows, cols, eps, 0.f, (uint64_t)0, (uint64_t)0, (unsigned char*)nullptr, (const float*)nullptr, (float*)nullptr)
-    if (cols % 8 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0) {   // 16-B stores of y (two 16-B loads of x per chunk)
-        const int it8 = ceil_div(cols / 8, 64);
-        if (it8 <= 1) L(1, 8); else if (it8 <= 2) L(2, 8); else L(4, 8);
-    } else {
-        const int it = ceil_div(cols / 4, 64);
-        if (it <= 1) L(1, 4); else if (it <= 2) L(2, 4); else if (it <= 3) L(3, 4); else if (it <= 4) L(4, 4); else L(8, 4);
-    }
-#undef L
+    ln_fwd_launch<ln_z32<bf16_t>>(x, nullptr, nullptr, gamma, beta, y, mean, rstd, rows, cols, eps, 0.f, 0, 0, stream);
     ECAMP_LAUNCH_CHECK();
     return 0;
 }
 
 extern "C" int ecamp_layernorm_bwd_z32(const void* dy, const float* z, const float* mean, const float* rstd, const float* gamma, const void* dres_in,
                                        void* dz, float* dgamma, float* dbeta, int64_t rows, int32_t cols, int32_t dtype, hipStream_t stream) {
-    typedef ln_z32<bf16_t> T;
     ECAMP_CHECK_ARG(dy && z && mean && rstd && gamma && dz && dgamma && dbeta, "layernorm_bwd_z32: null pointer");
     ECAMP_CHECK_ARG(cols % 4 == 0 && cols <= 2048 && rows > 0, "layernorm_bwd_z32: cols=%d must be a multiple of 4 and <= 2048", cols);
     ECAMP_CHECK_ARG(rows * (int64_t)cols < (1ll << 30), "layernorm_bwd_z32: rows * cols must stay below 2^30 (32-bit element offsets)");
     ECAMP_CHECK_ARG(dtype == ECAMP_BF16, "layernorm_bwd_z32: dy / dres / dz are 16-bit (dtype 1), got %d", dtype);
     ECAMP_CHECK_ARG((reinterpret_cast<uintptr_t>(z) & 15) == 0, "layernorm_bwd_z32: z 16-B aligned");
-    size_t shm = (size_t)8 * cols * sizeof(float);
-    auto al16 = [](const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-#define L(IT_, V_, W_, G_)                                                                                               \
-    do {                                                                                                                 \
-        int nb = ceil_div(rows, W_);                                                                                     \
-        if (nb > 256) nb = 256;                                                                                          \
-        hipLaunchKernelGGL((ln_bwd_kernel<T, IT_, V_, W_, G_>), dim3(nb), dim3(W_ * 64), shm, stream, (const T*)dy, (const T*)z, mean, rstd, gamma, \
-                           (const T*)dres_in, (T*)dz, (T*)nullptr, dgamma, dbeta, (long)rows, cols, 0.f, (uint64_t)0, (uint64_t)0); \
-    } while (0)
-    bool done = false;
-    if (cols % 8 == 0 && cols <= 1024 && al16(dy) && al16(dres_in) && al16(dz)) {
-        const int it8 = ceil_div(cols / 8, 64);
-        if (it8 <= 1) { L(1, 8, 16, true); done = true; }
-        else if (cols > 768) { shm = (size_t)9 * cols * sizeof(float); L(2, 8, 12, false); done = true; }
-    }
-    if (!done) {
-        const int it = ceil_div(cols / 4, 64);
-        if (it <= 1) L(1, 4, 16, true); else if (it <= 2) L(2, 4, 16, true); else if (it <= 3) L(3, 4, 16, true); else if (it <= 4) L(4, 4, 16, true); else L(8, 4, 16, true);
-    }
-#undef L
+    // 0, not OPT_LN_BWD: this entry has never honoured the development switch
+    ln_bwd_launch<ln_z32<bf16_t>>(dy, z, mean, rstd, gamma, dres_in, dz, nullptr, dgamma, dbeta, rows, cols, 0.f, 0, 0, 0, stream);
     ECAMP_LAUNCH_CHECK();
     return 0;
 }

@@ -123,9 +123,13 @@ def _dense(m, x, weights, bias, shape=None, x8=None, next_w=None, **kw):
     return r + (None,) if next_w is not None else r
 
 
-def _vit_linear(m, x, lin, x8=None, next_w=None, **kw):
-    """Forward of a timm Attention.qkv / proj or Mlp.fc1 / fc2 layer (see _dense)."""
-    return _dense(m, x, lin.weight, lin.bias.data, x8=x8, next_w=next_w, **kw)
+def _vit_linear(m, x, lin, x8=None, next_w=None, residual=None, **kw):
+    """Forward of a timm Attention.qkv / proj or Mlp.fc1 / fc2 layer (see _dense).  A residual that is the f32 residual stream
+    (ECAMP(f32_residual=True)) is added, with the bias, to the f32 accumulator and the sum stored in f32 (autocast's `x + attn(norm1(x))` /
+    `x + mlp(norm2(x))` with an f32 x, model_ecamp.py:233-234,254-255)."""
+    if residual is not None and residual.dtype != x.dtype:
+        return ops.linear_fwd_res32(x, m.arena.w(lin.weight), lin.bias.data, residual)
+    return _dense(m, x, lin.weight, lin.bias.data, x8=x8, next_w=next_w, residual=residual, **kw)
 
 
 def f32_carrier(x32, dtype):
@@ -152,11 +156,25 @@ def _ln_bwd(dy, z, mean, rstd, gamma, ggamma, gbeta, dres=None):
     return ops.layernorm_bwd(dy, z, mean, rstd, gamma, ggamma, gbeta, dres=dres)
 
 
-def _ln_q8(m, x, ln, weights, eps=None, **kw):
-    """LayerNorm whose output feeds the dense layer of `weights`: -> (y, z, mean, rstd, y8 or None)."""
-    site = _f8_site(m, x, weights)
-    r = ops.layernorm_fwd(x, ln.weight.data, ln.bias.data, ln.eps if eps is None else eps, q8_site=site, **kw)
+def _ln_fwd(m, x, ln, feeds=None, **kw):
+    """LayerNorm forward -> (y, z, mean, rstd, y8 or None).  x in f32 beside a 16-bit model is the f32 residual stream: y is 16-bit.
+    `feeds`: the weights of the dense layer that consumes y -- its e4m3 copy y8 is made here when that site is calibrated (fp8 forward).
+    **kw: the fused post-LN form, LN(dropout(x) + residual)."""
+    if x.dtype != m.compute_dtype:
+        return ops.layernorm_fwd_x32(x, ln.weight.data, ln.bias.data, ln.eps, m.compute_dtype) + (None,)
+    site = _f8_site(m, x, feeds) if feeds is not None else None
+    r = ops.layernorm_fwd(x, ln.weight.data, ln.bias.data, ln.eps, q8_site=site, **kw)
     return r if site is not None else r + (None,)
+
+
+def _post_ln_bwd(m, dout, z, mean, rstd, ln, ph, seed, offset):
+    """Backward of a post-LN site LN(dropout(y) + residual) -> (gradient of the residual, gradient of y: through the keep-mask, or the
+    same tensor when there is no dropout)."""
+    G = m.arena.grad
+    if ph > 0:
+        return ops.layernorm_bwd(dout, z, mean, rstd, ln.weight.data, G(ln.weight), G(ln.bias), drop_p=ph, seed=seed, offset=offset, want_drop=True)
+    dz = ops.layernorm_bwd(dout, z, mean, rstd, ln.weight.data, G(ln.weight), G(ln.bias))
+    return dz, dz
 
 
 # =============================================================================================
@@ -201,46 +219,26 @@ class StemFn(torch.autograd.Function):
 class VitBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, blk, m, B, T, heads):
+        """One body for both residual formats.  On the f32 residual stream (ECAMP(f32_residual=True)) x, x1 and x2 are f32: the
+        LayerNorms read them and write 16-bit GEMM inputs, proj / fc2 store f32 (_vit_linear), and the result crosses the autograd edge
+        as a carrier."""
         if m.f32_residual:
-            return VitBlockFn._forward_f32(ctx, f32_stream(x), blk, m, B, T, heads)
+            x = f32_stream(x)
         D = x.shape[1]
         hd = D // heads
-        eps = blk.norm1.eps
-        h, _, mean1, rstd1, h8 = _ln_q8(m, x, blk.norm1, blk.attn.qkv.weight)
+        h, _, mean1, rstd1, h8 = _ln_fwd(m, x, blk.norm1, blk.attn.qkv.weight)
         qkv = _vit_linear(m, h, blk.attn.qkv, x8=h8)
         st = (T * 3 * D, 3 * D, hd)
         flat = qkv.view(-1)
         a, lse = ops.attn_fwd(flat, flat[D:], flat[2 * D:], B, heads, T, T, hd, st, st, st, hd ** -0.5)
         a = a.view(B * T, D)
         x1 = _vit_linear(m, a, blk.attn.proj, residual=x)
-        h2, _, mean2, rstd2, h28 = _ln_q8(m, x1, blk.norm2, blk.mlp.fc1.weight)
+        h2, _, mean2, rstd2, h28 = _ln_fwd(m, x1, blk.norm2, blk.mlp.fc1.weight)
         u, pre, u8 = _vit_linear(m, h2, blk.mlp.fc1, x8=h28, next_w=blk.mlp.fc2.weight, act=m.gelu_act, save_pre=True)   # (act 2: `pre` holds gelu')
         x2 = _vit_linear(m, u, blk.mlp.fc2, x8=u8, residual=x1)
         ctx.s = (x, mean1, rstd1, h, qkv, a, lse, x1, mean2, rstd2, h2, pre, u)
         ctx.cfg = (blk, m, B, T, heads)
-        return x2
-
-    @staticmethod
-    def _forward_f32(ctx, x, blk, m, B, T, heads):
-        """The block on the f32 residual stream (ECAMP(f32_residual=True)): x, x1 and x2 are f32; the LayerNorms read them and write
-        16-bit GEMM inputs, the proj / fc2 epilogues add bias and residual to the f32 accumulator and store f32 (autocast's
-        `x + attn(norm1(x))` / `x + mlp(norm2(x))` with an f32 x, model_ecamp.py:233-234,254-255).  The backward is the common one."""
-        A, cd = m.arena, m.compute_dtype
-        D = x.shape[1]
-        hd = D // heads
-        h, _, mean1, rstd1 = ops.layernorm_fwd_x32(x, blk.norm1.weight.data, blk.norm1.bias.data, blk.norm1.eps, cd)
-        qkv = _vit_linear(m, h, blk.attn.qkv)
-        st = (T * 3 * D, 3 * D, hd)
-        flat = qkv.view(-1)
-        a, lse = ops.attn_fwd(flat, flat[D:], flat[2 * D:], B, heads, T, T, hd, st, st, st, hd ** -0.5)
-        a = a.view(B * T, D)
-        x1 = ops.linear_fwd_res32(a, A.w(blk.attn.proj.weight), blk.attn.proj.bias.data, x)
-        h2, _, mean2, rstd2 = ops.layernorm_fwd_x32(x1, blk.norm2.weight.data, blk.norm2.bias.data, blk.norm2.eps, cd)
-        u, pre = _vit_linear(m, h2, blk.mlp.fc1, act=m.gelu_act, save_pre=True)
-        x2 = ops.linear_fwd_res32(u, A.w(blk.mlp.fc2.weight), blk.mlp.fc2.bias.data, x1)
-        ctx.s = (x, mean1, rstd1, h, qkv, a, lse, x1, mean2, rstd2, h2, pre, u)
-        ctx.cfg = (blk, m, B, T, heads)
-        return f32_carrier(x2, cd)
+        return f32_carrier(x2, m.compute_dtype) if m.f32_residual else x2
 
     @staticmethod
     def backward(ctx, dx2):
@@ -287,9 +285,7 @@ class NormFn(torch.autograd.Function):
     def forward(ctx, x, ln, m):
         if m.f32_residual:
             x = f32_stream(x)
-            y, _, mean, rstd = ops.layernorm_fwd_x32(x, ln.weight.data, ln.bias.data, ln.eps, m.compute_dtype)
-        else:
-            y, _, mean, rstd = ops.layernorm_fwd(x, ln.weight.data, ln.bias.data, ln.eps)
+        y, _, mean, rstd, _ = _ln_fwd(m, x, ln)
         ctx.s = (x, mean, rstd, ln, m)
         return y
 
@@ -339,9 +335,7 @@ def _dec_head_fwd(m, xd):
     ln = m.decoder_norm
     if m.f32_residual:
         xd = f32_stream(xd)
-        h, _, mean, rstd = ops.layernorm_fwd_x32(xd, ln.weight.data, ln.bias.data, ln.eps, m.compute_dtype)
-    else:
-        h, _, mean, rstd = ops.layernorm_fwd(xd, ln.weight.data, ln.bias.data, ln.eps)
+    h, _, mean, rstd, _ = _ln_fwd(m, xd, ln)
     pred = ops.linear_fwd(h, m.arena.w(m.decoder_pred.weight), m.decoder_pred.bias.data)
     return pred, (xd, mean, rstd, h)
 
@@ -523,8 +517,7 @@ def _self_attn_fwd(m, att, out, h, B, S, key_mask, pa, ph, tape, next_w=None):
     s2, o2 = m.next_rng()
     ln = out.LayerNorm
     # (`next_w`: the dense layer this LayerNorm's output feeds -- its e4m3 copy is made here when that site is calibrated)
-    o, z, mean, rstd, o8 = _ln_q8(m, y, ln, next_w, residual=h, drop_p=ph, seed=s2, offset=o2) if next_w is not None else \
-        ops.layernorm_fwd(y, ln.weight.data, ln.bias.data, ln.eps, residual=h, drop_p=ph, seed=s2, offset=o2) + (None,)
+    o, z, mean, rstd, o8 = _ln_fwd(m, y, ln, next_w, residual=h, drop_p=ph, seed=s2, offset=o2)
     tape.append((att, out, h, qkv, a, lse, z, mean, rstd, (s1, o1), (s2, o2), bits))
     return (o, o8) if next_w is not None else o
 
@@ -537,10 +530,7 @@ def _self_attn_bwd(m, rec, dout, B, S, key_mask, pa, ph):
     heads = m.bert_config.num_attention_heads
     hd = H // heads
     ln = out.LayerNorm
-    if ph > 0:
-        dz, dy = ops.layernorm_bwd(dout, z, mean, rstd, ln.weight.data, G(ln.weight), G(ln.bias), drop_p=ph, seed=s2, offset=o2, want_drop=True)
-    else:
-        dz = dy = ops.layernorm_bwd(dout, z, mean, rstd, ln.weight.data, G(ln.weight), G(ln.bias))
+    dz, dy = _post_ln_bwd(m, dout, z, mean, rstd, ln, ph, s2, o2)
     _wgrad(A, dy, a, out.dense.weight, gb=G(out.dense.bias))
     da = ops.linear_dgrad(dy, A.w(out.dense.weight))
     dqkv = torch.empty_like(qkv)
@@ -561,8 +551,7 @@ def _ffn_fwd(m, inter, out, x, ph, tape, x8=None):
     u, pre, u8 = _dense(m, x, inter.dense.weight, inter.dense.bias.data, x8=x8, next_w=out.dense.weight, act=m.gelu_act, save_pre=True)
     y = _dense(m, u, out.dense.weight, out.dense.bias.data, x8=u8)
     s, o = m.next_rng()
-    ln = out.LayerNorm
-    r, z, mean, rstd = ops.layernorm_fwd(y, ln.weight.data, ln.bias.data, ln.eps, residual=x, drop_p=ph, seed=s, offset=o)
+    r, z, mean, rstd, _ = _ln_fwd(m, y, out.LayerNorm, residual=x, drop_p=ph, seed=s, offset=o)
     tape.append((inter, out, x, u, pre, z, mean, rstd, (s, o)))
     return r
 
@@ -572,10 +561,7 @@ def _ffn_bwd(m, rec, dout, ph):
     A = m.arena
     G = A.grad
     ln = out.LayerNorm
-    if ph > 0:
-        dz, dy = ops.layernorm_bwd(dout, z, mean, rstd, ln.weight.data, G(ln.weight), G(ln.bias), drop_p=ph, seed=s, offset=o, want_drop=True)
-    else:
-        dz = dy = ops.layernorm_bwd(dout, z, mean, rstd, ln.weight.data, G(ln.weight), G(ln.bias))
+    dz, dy = _post_ln_bwd(m, dout, z, mean, rstd, ln, ph, s, o)
     _wgrad(A, dy, u, out.dense.weight, gb=G(out.dense.bias))
     dpre = ops.linear_dgrad(dy, A.w(out.dense.weight), gmul=pre, gmul_is_grad=m.gelu_act == 2)
     _wgrad(A, dpre, x, inter.dense.weight, gb=G(inter.dense.bias))
@@ -628,7 +614,7 @@ class FusionFn(torch.autograd.Function):
         ol = fl.out_layer
         y = _dense(m, c2, ol.dense.weight, ol.dense.bias.data)
         s2, o2 = m.next_rng()
-        a2, z, mean, rstd, a28 = _ln_q8(m, y, ol.LayerNorm, fl.intermediate.dense.weight, residual=a1, drop_p=ph, seed=s2, offset=o2)
+        a2, z, mean, rstd, a28 = _ln_fwd(m, y, ol.LayerNorm, fl.intermediate.dense.weight, residual=a1, drop_p=ph, seed=s2, offset=o2)
         out = _ffn_fwd(m, fl.intermediate, fl.output, a2, ph, tape, x8=a28)
         ctx.s = (tape, e, lat, gap, fl, m, B, S, T, key_mask, pa, ph, a1, q, kv, c, lse, c2, z, mean, rstd, (s1, o1), (s2, o2), cbits)
         return out
@@ -644,10 +630,7 @@ class FusionFn(torch.autograd.Function):
         da2 = _ffn_bwd(m, tape[1], dout.contiguous(), ph)
         ol = fl.out_layer
         ln = ol.LayerNorm
-        if ph > 0:
-            dz, dy = ops.layernorm_bwd(da2, z, mean, rstd, ln.weight.data, G(ln.weight), G(ln.bias), drop_p=ph, seed=s2, offset=o2, want_drop=True)
-        else:
-            dz = dy = ops.layernorm_bwd(da2, z, mean, rstd, ln.weight.data, G(ln.weight), G(ln.bias))
+        dz, dy = _post_ln_bwd(m, da2, z, mean, rstd, ln, ph, s2, o2)
         _wgrad(A, dy, c2, ol.dense.weight, gb=G(ol.dense.bias))
         dc2 = ops.linear_dgrad(dy, A.w(ol.dense.weight))                       # [B*S, H] == d c (broadcast add passes through)
         dgp = ops.seq_sum(dc2.view(B, S, H), 0, S, 1.0)                          # [B, H]
@@ -676,14 +659,13 @@ class FusionFn(torch.autograd.Function):
 def _mlm_transform(m, h, pr):
     """The MLM head's transform (dense + GELU + LayerNorm, bert_modeling.py:209) -> (t1, pre, mean, rstd, t, t8).  fp8 forward with
     model.fp8_head: the dense layer runs on the e4m3 kernel and the LayerNorm quantises its own output for the decoder (`t8`, else None)."""
-    ln = pr.transform.LayerNorm
-    if m.fp8_forward and m.fp8_head:
+    fp8 = m.fp8_forward and m.fp8_head
+    if fp8:
         t1, pre = _dense(m, h, pr.transform.dense.weight, pr.transform.dense.bias.data, act=1, save_pre=True)
-        t, _, mean, rstd, t8 = _ln_q8(m, t1, ln, pr.decoder.weight)
-        return t1, pre, mean, rstd, t, t8
-    t1, pre = ops.linear_fwd(h, m.arena.w(pr.transform.dense.weight), pr.transform.dense.bias.data, act=1, save_pre=True)
-    t, _, mean, rstd = ops.layernorm_fwd(t1, ln.weight.data, ln.bias.data, ln.eps)
-    return t1, pre, mean, rstd, t, None
+    else:
+        t1, pre = ops.linear_fwd(h, m.arena.w(pr.transform.dense.weight), pr.transform.dense.bias.data, act=1, save_pre=True)
+    t, _, mean, rstd, t8 = _ln_fwd(m, t1, pr.transform.LayerNorm, pr.decoder.weight if fp8 else None)
+    return t1, pre, mean, rstd, t, t8
 
 
 def _mlm_decoder(m, t, t8, pr):
