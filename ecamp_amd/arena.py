@@ -27,6 +27,55 @@ if not 1.0 <= F8_MARGIN <= 16.0:
     raise ValueError("ECAMP_FP8_MARGIN=%g: the delayed-scaling margin is a factor in [1, 16]" % F8_MARGIN)
 
 
+class FlatTail:
+    """A small flat f32 buffer for the few parameters that live outside a model's arena (the classifier's fc_norm and head): values,
+    gradients and SGD momentum in three buffers of one layout, every tensor padded to 64 elements, so that the grouped optimizer
+    kernels update them in one launch with the arena's clip coefficient.  `p.data` and `p.grad` become views; autograd accumulates into
+    `.grad` in place."""
+
+    def __init__(self, named_params):
+        named_params = list(named_params)
+        dev = named_params[0][1].device
+        if dev.type != "cuda":
+            raise ops._lib.EcampHipError("FlatTail needs the parameters on an MI355X device (model.to('cuda')); no CPU fallback exists")
+        self.device = dev
+        self.names, self.params, self.offsets, self.sizes, self.index = [], [], [], [], {}
+        off = 0
+        for name, p in named_params:
+            self.index[id(p)] = len(self.params)
+            self.names.append(name)
+            self.params.append(p)
+            self.offsets.append(off)
+            self.sizes.append(p.numel())
+            off += (p.numel() + ALIGN - 1) // ALIGN * ALIGN
+        self.total = off
+        self.flat_p = ops.zeros((off,), dev)
+        self.flat_g = ops.zeros((off,), dev)
+        self.flat_buf = ops.zeros((off,), dev)
+        for p, o, n in zip(self.params, self.offsets, self.sizes):
+            self.flat_p[o:o + n].view(p.shape).copy_(p.data)
+            p.data = self.flat_p[o:o + n].view(p.shape)
+            p.grad = self.flat_g[o:o + n].view(p.shape)
+            p._ecamp_tail = self
+
+    def owns(self):
+        """False once something re-materialised the parameters (module.to(), load into fresh tensors): the tail is then rebuilt."""
+        return all(p.data_ptr() == self.flat_p.data_ptr() + 4 * o and p.device == self.device for p, o in zip(self.params, self.offsets))
+
+    def attach_grads(self):
+        """Re-point p.grad at the buffer if someone set it to None (zero_grad(set_to_none=True))."""
+        lost = False
+        for p, o, n in zip(self.params, self.offsets, self.sizes):
+            if p.grad is None or p.grad.data_ptr() != self.flat_g.data_ptr() + 4 * o:
+                p.grad = self.flat_g[o:o + n].view(p.shape)
+                lost = True
+        if lost:
+            self.zero_grad()
+
+    def zero_grad(self):
+        ops.zero_(self.flat_g)
+
+
 class ParamArena:
     def __init__(self, model, compute_dtype):
         # registration order, except that members of a fuse group (e.g. BERT query/key/value weights, which run as one

@@ -104,10 +104,13 @@ def checkpoint_path(args, multilabel):
     return os.path.join(args.output_dir, "%s_%s_checkpoint.bin" % (args.name, "bestauc" if multilabel else "bestacc"))
 
 
-def train(model, train_loader, val_loader, args, log=print, writer=None, keep_losses=False):
+def train(model, train_loader, val_loader, args, log=print, writer=None, keep_losses=False, make_optimizer=None, train_step=None):
     """train.py:364-509 for the head: passes over `train_loader` until `num_steps` optimizer steps are done or the validation result
     has not improved for PATIENCE validations; validation after every pass; the best checkpoint (mean AUROC, ties replace: `<=`;
-    accuracy: `<`) is written in the reference's flat layout.  -> dict(global_step, best, losses (device scalars, keep_losses only))."""
+    accuracy: `<`) is written in the reference's flat layout.  -> dict(global_step, best, losses (device scalars, keep_losses only)).
+    `make_optimizer` / `train_step`: another optimizer and step under the same loop (engine_finetune); the defaults are this module's."""
+    make_optimizer = make_optimizer or globals()["make_optimizer"]
+    train_step = train_step or globals()["train_step"]
     optimizer = make_optimizer(model, args)
     optimizer.zero_grad(set_to_none=True)
     print_freq = max(1, int(getattr(args, "print_freq", 50)))

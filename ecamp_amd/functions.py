@@ -17,6 +17,7 @@ Reference restated per stage (paths relative to ECAMP/Pre-training/):
 Linear probe (paths relative to ECAMP/Fine-tuning/Classification/; module/classifier.py):
   ClsHeadFn     timm VisionTransformer.head, call site train.py:441
   ClsLossFn     train.py:200-202,423-425
+  PoolNormFn    models_vit.py:92-93 (fine-tuning: the pooled features with their backward)
 """
 import math
 
@@ -804,19 +805,46 @@ class MlmHeadFn(torch.autograd.Function):
 # =============================================================================================
 # Linear probe (ECAMP/Fine-tuning/Classification; module/classifier.py): the head and its loss behind the frozen encoder.
 class ClsHeadFn(torch.autograd.Function):
-    """logits = feat . weight^T + bias (timm's `self.head(x)`, call site train.py:441), f32.  The features come from the frozen encoder
-    and get no gradient; backward is one `cls_head_wgrad` whose two results autograd adds into the head's `.grad`."""
+    """logits = feat . weight^T + bias (timm's `self.head(x)`, call site train.py:441), f32.  backward is one `cls_head_wgrad` whose two
+    results autograd adds into the head's `.grad`.  The probe's features come from the frozen encoder and get no gradient; when they do
+    require one (fine-tuning: ECAMPClassifier(train_encoder=True)) a `cls_head_dgrad` launch returns it."""
 
     @staticmethod
     def forward(ctx, feat, weight, bias):
         ctx.feat = feat
+        ctx.w = weight.data if ctx.needs_input_grad[0] else None
         return ops.cls_head_fwd(feat, weight.data, bias.data)
 
     @staticmethod
     def backward(ctx, dlogits):
-        dw, db = ops.cls_head_wgrad(dlogits.contiguous(), ctx.feat)
-        ctx.feat = None
-        return None, dw, db
+        dlogits = dlogits.contiguous()
+        dw, db = ops.cls_head_wgrad(dlogits, ctx.feat)
+        dfeat = ops.cls_head_dgrad(dlogits, ctx.w) if ctx.needs_input_grad[0] else None
+        ctx.feat = ctx.w = None
+        return dfeat, dw, db
+
+
+class PoolNormFn(torch.autograd.Function):
+    """fc_norm(x[:, 1:, :].mean(dim=1)) behind the last block (models_vit.py:92-93) -> feat f32 [B, D]: `pool_norm` forward,
+    `pool_norm_bwd` backward.  x [B*T, D] is the residual stream (a carrier under f32_residual); its gradient goes back in the
+    gradient stream's format -- the model's 16-bit format, or f32 in the f32 parity mode -- as VitBlockFn's does.  dgamma / dbeta are
+    returned for autograd to add into fc_norm's `.grad` (views of the classifier's tail buffer)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, m, B, T, eps):
+        gdt = x.dtype
+        if m.f32_residual:
+            x = f32_stream(x)
+        pooled, feat = ops.pool_norm(x.view(B, T, -1), 1, T, gamma.data, beta.data, eps)
+        ctx.s = (pooled, gamma, T, eps, gdt)
+        return feat
+
+    @staticmethod
+    def backward(ctx, dfeat):
+        pooled, gamma, T, eps, gdt = ctx.s
+        dx, dgamma, dbeta = ops.pool_norm_bwd(dfeat.contiguous(), pooled, gamma.data, 1, T, T, eps, gdt)
+        ctx.s = None
+        return dx.view(-1, dx.shape[-1]), dgamma, dbeta, None, None, None, None
 
 
 class ClsLossFn(torch.autograd.Function):

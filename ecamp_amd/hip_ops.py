@@ -697,6 +697,67 @@ def cls_head_wgrad(dlogits, feat):
     return dw, db
 
 
+# --------------------------------------------------------------------------------------------- fine-tuning (csrc/finetune.hip)
+def cls_head_dgrad(dlogits, w):
+    """-> dfeat f32 [B, D] = dlogits [B, C] . w [C, D]."""
+    _chk(dlogits, w)
+    B, C = dlogits.shape
+    D = w.shape[1]
+    assert dlogits.dtype == w.dtype == torch.float32 and dlogits.is_contiguous() and w.is_contiguous() and w.shape[0] == C
+    dfeat = torch.empty((B, D), device=w.device, dtype=torch.float32)
+    call("ecamp_cls_head_dgrad", ptr(dlogits), ptr(w), ptr(dfeat), B, C, D, stream())
+    return dfeat
+
+
+def pool_norm_bwd(dfeat, pooled, gamma, t0, t1, T, eps, dtype, want_affine=True):
+    """Backward of `pool_norm`: dfeat / pooled f32 [B, D], gamma f32 [D] or None -> (dx [B, T, D] in `dtype`: dpooled / (t1 - t0) on the
+    tokens t0 <= t < t1, zero elsewhere; dgamma, dbeta f32 [D], or None without want_affine)."""
+    _chk(dfeat, pooled, gamma)
+    B, D = pooled.shape
+    assert dfeat.dtype == pooled.dtype == torch.float32 and dfeat.is_contiguous() and pooled.is_contiguous() and dfeat.shape == pooled.shape
+    assert gamma is None or (gamma.dtype == torch.float32 and gamma.numel() == D and gamma.is_contiguous())
+    dev = pooled.device
+    dt = code(dtype)
+    dx = torch.empty((B, T, D), device=dev, dtype=dtype)
+    dgamma = torch.empty((D,), device=dev, dtype=torch.float32) if want_affine else None
+    dbeta = torch.empty((D,), device=dev, dtype=torch.float32) if want_affine else None
+    ws = torch.empty((max(16, int(_lib.load().ecamp_pool_norm_bwd_workspace_bytes(B, int(T), D, int(t0), int(t1), dt))),), device=dev, dtype=torch.uint8)
+    call("ecamp_pool_norm_bwd", ptr(dfeat), ptr(pooled), ptr(gamma), ptr(dgamma), ptr(dbeta), ptr(dx), B, int(T), D, int(t0), int(t1), float(eps),
+         ptr(ws), dt, stream())
+    return dx, dgamma, dbeta
+
+
+SUMSQ_MAX_SLOTS = 2048   # ecamp_sumsq_grouped fills at most this many partials per launch
+
+
+def sumsq_grouped_slots(n):
+    """How many f32 partials one `sumsq_grouped` launch over n elements fills (a function of n alone)."""
+    return int(_lib.load().ecamp_sumsq_grouped_slots(int(n)))
+
+
+def sumsq_grouped(g, block_group, partials):
+    """sum(g^2) over the 64-element blocks of the flat f32 `g` whose `block_group` byte is below 8, one partial per workgroup into
+    `partials[0:slots]` (a slice of a larger buffer is fine) -> slots.  No scalar: `sgd_grouped` adds the partials itself."""
+    _chk(g, block_group, partials)
+    n = g.numel()
+    assert g.dtype == torch.float32 and g.is_contiguous() and block_group.dtype == torch.uint8 and block_group.numel() == n // 64
+    slots = sumsq_grouped_slots(n)
+    assert partials.dtype == torch.float32 and partials.is_contiguous() and (slots == 0 or partials.numel() >= slots)
+    call("ecamp_sumsq_grouped", ptr(g), ptr(block_group), n, ptr(partials), None, stream())
+    return slots
+
+
+def sgd_grouped(p, g, buf, p16, block_group, lrs, wds, momentum, max_norm, partials, npart, grad_scale=1.0, ctl=None, norm_out=None):
+    """clip_grad_norm_(max_norm) + torch.optim.SGD(momentum) over a flat buffer (include/ecamp_hip.h): `partials[0:npart]` are the
+    sums of squares of the (scaled) gradients, `ctl` the optional device f32[4] of `loss_scale_update`, `norm_out` an optional device
+    f32[1] for the global norm."""
+    _chk(p, g, buf, p16, block_group, partials, ctl, norm_out)
+    n = len(lrs)
+    arr = ctypes.c_float * n
+    call("ecamp_sgd_grouped", ptr(p), ptr(g), ptr(buf), ptr(p16), ptr(block_group), p.numel(), n, arr(*lrs), arr(*wds), float(momentum),
+         float(max_norm), ptr(partials), int(npart), float(grad_scale), ptr(ctl), ptr(norm_out), stream())
+
+
 # --------------------------------------------------------------------------------------------- optimizer side
 def sumsq(x, out):
     call("ecamp_sumsq", ptr(x), x.numel(), ptr(out), stream())

@@ -1,0 +1,108 @@
+"""Fine-tuning the pre-trained encoder on a classification task -- drop-in for `python train.py` of
+ECAMP/Fine-tuning/Classification in its default `--mode Finetune` (run_ft.sh), on one MI355X:
+
+    python -m ecamp_amd.main_finetune --name ecamp --stage train --model vit_base_patch16 --task ChestX-ray14 --num_classes 14 \
+        --pretrained_path <pre-training checkpoint> --dataset_path <images> --list_dir <directory of the list files> \
+        --output_dir output/ChestX-ray14/1/ --data_volume 1 --num_steps 3000 --eval_batch_size 512 --img_size 224 \
+        --learning_rate 3e-2 --warmup_steps 50 --train_batch_size 96 --compute_dtype bf16
+    python -m ecamp_amd.main_finetune --name ecamp --stage test ... (scores <output_dir>/<name>_best{auc,acc}_checkpoint.bin)
+
+The flags are main_linprobe's (the reference's names and its additions); `--mode` defaults to Finetune, and `--mode LinearProbe` hands
+over to main_linprobe.  Two deviations from the reference, stated in the first log line of every run: stochastic depth (its
+drop_path_rate=0.1) is not applied, and `pos_embed` is held at the fixed sin-cos table (timm's is a trained parameter).
+
+NOT implemented, and refused with a message before any device work: data-parallel fine-tuning (`--local_rank` other than -1),
+`--gradient_accumulation_steps` other than 1, and `--fp16` (IEEE half with loss scaling): use `--compute_dtype bf16`.
+"""
+import os
+import random
+
+import numpy as np
+import torch
+
+from . import main_linprobe
+from .main_linprobe import build_loader, get_args_parser  # noqa: F401  (one parser: run_ft.sh's command lines parse unchanged)
+
+DEVIATIONS = ("NOTE: stochastic depth (the reference's drop_path_rate=0.1) is NOT applied, and pos_embed is held fixed at the sin-cos table "
+              "(the reference trains it)")
+
+
+def check_args(args):
+    """Refuse what is not implemented before any device or dataset is touched; everything else is main_linprobe's check."""
+    if args.mode != "Finetune":
+        raise SystemExit("--mode %s: this driver fine-tunes the encoder (--mode Finetune) or hands --mode LinearProbe to main_linprobe" % args.mode)
+    if args.local_rank != -1:
+        raise SystemExit("--local_rank %d: data-parallel fine-tuning is not implemented here; run on one device (--local_rank -1)" % args.local_rank)
+    if args.gradient_accumulation_steps != 1:
+        raise SystemExit("--gradient_accumulation_steps %d: gradient accumulation is not implemented here (only 1)" % args.gradient_accumulation_steps)
+    if args.fp16 or args.compute_dtype == "fp16":
+        raise SystemExit("--fp16 --mode Finetune is not implemented here (IEEE half needs loss scaling around the fused SGD step): "
+                         "use --compute_dtype bf16 (or fp32)")
+    args.mode = "LinearProbe"          # the remaining checks are shared
+    try:
+        args = main_linprobe.check_args(args)
+    finally:
+        args.mode = "Finetune"
+    return args
+
+
+def build_model(args):
+    from .module.classifier import build_classifier
+    dtype = {"bf16": torch.bfloat16, "fp32": torch.float32}[args.compute_dtype]
+    return build_classifier(args.model, args.num_classes, args.is_multilabel, img_size=args.img_size, pool=args.pool, train_encoder=True,
+                            compute_dtype=dtype, f32_residual=args.f32_residual)
+
+
+def main(args):
+    if args.mode == "LinearProbe":
+        return main_linprobe.main(args)
+    args = check_args(args)
+    if not torch.cuda.is_available():
+        raise SystemExit("an MI355X is required: the encoder and the head are HIP kernels, there is no CPU path")
+    from . import engine_finetune as engine
+    device = torch.device("cuda")
+    os.makedirs(args.output_dir, exist_ok=True)
+    log_path = os.path.join(args.output_dir, "log.txt")
+
+    def log(msg):
+        print(msg, flush=True)
+        with open(log_path, mode="a", encoding="utf-8") as f:
+            f.write(str(msg) + "\n")
+
+    random.seed(args.seed)
+    np.random.seed(args.seed)
+    torch.manual_seed(args.seed)
+    log(DEVIATIONS)
+    if args.synthetic:
+        log("WARNING: --synthetic: fine-tuning on RANDOM images (no dataset is read); the numbers are meaningless")
+    if args.stage == "train":
+        writer = None
+        try:
+            from torch.utils.tensorboard import SummaryWriter
+            writer = SummaryWriter(log_dir=os.path.join(args.output_dir, "logs"))
+        except Exception:   # tensorboard is optional
+            print("tensorboard not available: scalars go to log.txt only")
+        model = build_model(args)
+        if args.pretrained_path:
+            loaded = model.load_pretrained(args.pretrained_path)
+            log("loaded %d tensors from %s" % (len(loaded), args.pretrained_path))
+        model.to(device)
+        log("Training parameters %s" % args)
+        log("Total Parameter: \t%2.4fM" % (sum(p.numel() for _, p in model.finetune_parameters()) / 1e6))
+        engine.train(model, build_loader(args, "train"), build_loader(args, "val"), args, log=log, writer=writer)
+        if writer is not None:
+            writer.close()
+        del model
+    # test the best checkpoint (train.py:616-618: also after training)
+    path = engine.checkpoint_path(args, args.is_multilabel)
+    if not os.path.exists(path):
+        raise SystemExit("%s not found: --stage test scores the best checkpoint of a --stage train run with the same --name and --output_dir" % path)
+    model = build_model(args)
+    model.load_pretrained(path)
+    model.to(device)
+    model.eval()
+    return engine.test(model, build_loader(args, "test"), args, log=log)
+
+
+if __name__ == "__main__":
+    main(get_args_parser().parse_args())

@@ -4,7 +4,12 @@ ECAMP/Fine-tuning/Classification (models_vit.py:61-97, train.py:115-166), MI355X
 `ECAMPClassifier` wraps an `ECAMP` instance and runs ITS encoder stages (StemFn, VitBlockFn, NormFn over the model's parameter arena)
 forward only, with every patch kept; what it adds sits behind the last block: token mean + `fc_norm` in one kernel
 (`ecamp_pool_norm`), the head (`ecamp_cls_head_fwd` / `ecamp_cls_head_wgrad`) and its loss (`ecamp_cls_loss`).  `fc_norm` and `head` are
-plain f32 parameters of this module, outside the wrapped model's arena and state dict.  Fine-tuning the encoder is not implemented.
+plain f32 parameters of this module, outside the wrapped model's arena and state dict.
+
+`ECAMPClassifier(..., train_encoder=True)` is the `--mode Finetune` share (train.py:144-166): in training mode `forward` runs the same
+stages with their hand-written backwards (StemFn, VitBlockFn, then PoolNormFn or NormFn) so that the loss reaches every encoder
+parameter; `fc_norm` and `head` then live in a small flat buffer of their own (arena.FlatTail) which the fused SGD step updates beside
+the arena.  Stochastic depth (the reference's drop_path_rate=0.1) is not applied, and `pos_embed` stays the fixed sin-cos table.
 """
 import os
 
@@ -19,7 +24,7 @@ def _is_encoder_key(k):
 
 
 class ECAMPClassifier(nn.Module):
-    def __init__(self, encoder, num_classes, multilabel=True, pool="avg"):
+    def __init__(self, encoder, num_classes, multilabel=True, pool="avg", train_encoder=False):
         super().__init__()
         if pool not in ("avg", "cls"):
             raise ValueError("pool must be 'avg' (the reference's global_pool=True) or 'cls', got %r" % (pool,))
@@ -35,6 +40,8 @@ class ECAMPClassifier(nn.Module):
         self.last_counts = None    # int64[2] on the device after `loss`: [rows seen, rows predicted right]
         self.bad_label = None      # int32[1] on the device: 1 once ANY `loss` call since the last `check_labels` saw a label outside [0, C)
         self._noise = {}
+        self.train_encoder = bool(train_encoder)   # False: the linear probe, exactly; True: `forward` is differentiable down to the stem
+        self._tail = None          # arena.FlatTail over fc_norm and head (train_encoder only; built on the device, on first use)
 
     # ---------------------------------------------------------------------------------------------
     def _identity_noise(self, B, dev):
@@ -74,9 +81,58 @@ class ECAMPClassifier(nn.Module):
         return ops.pool_norm(x.view(B, T, -1), 1, T, self.fc_norm.weight.data, self.fc_norm.bias.data, self.fc_norm.eps)[1]
 
     def forward(self, imgs):
-        """-> logits f32 [B, C], differentiable with respect to `head` only."""
+        """-> logits f32 [B, C].  Differentiable with respect to `head` only -- except on a `train_encoder=True` model in training mode
+        with gradients enabled, where the encoder stages run with their backwards (`_forward_finetune`)."""
         from ..functions import ClsHeadFn
+        if self.train_encoder and self.training and torch.is_grad_enabled():
+            return self._forward_finetune(imgs)
         return ClsHeadFn.apply(self.forward_features(imgs), self.head.weight, self.head.bias)
+
+    def tail(self):
+        """The flat buffer of `fc_norm` and `head` (train_encoder=True only; built where the parameters are, rebuilt after `.to()`)."""
+        if not self.train_encoder:
+            raise RuntimeError("ECAMPClassifier.tail(): only a train_encoder=True model keeps fc_norm and head in a flat buffer")
+        if self._tail is None or not self._tail.owns():
+            from ..arena import FlatTail
+            self.encoder.prepare()
+            self._tail = FlatTail([("fc_norm.weight", self.fc_norm.weight), ("fc_norm.bias", self.fc_norm.bias),
+                                   ("head.weight", self.head.weight), ("head.bias", self.head.bias)])
+        else:
+            self._tail.attach_grads()
+        return self._tail
+
+    def _forward_finetune(self, imgs):
+        """The differentiable twin of `forward_features` + head: the same kernels in the same order, every patch kept in place (identity
+        noise, ratio 0: the Philox counter is not advanced), so its logits are the forward-only path's bits."""
+        from ..functions import ClsHeadFn, NormFn, PoolNormFn, StemFn, VitBlockFn
+        m = self.encoder
+        A = m.prepare()
+        self.tail()
+        imgs = imgs.to(A.device, dtype=torch.float32, non_blocking=True).contiguous()
+        if imgs.dim() != 4 or imgs.shape[1:] != (3, m.img_size, m.img_size):
+            raise ValueError("imgs must be [B,3,%d,%d], got %s" % (m.img_size, m.img_size, tuple(imgs.shape)))
+        B = imgs.shape[0]
+        x, _, _, _, ids_keep = StemFn.apply(imgs, self._identity_noise(B, A.device), m, 0.0, m.cls_token)
+        T = ids_keep.shape[1] + 1
+        for blk in m.blocks:
+            x = VitBlockFn.apply(x, blk, m, B, T, m.num_heads)
+        if self.pool == "cls":
+            feat = NormFn.apply(x, m.norm, m).view(B, T, -1)[:, 0].float().contiguous()
+        else:
+            feat = PoolNormFn.apply(x, self.fc_norm.weight, self.fc_norm.bias, m, B, T, self.fc_norm.eps)
+        return ClsHeadFn.apply(feat, self.head.weight, self.head.bias)
+
+    def finetune_parameters(self):
+        """[(name, parameter)] of what `--mode Finetune` trains, named as the reference's flat layout names them: the encoder's cls_token,
+        patch_embed.proj.* and blocks.*, `norm.*` only when it is used (pool="cls"), `fc_norm.*` only when it is (pool="avg"), head.*.
+        `pos_embed` is the fixed sin-cos table (requires_grad=False, outside the arena); decoder and report side are not trained."""
+        out = []
+        for k, p in self.encoder.named_parameters():
+            if k == "cls_token" or k.startswith(("patch_embed.proj.", "blocks.")) or (k.startswith("norm.") and self.pool == "cls"):
+                out.append((k, p))
+        if self.pool == "avg":
+            out += [("fc_norm.weight", self.fc_norm.weight), ("fc_norm.bias", self.fc_norm.bias)]
+        return out + [("head.weight", self.head.weight), ("head.bias", self.head.bias)]
 
     def loss(self, logits, y):
         """BCEWithLogitsLoss against multi-hot y [B, C] (multilabel) or CrossEntropyLoss against class indices y [B] / [B, 1]
@@ -159,7 +215,7 @@ _ENCODERS = {"vit_tiny_patch16": dict(embed_dim=192, depth=12, num_heads=3), "vi
              "vit_large_patch16": dict(embed_dim=1024, depth=24, num_heads=16)}
 
 
-def build_classifier(model_name, num_classes, multilabel, img_size=224, pool="avg", **kwargs):
+def build_classifier(model_name, num_classes, multilabel, img_size=224, pool="avg", train_encoder=False, **kwargs):
     """The reference's `--model` name -> an ECAMPClassifier around an ECAMP with that encoder at `img_size` (decoder and report side
     as the pre-training factories build them, so a pre-training checkpoint's encoder keys fit)."""
     from functools import partial
@@ -172,4 +228,4 @@ def build_classifier(model_name, num_classes, multilabel, img_size=224, pool="av
         kwargs.setdefault("bert_config", BertConfig(num_hidden_layers=2))
     enc = ECAMP(img_size=img_size, patch_size=16, in_chans=3, decoder_embed_dim=512, decoder_depth=4, decoder_num_heads=16, mlp_ratio=4,
                 norm_layer=partial(nn.LayerNorm, eps=1e-6), **_ENCODERS[model_name], **kwargs)
-    return ECAMPClassifier(enc, num_classes, multilabel=multilabel, pool=pool)
+    return ECAMPClassifier(enc, num_classes, multilabel=multilabel, pool=pool, train_encoder=train_encoder)

@@ -215,3 +215,147 @@ class FusedAdamW(torch.optim.Optimizer):
                     self._v[o:o + n].view(p.shape).copy_(st["exp_avg_sq"])
                     self._step, self._step_dev = int(float(st["step"])), None
                 idx += 1
+
+
+class FusedSGD(torch.optim.Optimizer):
+    """torch.optim.SGD(momentum, dampening 0, no Nesterov, weight decay added to the gradient) behind
+    torch.nn.utils.clip_grad_norm_(max_grad_norm) -- train.py:377-384,458 of the reference's Fine-tuning/Classification -- as fused HIP
+    launches over the parameter arena: `ecamp_sumsq_grouped` leaves one partial sum of squares per workgroup, `ecamp_sgd_grouped` adds them
+    in every workgroup, forms the clip coefficient and updates parameters, momentum and the 16-bit shadows.  Parameters outside the arena
+    must sit in ONE arena.FlatTail (ECAMPClassifier's fc_norm and head): a second pair of launches updates them with the same partials,
+    hence the same norm and coefficient.  Nothing is read back: `last_norm` is the global gradient norm as a device scalar.
+    max_grad_norm <= 0: no clipping.  Binding, block table, `zero_grad` / `flush_grads` / `pace` are FusedAdamW's."""
+
+    def __init__(self, params, lr=1e-3, momentum=0.9, weight_decay=0.0, max_grad_norm=0.0):
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=0, weight_decay=weight_decay, nesterov=False))
+        if len(self.param_groups) > 8:
+            raise ValueError("FusedSGD supports at most 8 param groups")
+        if len({g["momentum"] for g in self.param_groups}) != 1:
+            raise ValueError("all groups must share momentum")
+        if any(g.get("dampening", 0) != 0 or g.get("nesterov", False) for g in self.param_groups):
+            raise ValueError("FusedSGD implements dampening 0 without Nesterov momentum only")
+        self.max_grad_norm = float(max_grad_norm)
+        self.grad_scale = 1.0
+        self.last_norm = None       # f32[1] on the device after a step: the global norm of the (un-scaled) gradients before clipping
+        self._arena = self._tail = None
+        self._steps = 0
+        self._inflight = collections.deque()
+
+    pace = FusedAdamW.pace
+
+    @property
+    def arena(self):
+        return self._bind()
+
+    def _bind(self):
+        if self._arena is not None:
+            return self._arena
+        arena = tail = None
+        for g in self.param_groups:
+            for p in g["params"]:
+                a, t = getattr(p, "_ecamp_arena", None), getattr(p, "_ecamp_tail", None)
+                if a is None and t is None:
+                    raise RuntimeError("FusedSGD: parameter is not in an ecamp_amd arena -- call model.prepare() (or run one forward) after "
+                                       "model.to('cuda') and before the first optimizer.step()")
+                if a is not None:
+                    arena = arena or a
+                    if a is not arena:
+                        raise RuntimeError("FusedSGD: parameters from different arenas")
+                else:
+                    tail = tail or t
+                    if t is not tail:
+                        raise RuntimeError("FusedSGD: parameters from different arenas (two tail buffers)")
+        if arena is None:
+            raise RuntimeError("FusedSGD: no parameter of a model's arena among the groups (the tail buffer alone is not supported)")
+        if arena.reducer is not None:
+            raise RuntimeError("FusedSGD: data-parallel fine-tuning is not implemented")
+
+        def table(space):
+            t = torch.full((space.total // 64,), 255, dtype=torch.uint8)
+            for gi, g in enumerate(self.param_groups):
+                for p in g["params"]:
+                    if id(p) not in space.index or getattr(p, "_ecamp_unused", False):
+                        continue
+                    i = space.index[id(p)]
+                    o, n = space.offsets[i], space.sizes[i]
+                    t[o // 64:(o + n + 63) // 64] = gi
+            return t.to(space.device)
+
+        self._table = table(arena)
+        self._buf = ops.zeros((arena.total,), arena.device)
+        self._tail_table = table(tail) if tail is not None else None
+        self._slots = (ops.sumsq_grouped_slots(arena.total), ops.sumsq_grouped_slots(tail.total) if tail is not None else 0)
+        self._partials = ops.zeros((sum(self._slots),), arena.device)
+        self.last_norm = ops.zeros((1,), arena.device)
+        self._arena, self._tail = arena, tail
+        return arena
+
+    @torch.no_grad()
+    def step(self, closure=None, ctl=None):
+        """`ctl` (device f32[4], hip_ops.loss_scale_update): the gradient scale and whether this step happens at all are read on the device."""
+        loss = closure() if closure is not None else None
+        A, T = self._bind(), self._tail
+        A.flush_fresh()
+        lrs = [g["lr"] for g in self.param_groups]
+        wds = [g["weight_decay"] for g in self.param_groups]
+        mom = self.param_groups[0]["momentum"]
+        n0, n1 = self._slots
+        ops.sumsq_grouped(A.flat_g, self._table, self._partials)
+        if T is not None:
+            ops.sumsq_grouped(T.flat_g, self._tail_table, self._partials[n0:])
+        ops.sgd_grouped(A.flat_p, A.flat_g, self._buf, A.flat_p16, self._table, lrs, wds, mom, self.max_grad_norm, self._partials, n0 + n1,
+                        self.grad_scale, ctl, self.last_norm)
+        if T is not None:
+            ops.sgd_grouped(T.flat_p, T.flat_g, T.flat_buf, None, self._tail_table, lrs, wds, mom, self.max_grad_norm, self._partials, n0 + n1,
+                            self.grad_scale, ctl, None)
+        self._steps += 1
+        A.version += 1   # the 16-bit shadows changed
+        self.pace()
+        return loss
+
+    def zero_grad(self, set_to_none=False):
+        """p.grad stay views of the gradient arena / the tail buffer (see FusedAdamW.zero_grad: lazy for the weight matrices)."""
+        self._bind().zero_grad()
+        if self._tail is not None:
+            self._tail.zero_grad()
+
+    def flush_grads(self):
+        self._bind().flush_fresh()
+
+    def _slot(self, p):
+        """-> (momentum buffer, offset, size) of parameter p."""
+        if id(p) in self._arena.index:
+            i = self._arena.index[id(p)]
+            return self._buf, self._arena.offsets[i], self._arena.sizes[i]
+        i = self._tail.index[id(p)]
+        return self._tail.flat_buf, self._tail.offsets[i], self._tail.sizes[i]
+
+    # -- checkpoint format compatible with torch.optim.SGD ------------------------------------------------------
+    def state_dict(self):
+        self._bind()
+        state, packed_groups, idx = {}, [], 0
+        for g in self.param_groups:
+            ids = []
+            for p in g["params"]:
+                if self._steps > 0 and not getattr(p, "_ecamp_unused", False):
+                    buf, o, n = self._slot(p)
+                    state[idx] = {"momentum_buffer": buf[o:o + n].view(p.shape).clone()}
+                ids.append(idx)
+                idx += 1
+            packed_groups.append({**{k: v for k, v in g.items() if k != "params"}, "params": ids})
+        return {"state": state, "param_groups": packed_groups}
+
+    def load_state_dict(self, sd):
+        self._bind()
+        idx = 0
+        for g, sg in zip(self.param_groups, sd["param_groups"]):
+            for k, v in sg.items():
+                if k != "params":
+                    g[k] = v
+            for p in g["params"]:
+                st = sd["state"].get(idx, sd["state"].get(str(idx)))
+                if st is not None and st.get("momentum_buffer") is not None:
+                    buf, o, n = self._slot(p)
+                    buf[o:o + n].view(p.shape).copy_(st["momentum_buffer"])
+                    self._steps = max(self._steps, 1)
+                idx += 1

@@ -366,6 +366,39 @@ int ecamp_adamw_grouped(float* p, const float* g, float* m, float* v, void* p_bf
 int ecamp_loss_scale_update(const float* sumsq, float* state, float* opt_step, float* ctl, float* norm_out, float growth_factor,
                             float backoff_factor, int32_t growth_interval, float beta1, float beta2, ecampStream_t stream);
 
+/* ---- fine-tuning the encoder behind the classifier (`--mode Finetune` of ECAMP/Fine-tuning/Classification; csrc/finetune.hip).  Added at
+ * version 5: no existing signature changes.  Conventions as the linear-probe kernels above: f32 arithmetic, every sum in one fixed order
+ * (no float atomics, no workgroup waits for another: two calls on the same input give the same bits), grids capped with a loop beyond
+ * the cap; a null pointer, C outside [1, 64], D % 4 != 0, t0 >= t1 or n % 64 != 0 is refused before the device is touched. ---- */
+/* dfeat f32 [B, D] = dlogits [B, C] . W [C, D]: the head's data gradient (the share of `loss.backward()` that leaves the head towards
+ * the encoder), 1 <= C <= 64, D % 4 == 0; W and dfeat 16-byte aligned. */
+int ecamp_cls_head_dgrad(const float* dlogits, const float* W, float* dfeat, int64_t B, int32_t C, int32_t D, ecampStream_t stream);
+/* Backward of ecamp_pool_norm.  dfeat f32 [B, D]; pooled f32 [B, D] as ecamp_pool_norm returned it (mean and rstd are computed again
+ * from it); gamma f32 [D] or NULL (identity affine).  dgamma / dbeta f32 [D] (given together, or both NULL): WRITTEN, not accumulated,
+ * from per-workgroup partial sums in the workspace added in workgroup order.  dx [B, T, D] in `dtype` (0: f32, 1: the build's 16-bit
+ * format): dx[b, t, :] = dpooled[b] / (t1 - t0) for t0 <= t < t1 and 0 for every other token (the cls row).  dx, ws, dgamma and dbeta 16-byte aligned;
+ * ws: ecamp_pool_norm_bwd_workspace_bytes(...) bytes of device memory, scratch. */
+int64_t ecamp_pool_norm_bwd_workspace_bytes(int64_t B, int32_t T, int32_t D, int32_t t0, int32_t t1, int32_t dtype);
+int ecamp_pool_norm_bwd(const float* dfeat, const float* pooled, const float* gamma, float* dgamma, float* dbeta, void* dx, int64_t B,
+                        int32_t T, int32_t D, int32_t t0, int32_t t1, float eps, void* ws, int32_t dtype, ecampStream_t stream);
+/* sum(g^2) over the 64-element blocks of g [n] whose block_group byte is below 8 (ecamp_adamw_grouped's table; 255 = skipped), as ONE f32
+ * partial PER WORKGROUP in partials[0 .. slots): no scalar is produced, ecamp_sgd_grouped adds the partials itself.
+ * slots = ecamp_sumsq_grouped_slots(n) <= 2048 (a function of n alone; 0 for an n the launch refuses); *npart_out (a HOST int, nullable)
+ * receives the same number.  Two launches may fill disjoint ranges of one partials buffer (an arena and a tail buffer).  n % 64 == 0. */
+int64_t ecamp_sumsq_grouped_slots(int64_t n);
+int ecamp_sumsq_grouped(const float* g, const uint8_t* block_group, int64_t n, float* partials, int32_t* npart_out, ecampStream_t stream);
+/* torch.optim.SGD (momentum, dampening 0, no Nesterov, weight decay added to the gradient; train.py:377-384) behind
+ * torch.nn.utils.clip_grad_norm_(max_norm) (train.py:458), over a flat buffer with ecamp_adamw_grouped's block table and per-group
+ * lr / weight decay.  Every workgroup adds partials[0 .. npart) (device, ecamp_sumsq_grouped; npart <= 4096) in one fixed order, then
+ *   norm = sqrt(sum) * grad_scale;   coef = max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1
+ *   d = g * grad_scale * coef + wd * p;   buf = momentum * buf + d;   p -= lr * buf
+ * per element of a live block (a zero `buf` reproduces torch's first step); p16 (nullable): the 16-bit shadow, refreshed.  Blocks of
+ * group 255 are neither read nor written.  norm_out (nullable, device f32[1]) receives `norm`.  ctl (nullable, device f32[4] as
+ * ecamp_loss_scale_update writes it): ctl[0] replaces grad_scale, ctl[1] != 0 leaves every byte alone.  n % 64 == 0. */
+int ecamp_sgd_grouped(float* p, const float* g, float* buf, void* p16, const uint8_t* block_group, int64_t n, int32_t ngroups,
+                      const float* lr_host, const float* wd_host, float momentum, float max_norm, const float* partials, int32_t npart,
+                      float grad_scale, const float* ctl, float* norm_out, ecampStream_t stream);
+
 /* ---- optional in-process timing (bench.py roofline): HIP-event pairs around every GEMM / attention launch ---- */
 int ecamp_prof_enable(int on);
 int ecamp_prof_collect(int category, double* total_ms, double* total_work, int64_t* count); /* 0 gemm bf16, 1 gemm f32, 2 attention, 3 gemm fp8; <0 clears */

@@ -1,0 +1,167 @@
+"""Encoder fine-tuning, measured (profiles/finetune.txt): ViT-B/16 in bf16, R = 224, 14 classes, at B = 96 and B = 256 on one MI355X:
+
+  1  one fine-tune step end to end (engine_finetune.train_step: differentiable encoder forward, head, loss, the whole backward, the fused
+     clip + SGD step) in images/s, beside the probe step (engine_linprobe.train_step) of the same shape in the same process.
+  2  `ecamp_sumsq_grouped` + `ecamp_sgd_grouped` over the parameter arena (the launches of one FusedSGD.step, with its block table)
+     beside ONE `ecamp_adamw_grouped` launch over the same arena with the same table, alternating in one loop: HIP events around
+     groups of calls.  The two SGD launches move about 6.5 arena-sized streams of the live blocks (g; p, g, buf in; p, buf, p16 out)
+     where AdamW moves 7.5 (p, g, m, v in; p, m, v, p16 out): expected no more than 1.1 x AdamW's time.
+  3  `ecamp_pool_norm_bwd` (dx [B, 197, 768] in bf16) beside a plain device copy of the same bytes.
+
+    python tools/finetune_bench.py [--iters 20] [--warmup 3] [--batches 96,256] [--out profiles/finetune.txt]
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def stats(xs):
+    return statistics.median(xs), min(xs), max(xs)
+
+
+def timed(fn, iters, warmup, reps=3):
+    """Host clock around `iters` calls that end in a device synchronise, after `warmup` calls -> seconds per call, per repetition."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        for _ in range(iters):
+            fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) / iters)
+    return out
+
+
+def event_groups(fns, iters, warmup, group):
+    """HIP events around groups of `group` back-to-back calls of each fn, the fns alternating in one loop -> {name: [us per call]}."""
+    t = {name: [] for name, _ in fns}
+    for i in range(iters + warmup):
+        for name, fn in fns:
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(group):
+                fn()
+            b.record()
+            if i >= warmup:
+                t[name].append((a, b))
+        torch.cuda.synchronize()
+    return {name: [1e3 * p.elapsed_time(q) / group for p, q in pairs] for name, pairs in t.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--batches", type=str, default="96,256")
+    ap.add_argument("--classes", type=int, default=14)
+    ap.add_argument("--out", type=str, default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "finetune.txt"))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("finetune_bench needs an MI355X: nothing here can be measured on a CPU")
+    from ecamp_amd import engine_finetune, engine_linprobe
+    from ecamp_amd import hip_ops as ops
+    from ecamp_amd.module.classifier import build_classifier
+    lines = []
+
+    def say(msg):
+        print(msg, flush=True)
+        lines.append(msg)
+
+    dev = torch.device("cuda")
+    C = args.classes
+    torch.manual_seed(0)
+    clf = build_classifier("vit_base_patch16", C, True, img_size=224, compute_dtype=torch.bfloat16, train_encoder=True).to(dev)
+    step_args = argparse.Namespace(learning_rate=3e-2, weight_decay=1e-4, decay_type="cosine", warmup_steps=50, num_steps=3000, max_grad_norm=1.0)
+    say("encoder fine-tuning on %s: ViT-B/16 in bf16, R = 224, %d classes; %d iterations x 3 repetitions after %d warm-up calls"
+        % (torch.cuda.get_device_name(0), C, args.iters, args.warmup))
+    opt = engine_finetune.make_optimizer(clf, step_args)
+    A = opt.arena
+    live = int((opt._table < 8).sum().item()) * 64
+    say("arena: %d f32 elements (%.2f GB), of which fine-tuning updates %d (%.1f %%); tail buffer %d elements"
+        % (A.total, 4 * A.total / 1e9, live, 100.0 * live / A.total, opt._tail.total))
+
+    for B in [int(b) for b in args.batches.split(",")]:
+        imgs = torch.randn(B, 3, 224, 224, device=dev)
+        y = (torch.rand(B, C, device=dev) < 0.3).float()
+        n = [0]
+
+        def ft_step():
+            engine_finetune.train_step(clf, opt, imgs, y, n[0], step_args)
+            n[0] += 1
+
+        med, lo, hi = stats(timed(ft_step, args.iters, args.warmup))
+        say("1  B = %3d  fine-tune step (forward + backward + clip + SGD): %.2f ms (min %.2f, max %.2f) = %.0f images/s"
+            % (B, 1e3 * med, 1e3 * lo, 1e3 * hi, B / med))
+        clf.eval()
+        popt = engine_linprobe.make_optimizer(clf, step_args)
+        clf.head.weight.grad = clf.head.bias.grad = None      # the probe's optimizer clips and steps plain `.grad` tensors
+        m = [0]
+
+        def probe_step():
+            engine_linprobe.train_step(clf, popt, imgs, y, m[0], step_args)
+            m[0] += 1
+
+        med_p, lo_p, hi_p = stats(timed(probe_step, args.iters, args.warmup))
+        clf.tail()                                            # (`.grad` back onto the tail buffer)
+        say("   B = %3d  probe step (encoder forward + head + loss + head gradient + clip + SGD): %.2f ms (min %.2f, max %.2f) = %.0f images/s; "
+            "fine-tune / probe = %.2f x" % (B, 1e3 * med_p, 1e3 * lo_p, 1e3 * hi_p, B / med_p, med / med_p))
+
+        T, D = 197, 768
+        pooled = torch.randn(B, D, device=dev)
+        dfeat = torch.randn(B, D, device=dev)
+        gamma = torch.ones(D, device=dev)
+        src = torch.randn(B, T, D, device=dev).to(torch.bfloat16)
+        dst = torch.empty_like(src)
+        nbytes = src.numel() * 2
+        us = event_groups([("pool_norm_bwd", lambda: ops.pool_norm_bwd(dfeat, pooled, gamma, 1, T, T, 1e-6, torch.bfloat16)),
+                           ("device copy", lambda: dst.copy_(src))], args.iters, args.warmup, 20)
+        say("3  B = %3d  dx = bf16 [%d, %d, %d] = %.1f MB; per call, from event pairs around 20 calls (pool_norm_bwd includes its output / workspace allocations)"
+            % (B, B, T, D, nbytes / 1e6))
+        for name in ("pool_norm_bwd", "device copy"):
+            med_u, lo_u, hi_u = stats(us[name])
+            say("   %-16s median %7.1f us (min %.1f, max %.1f) = %.0f GB/s written" % (name, med_u, lo_u, hi_u, nbytes / (med_u * 1e-6) / 1e9))
+
+    # 2: the optimizer launches over the arena, same block table, same process
+    mbuf, vbuf = ops.zeros((A.total,), dev), ops.zeros((A.total,), dev)
+    lrs, wds = [1e-3], [1e-4]
+    ops.zero_(A.flat_g)
+    A.flat_g.normal_(std=1e-3)
+    n0 = ops.sumsq_grouped_slots(A.total)
+    partials = ops.zeros((n0,), dev)
+
+    def sgd():
+        ops.sumsq_grouped(A.flat_g, opt._table, partials)
+        ops.sgd_grouped(A.flat_p, A.flat_g, opt._buf, A.flat_p16, opt._table, lrs, wds, 0.9, 1.0, partials, n0, 1.0, None, opt.last_norm)
+
+    def sumsq_only():
+        ops.sumsq_grouped(A.flat_g, opt._table, partials)
+
+    def adamw():
+        ops.adamw_grouped(A.flat_p, A.flat_g, mbuf, vbuf, A.flat_p16, opt._table, lrs, wds, 0.9, 0.95, 1e-8, 10, 1.0, None, None)
+
+    us = event_groups([("sumsq_grouped + sgd_grouped", sgd), ("adamw_grouped", adamw), ("sumsq_grouped alone", sumsq_only)], args.iters, args.warmup, 5)
+    say("2  optimizer launches over the arena (%d live f32 elements of %d), per call, from event pairs around 5 calls, alternating:" % (live, A.total))
+    med_a = stats(us["adamw_grouped"])[0]
+    for name in ("sumsq_grouped + sgd_grouped", "adamw_grouped", "sumsq_grouped alone"):
+        med_u, lo_u, hi_u = stats(us[name])
+        streams = {"sumsq_grouped + sgd_grouped": 6.5, "adamw_grouped": 7.5, "sumsq_grouped alone": 1.0}[name]
+        say("   %-28s median %8.1f us (min %.1f, max %.1f) = %.2f x adamw_grouped; %.1f streams of %.2f GB = %.0f GB/s"
+            % (name, med_u, lo_u, hi_u, med_u / med_a, streams, 4 * live / 1e9, streams * 4 * live / (med_u * 1e-6) / 1e9))
+    say("   expectation: sumsq_grouped + sgd_grouped <= 1.10 x adamw_grouped (6.5 against 7.5 streams, a second launch): %s"
+        % ("met" if stats(us["sumsq_grouped + sgd_grouped"])[0] <= 1.1 * med_a else "NOT met"))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
