@@ -27,43 +27,55 @@ if not 1.0 <= F8_MARGIN <= 16.0:
     raise ValueError("ECAMP_FP8_MARGIN=%g: the delayed-scaling margin is a factor in [1, 16]" % F8_MARGIN)
 
 
-class FlatTail:
-    """A small flat f32 buffer for the few parameters that live outside a model's arena (the classifier's fc_norm and head): values,
-    gradients and SGD momentum in three buffers of one layout, every tensor padded to 64 elements, so that the grouped optimizer
-    kernels update them in one launch with the arena's clip coefficient.  `p.data` and `p.grad` become views; autograd accumulates into
-    `.grad` in place."""
+def flat_layout(sizes):
+    """Element counts -> (offsets, total): the tensors in order, each padded to ALIGN elements."""
+    offsets, off = [], 0
+    for n in sizes:
+        offsets.append(off)
+        off += (n + ALIGN - 1) // ALIGN * ALIGN
+    return offsets, off
 
-    def __init__(self, named_params):
-        named_params = list(named_params)
-        dev = named_params[0][1].device
-        if dev.type != "cuda":
-            raise ops._lib.EcampHipError("FlatTail needs the parameters on an MI355X device (model.to('cuda')); no CPU fallback exists")
+
+def block_table(total, spans):
+    """uint8 [total // ALIGN] on the CPU for the grouped optimizer kernels: every ALIGN-element block of a span (offset, size, group) carries
+    that span's group index, every other block 255 (frozen / not this optimizer's: the kernels skip it)."""
+    table = torch.full((total // ALIGN,), 255, dtype=torch.uint8)
+    for o, n, g in spans:
+        table[o // ALIGN:(o + n + ALIGN - 1) // ALIGN] = g
+    return table
+
+
+class FlatSpace:
+    """Named parameters in one flat f32 buffer `flat_p`, their gradients in a second one `flat_g` of the same layout (`flat_layout`);
+    `p.data` and `p.grad` become views, and autograd accumulates into `.grad` in place.  A subclass supplies `zero_grad`."""
+
+    def __init__(self, named_params, dev):
         self.device = dev
-        self.names, self.params, self.offsets, self.sizes, self.index = [], [], [], [], {}
-        off = 0
-        for name, p in named_params:
-            self.index[id(p)] = len(self.params)
-            self.names.append(name)
-            self.params.append(p)
-            self.offsets.append(off)
-            self.sizes.append(p.numel())
-            off += (p.numel() + ALIGN - 1) // ALIGN * ALIGN
-        self.total = off
-        self.flat_p = ops.zeros((off,), dev)
-        self.flat_g = ops.zeros((off,), dev)
-        self.flat_buf = ops.zeros((off,), dev)
+        self.names = [name for name, _ in named_params]
+        self.params = [p for _, p in named_params]
+        self.sizes = [p.numel() for p in self.params]
+        self.offsets, self.total = flat_layout(self.sizes)
+        self.index = {id(p): i for i, p in enumerate(self.params)}
+        self.flat_p = ops.zeros((self.total,), dev)
+        self.flat_g = ops.zeros((self.total,), dev)
         for p, o, n in zip(self.params, self.offsets, self.sizes):
             self.flat_p[o:o + n].view(p.shape).copy_(p.data)
             p.data = self.flat_p[o:o + n].view(p.shape)
             p.grad = self.flat_g[o:o + n].view(p.shape)
-            p._ecamp_tail = self
 
-    def owns(self):
-        """False once something re-materialised the parameters (module.to(), load into fresh tensors): the tail is then rebuilt."""
-        return all(p.data_ptr() == self.flat_p.data_ptr() + 4 * o and p.device == self.device for p, o in zip(self.params, self.offsets))
+    def span(self, p):
+        """-> (offset, size) of parameter p in the flat buffers."""
+        i = self.index[id(p)]
+        return self.offsets[i], self.sizes[i]
+
+    def block_table(self, param_groups):
+        """`block_table` of an optimizer's groups: parameters of another space, and the ones whose gradient never arrives
+        (`_ecamp_unused`), stay 255."""
+        return block_table(self.total, [(*self.span(p), gi) for gi, g in enumerate(param_groups) for p in g["params"]
+                                        if id(p) in self.index and not getattr(p, "_ecamp_unused", False)])
 
     def attach_grads(self):
-        """Re-point p.grad at the buffer if someone set it to None (zero_grad(set_to_none=True))."""
+        """Re-point p.grad at the buffer if someone set it to None (stock optimizers' zero_grad(set_to_none=True))."""
         lost = False
         for p, o, n in zip(self.params, self.offsets, self.sizes):
             if p.grad is None or p.grad.data_ptr() != self.flat_g.data_ptr() + 4 * o:
@@ -72,11 +84,31 @@ class FlatTail:
         if lost:
             self.zero_grad()
 
+
+class FlatTail(FlatSpace):
+    """A small flat f32 buffer for the few parameters that live outside a model's arena (the classifier's fc_norm and head): values,
+    gradients and SGD momentum in three buffers of one layout, so that the grouped optimizer kernels update them in one launch with the
+    arena's clip coefficient."""
+
+    def __init__(self, named_params):
+        named_params = list(named_params)
+        dev = named_params[0][1].device
+        if dev.type != "cuda":
+            raise ops._lib.EcampHipError("FlatTail needs the parameters on an MI355X device (model.to('cuda')); no CPU fallback exists")
+        super().__init__(named_params, dev)
+        self.flat_buf = ops.zeros((self.total,), dev)
+        for p in self.params:
+            p._ecamp_tail = self
+
+    def owns(self):
+        """False once something re-materialised the parameters (module.to(), load into fresh tensors): the tail is then rebuilt."""
+        return all(p.data_ptr() == self.flat_p.data_ptr() + 4 * o and p.device == self.device for p, o in zip(self.params, self.offsets))
+
     def zero_grad(self):
         ops.zero_(self.flat_g)
 
 
-class ParamArena:
+class ParamArena(FlatSpace):
     def __init__(self, model, compute_dtype):
         # registration order, except that members of a fuse group (e.g. BERT query/key/value weights, which run as one
         # [3H,H] GEMM) are placed back to back at the position of the group's first member
@@ -98,29 +130,12 @@ class ParamArena:
         dev = params[0][1].device
         if dev.type != "cuda":
             raise ops._lib.EcampHipError("ParamArena needs the model on an MI355X device (model.to('cuda')); no CPU fallback exists")
-        self.device = dev
+        super().__init__(params, dev)
         self.compute_dtype = compute_dtype
-        self.names, self.params, self.offsets, self.sizes = [], [], [], []
-        off = 0
-        for name, p in params:
-            n = p.numel()
-            self.names.append(name)
-            self.params.append(p)
-            self.offsets.append(off)
-            self.sizes.append(n)
-            off += (n + ALIGN - 1) // ALIGN * ALIGN
-        self.total = off
-        self.flat_p = ops.zeros((off,), dev)
-        self.flat_g = ops.zeros((off,), dev)
-        self.flat_p16 = torch.empty((off,), device=dev, dtype=compute_dtype) if compute_dtype in (torch.bfloat16, torch.float16) else None
-        self.index = {}
-        for i, (p, o, n) in enumerate(zip(self.params, self.offsets, self.sizes)):
-            self.flat_p[o:o + n].view(p.shape).copy_(p.data)
-            p.data = self.flat_p[o:o + n].view(p.shape)
-            p.grad = self.flat_g[o:o + n].view(p.shape)
+        self.flat_p16 = torch.empty((self.total,), device=dev, dtype=compute_dtype) if compute_dtype in (torch.bfloat16, torch.float16) else None
+        for i, p in enumerate(self.params):
             p._ecamp_slot = i
             p._ecamp_arena = self
-            self.index[id(p)] = i
         self.unused = [i for i, p in enumerate(self.params) if getattr(p, "_ecamp_unused", False)]
         self.on_ready = None  # callback(list of slot ids) set by the data-parallel reducer
         self.reducer = None   # the GradReducer itself (parallel.DistributedDataParallel): the loss scaler / optimizer check it
@@ -143,16 +158,14 @@ class ParamArena:
 
     # -- views ---------------------------------------------------------------------------------
     def grad(self, p):
-        i = self.index[id(p)]
-        o, n = self.offsets[i], self.sizes[i]
+        o, n = self.span(p)
         return self.flat_g[o:o + n].view(p.shape)
 
     def w(self, p):
         """The tensor the kernels read for parameter p: the bf16 shadow in bf16 mode, the f32 master otherwise."""
         if self.flat_p16 is None:
             return p.data
-        i = self.index[id(p)]
-        o, n = self.offsets[i], self.sizes[i]
+        o, n = self.span(p)
         return self.flat_p16[o:o + n].view(p.shape)
 
     def gradw(self, ps, shape=None):
@@ -190,7 +203,7 @@ class ParamArena:
         i = self.index[id(plist[0])]
         if self._w8.get("version") != self.version:
             self._quantize_weights()
-        o, n = self._span(plist) if len(plist) > 1 else (self.offsets[i], self.sizes[i])
+        o, n = self._span(plist) if len(plist) > 1 else self.span(plist[0])
         q = self.flat_p8[o:o + n]
         return (q.view(shape) if shape is not None else q.view(plist[0].shape)), self.w8_scale[self._w8["sid"][i]:self._w8["sid"][i] + 1]
 
@@ -284,16 +297,6 @@ class ParamArena:
             self._zero_flags = flags.to(self.device)
         ops.zero_blocks_(self.flat_g, self._zero_flags)
         self._fresh = set(self._gemm_written) - set(self.unused)
-
-    def attach_grads(self):
-        """Re-point p.grad at the arena if someone set it to None (stock optimizers' zero_grad(set_to_none=True))."""
-        lost = False
-        for p, o, n in zip(self.params, self.offsets, self.sizes):
-            if p.grad is None or p.grad.data_ptr() != self.flat_g.data_ptr() + 4 * o:
-                p.grad = self.flat_g[o:o + n].view(p.shape)
-                lost = True
-        if lost:
-            self.zero_grad()
 
     def ready(self, *ps):
         if self.on_ready is not None:

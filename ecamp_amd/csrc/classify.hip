@@ -3,7 +3,7 @@
 // its loss, gradient and weight gradient.  Everything here is f32 arithmetic and DETERMINISTIC: every sum has one fixed order (per-thread
 // strides, LDS slices added in index order, partials added in index order), no float atomic, and no workgroup waits for another.
 // No grid depends on a row count beyond a cap: the kernels loop over samples / rows.
-#include "common.h"
+#include "classify.h"
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // ecamp_pool_norm.  HBM-bound (B = 256, T = 197, D = 768 in 16 bits: 77 MB), so the token range of a sample is spread over `nchunk`
@@ -29,33 +29,6 @@ template <> struct PoolVec<bf16_t, 8> {
         a[4] += h16_lo(v.z); a[5] += h16_hi(v.z); a[6] += h16_lo(v.w); a[7] += h16_hi(v.w);
     }
 };
-
-constexpr int POOL_THREADS = 256;
-constexpr int POOL_MAX_GRID = 2048;     // workgroups per launch: beyond it a workgroup takes several (sample, chunk, slab) items in turn
-constexpr int POOL_TARGET_WG = 1024;    // four workgroups per CU (4 x 16-byte loads per thread in flight) before the token range stops being split further
-constexpr int POOL_MAX_CHUNKS = 64;
-
-struct PoolPlan {
-    int vec, nv, cw, rows_par, nslab, nchunk, chunk_len;
-};
-
-// The split is a function of (B, token count, D, dtype) alone, so that ecamp_pool_norm_workspace_bytes and the launch agree.
-static PoolPlan pool_plan(int64_t B, int ntok, int D, int dtype) {
-    PoolPlan p;
-    p.vec = (dtype == ECAMP_F32) ? 4 : (D % 8 == 0 ? 8 : 4);
-    p.nv = D / p.vec;
-    p.cw = p.nv < POOL_THREADS ? p.nv : POOL_THREADS;
-    p.rows_par = POOL_THREADS / p.cw;
-    p.nslab = ceil_div(p.nv, p.cw);
-    int64_t want = (POOL_TARGET_WG + B * p.nslab - 1) / (B * p.nslab);
-    const int most = ceil_div(ntok, (int64_t)p.rows_par * 4);   // a thread keeps at least four tokens of its lane
-    if (want > most) want = most;
-    if (want > POOL_MAX_CHUNKS) want = POOL_MAX_CHUNKS;
-    if (want < 1) want = 1;
-    p.chunk_len = ceil_div(ntok, want);
-    p.nchunk = ceil_div(ntok, p.chunk_len);
-    return p;
-}
 
 template <typename T, int VEC>
 __global__ __launch_bounds__(POOL_THREADS) void pool_partial_kernel(const T* __restrict__ x, float* __restrict__ part, int64_t B, int Tn, int D,
@@ -135,7 +108,7 @@ __global__ __launch_bounds__(256) void pool_norm_finish_kernel(const float* __re
 }
 
 extern "C" int64_t ecamp_pool_norm_workspace_bytes(int64_t B, int32_t T, int32_t D, int32_t t0, int32_t t1, int32_t dtype) {
-    if (B < 1 || T < 1 || D < 4 || D % 4 != 0 || t0 < 0 || t0 >= t1 || t1 > T || (dtype != ECAMP_F32 && dtype != ECAMP_BF16)) return 0;
+    if (!pool_shape_ok(B, T, D, t0, t1, dtype)) return 0;
     const PoolPlan p = pool_plan(B, t1 - t0, D, dtype);
     return B * p.nchunk * (int64_t)D * (int64_t)sizeof(float);
 }
@@ -153,7 +126,7 @@ extern "C" int ecamp_pool_norm(const void* x, const float* gamma, const float* b
     ECAMP_CHECK_ARG(al16(ws) && al16(pooled) && al16(feat) && (reinterpret_cast<uintptr_t>(x) & (p.vec == 4 && dtype == ECAMP_BF16 ? 7 : 15)) == 0,
                     "pool_norm: x, pooled, feat and ws must be 16-byte aligned");
     const int64_t items = B * p.nchunk * p.nslab;
-    const dim3 grid((unsigned)(items < POOL_MAX_GRID ? items : POOL_MAX_GRID)), block(POOL_THREADS);
+    const dim3 grid((unsigned)(items < CLS_MAX_GRID ? items : CLS_MAX_GRID)), block(POOL_THREADS);
 #define L(T_, V_) hipLaunchKernelGGL((pool_partial_kernel<T_, V_>), grid, block, 0, stream, (const T_*)x, (float*)ws, B, T, D, t0, t1, p.nv, p.cw, \
                                      p.rows_par, p.nslab, p.nchunk, p.chunk_len)
     if (dtype == ECAMP_F32) L(float, 4);
@@ -161,7 +134,7 @@ extern "C" int ecamp_pool_norm(const void* x, const float* gamma, const float* b
     else L(bf16_t, 4);
 #undef L
     ECAMP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(pool_norm_finish_kernel, dim3((unsigned)(B < POOL_MAX_GRID ? B : POOL_MAX_GRID)), dim3(256), 0, stream, (const float*)ws, gamma,
+    hipLaunchKernelGGL(pool_norm_finish_kernel, dim3((unsigned)(B < CLS_MAX_GRID ? B : CLS_MAX_GRID)), dim3(256), 0, stream, (const float*)ws, gamma,
                        beta, pooled, feat, B, D, p.nchunk, (float)(t1 - t0), eps);
     ECAMP_LAUNCH_CHECK();
     return 0;
@@ -170,9 +143,6 @@ extern "C" int ecamp_pool_norm(const void* x, const float* gamma, const float* b
 // ---------------------------------------------------------------------------------------------------------------------------------
 // The head: logits[B, C] = feat[B, D] . W[C, D]^T + b[C] for 1 <= C <= 64 (the datasets have 1..20 classes: N far below an MFMA tile, so
 // a plain f32 dot product): one wave per (sample, class), lanes stride over the row in 16-byte vectors, one wave reduction.
-constexpr int CLS_MAX_CLASSES = 64;
-constexpr int CLS_MAX_GRID = 2048;
-
 __global__ __launch_bounds__(256) void cls_head_fwd_kernel(const float* __restrict__ feat, const float* __restrict__ W, const float* __restrict__ bias,
                                                            float* __restrict__ logits, int64_t B, int C, int D) {
     const int lane = threadIdx.x & 63;

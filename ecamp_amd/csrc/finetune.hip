@@ -4,10 +4,8 @@
 // ecamp_sgd_grouped).  Conventions as classify.hip: f32 arithmetic, every sum in ONE fixed order (per-thread strides, LDS, partials in
 // index order), no float atomic, no workgroup waits for another, grids capped with a loop beyond the cap.  All four are HBM-bound:
 // 16-byte accesses, three or four loads in flight per thread, enough workgroups for 256 CUs.
-#include "common.h"
-
-constexpr int FT_MAX_CLASSES = 64;
-constexpr int FT_MAX_GRID = 2048;
+#include "classify.h"
+#include "group_hyper.h"
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // dfeat[B, D] = dlogits[B, C] . W[C, D]: the data gradient of the head (C <= 64: far below an MFMA tile).  One thread per (sample,
@@ -33,12 +31,12 @@ __global__ __launch_bounds__(256) void cls_head_dgrad_kernel(const float* __rest
 
 extern "C" int ecamp_cls_head_dgrad(const float* dlogits, const float* W, float* dfeat, int64_t B, int32_t C, int32_t D, hipStream_t stream) {
     ECAMP_CHECK_ARG(dlogits && W && dfeat, "cls_head_dgrad: null pointer");
-    ECAMP_CHECK_ARG(C >= 1 && C <= FT_MAX_CLASSES, "cls_head_dgrad: C=%d must lie in [1, %d]", C, FT_MAX_CLASSES);
+    ECAMP_CHECK_ARG(C >= 1 && C <= CLS_MAX_CLASSES, "cls_head_dgrad: C=%d must lie in [1, %d]", C, CLS_MAX_CLASSES);
     ECAMP_CHECK_ARG(D >= 4 && D % 4 == 0, "cls_head_dgrad: D=%d must be a positive multiple of 4", D);
     ECAMP_CHECK_ARG(B >= 1, "cls_head_dgrad: B=%lld must be positive", (long long)B);
     ECAMP_CHECK_ARG(((reinterpret_cast<uintptr_t>(W) | reinterpret_cast<uintptr_t>(dfeat)) & 15) == 0, "cls_head_dgrad: W and dfeat must be 16-byte aligned");
     const int64_t blocks = (B * (D / 4) + 255) / 256;
-    hipLaunchKernelGGL(cls_head_dgrad_kernel, dim3((unsigned)(blocks < FT_MAX_GRID ? blocks : FT_MAX_GRID)), dim3(256), 0, stream, dlogits, W, dfeat,
+    hipLaunchKernelGGL(cls_head_dgrad_kernel, dim3((unsigned)(blocks < CLS_MAX_GRID ? blocks : CLS_MAX_GRID)), dim3(256), 0, stream, dlogits, W, dfeat,
                        B, C, D);
     ECAMP_LAUNCH_CHECK();
     return 0;
@@ -52,33 +50,9 @@ extern "C" int ecamp_cls_head_dgrad(const float* dlogits, const float* W, float*
 //   2. dgamma / dbeta = the slabs added in workgroup order (written, not accumulated);
 //   3. the store of dx [B, T, D] -- where the bytes are (77 MB at B = 256 in 16 bits): the rows of a sample are split over workgroups as
 //      ecamp_pool_norm splits them, a thread converts its 16-byte column vector once and stores it down its row lane; rows outside
-//      [t0, t1) get zeros.
+//      [t0, t1) get zeros.  (pool_plan, classify.h: the one split of both directions.)
 constexpr int PNB_ROW_GRID = 256;       // workgroups of launch 1 = partial slabs launch 2 adds per column
-constexpr int PNB_TARGET_WG = 1024;     // four workgroups per CU before the row range stops being split further
-constexpr int PNB_MAX_CHUNKS = 64;
-
-struct PnbPlan {
-    int vec, nv, cw, rows_par, nslab, nchunk, chunk_len, nrow_wg;
-};
-
-// a function of (B, T, D, dtype) alone, so that ecamp_pool_norm_bwd_workspace_bytes and the launch agree
-static PnbPlan pnb_plan(int64_t B, int T, int D, int dtype) {
-    PnbPlan p;
-    p.vec = (dtype == ECAMP_F32) ? 4 : (D % 8 == 0 ? 8 : 4);
-    p.nv = D / p.vec;
-    p.cw = p.nv < 256 ? p.nv : 256;
-    p.rows_par = 256 / p.cw;
-    p.nslab = ceil_div(p.nv, p.cw);
-    int64_t want = (PNB_TARGET_WG + B * p.nslab - 1) / (B * p.nslab);
-    const int most = ceil_div(T, (int64_t)p.rows_par * 4);   // a thread keeps at least four rows of its lane
-    if (want > most) want = most;
-    if (want > PNB_MAX_CHUNKS) want = PNB_MAX_CHUNKS;
-    if (want < 1) want = 1;
-    p.chunk_len = ceil_div(T, want);
-    p.nchunk = ceil_div(T, p.chunk_len);
-    p.nrow_wg = (int)(B < PNB_ROW_GRID ? B : PNB_ROW_GRID);
-    return p;
-}
+static int pnb_row_wgs(int64_t B) { return (int)(B < PNB_ROW_GRID ? B : PNB_ROW_GRID); }
 
 // The one place of this file that leaves f32 arithmetic: dpooled = rstd * (g - mean(g) - xhat * mean(g * xhat)) cancels, and an element
 // that comes out small carries the f32 rounding of its three terms -- 1e-7 of THEIR size, not of its own -- while the 16-bit dx is held
@@ -211,14 +185,9 @@ __global__ __launch_bounds__(256) void pool_norm_bwd_store_kernel(const float* _
     }
 }
 
-static bool pnb_shape_ok(int64_t B, int32_t T, int32_t D, int32_t t0, int32_t t1, int32_t dtype) {
-    return B >= 1 && T >= 1 && D >= 4 && D % 4 == 0 && t0 >= 0 && t0 < t1 && t1 <= T && (dtype == ECAMP_F32 || dtype == ECAMP_BF16);
-}
-
 extern "C" int64_t ecamp_pool_norm_bwd_workspace_bytes(int64_t B, int32_t T, int32_t D, int32_t t0, int32_t t1, int32_t dtype) {
-    if (!pnb_shape_ok(B, T, D, t0, t1, dtype)) return 0;
-    const PnbPlan p = pnb_plan(B, T, D, dtype);
-    return (B + 2 * (int64_t)p.nrow_wg) * D * (int64_t)sizeof(float);   // dpooled [B, D] | slabs [nrow_wg, 2, D]
+    if (!pool_shape_ok(B, T, D, t0, t1, dtype)) return 0;
+    return (B + 2 * (int64_t)pnb_row_wgs(B)) * D * (int64_t)sizeof(float);   // dpooled [B, D] | slabs [row workgroups, 2, D]
 }
 
 extern "C" int ecamp_pool_norm_bwd(const float* dfeat, const float* pooled, const float* gamma, float* dgamma, float* dbeta, void* dx, int64_t B,
@@ -229,22 +198,23 @@ extern "C" int ecamp_pool_norm_bwd(const float* dfeat, const float* pooled, cons
     ECAMP_CHECK_ARG(t0 >= 0 && t0 < t1 && t1 <= T, "pool_norm_bwd: token range t0=%d, t1=%d must satisfy 0 <= t0 < t1 <= T=%d", t0, t1, T);
     ECAMP_CHECK_ARG(B >= 1, "pool_norm_bwd: B=%lld must be positive", (long long)B);
     ECAMP_CHECK_ARG(dtype == ECAMP_F32 || dtype == ECAMP_BF16, "pool_norm_bwd: bad dtype %d", dtype);
-    const PnbPlan p = pnb_plan(B, T, D, dtype);
+    const PoolPlan p = pool_plan(B, T, D, dtype);
+    const int nrow_wg = pnb_row_wgs(B);
     ECAMP_CHECK_ARG((reinterpret_cast<uintptr_t>(ws) & 15) == 0 && (reinterpret_cast<uintptr_t>(dx) & (p.vec == 4 && dtype == ECAMP_BF16 ? 7 : 15)) == 0 &&
                         ((reinterpret_cast<uintptr_t>(dgamma) | reinterpret_cast<uintptr_t>(dbeta)) & 15) == 0,
                     "pool_norm_bwd: dx, ws, dgamma and dbeta must be 16-byte aligned");
     float* dpool = (float*)ws;
     float* part = dgamma ? dpool + B * D : nullptr;
-    hipLaunchKernelGGL(pool_norm_bwd_row_kernel, dim3((unsigned)p.nrow_wg), dim3(256), 0, stream, dfeat, pooled, gamma, dpool, part, B, D,
+    hipLaunchKernelGGL(pool_norm_bwd_row_kernel, dim3((unsigned)nrow_wg), dim3(256), 0, stream, dfeat, pooled, gamma, dpool, part, B, D,
                        t1 - t0, eps);
     ECAMP_LAUNCH_CHECK();
     if (dgamma) {
         hipLaunchKernelGGL(pool_norm_bwd_affine_kernel, dim3((unsigned)ceil_div(D, 64)), dim3(256), 0, stream, (const float*)part, dgamma, dbeta, D,
-                           p.nrow_wg);
+                           nrow_wg);
         ECAMP_LAUNCH_CHECK();
     }
     const int64_t items = B * p.nchunk * p.nslab;
-    const dim3 grid((unsigned)(items < FT_MAX_GRID ? items : FT_MAX_GRID)), block(256);
+    const dim3 grid((unsigned)(items < CLS_MAX_GRID ? items : CLS_MAX_GRID)), block(256);
 #define L(T_, V_) hipLaunchKernelGGL((pool_norm_bwd_store_kernel<T_, V_>), grid, block, 0, stream, (const float*)dpool, (T_*)dx, B, T, D, t0, t1, p.nv, \
                                      p.cw, p.rows_par, p.nslab, p.nchunk, p.chunk_len)
     if (dtype == ECAMP_F32) L(float, 4);
@@ -309,15 +279,8 @@ extern "C" int ecamp_sumsq_grouped(const float* g, const uint8_t* block_group, i
 // with ecamp_adamw_grouped's block table.  Every workgroup adds partials[0 .. npart) itself -- a few thousand floats from L2, in one
 // order: thread t takes slots t, t + 256, ... in turn, then the 256 sums go through block_sum_256 -- so every workgroup holds the same
 // bits of the norm and nothing waits for a reduction launch.  A zero momentum buffer reproduces torch's first step (buf = d).
-struct SgdHyper {
-    float lr[8];
-    float wd[8];
-};
-
-constexpr int SGD_MAX_GRID = 8192;      // as ecamp_adamw_grouped
-
 __global__ __launch_bounds__(256) void sgd_grouped_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
-                                                          bf16_t* __restrict__ p16, const unsigned char* __restrict__ grp, long n4, SgdHyper hp,
+                                                          bf16_t* __restrict__ p16, const unsigned char* __restrict__ grp, long n4, GroupHyper hp,
                                                           float momentum, float max_norm, const float* __restrict__ partials, int npart,
                                                           float gscale, const float* __restrict__ ctl, float* __restrict__ norm_out) {
     __shared__ float sh[4];
@@ -361,14 +324,14 @@ extern "C" int ecamp_sgd_grouped(float* p, const float* g, float* buf, void* p16
     ECAMP_CHECK_ARG(npart >= 0 && npart <= 2 * SUMSQ_MAX_SLOTS, "sgd_grouped: npart=%d must lie in [0, %d]", npart, 2 * SUMSQ_MAX_SLOTS);
     ECAMP_CHECK_ARG(partials || npart == 0, "sgd_grouped: null pointer (partials) with npart=%d", npart);
     ECAMP_CHECK_ARG(!(max_norm > 0.f) || npart > 0, "sgd_grouped: max_norm=%g needs the partials of ecamp_sumsq_grouped (npart=%d)", (double)max_norm, npart);
-    SgdHyper hp;
+    GroupHyper hp;
     for (int i = 0; i < 8; ++i) {
         hp.lr[i] = i < ngroups ? lr_host[i] : 0.f;
         hp.wd[i] = i < ngroups ? wd_host[i] : 0.f;
     }
     const long n4 = n / 4;
     int nb = (int)((n4 + 255) / 256);
-    if (nb > SGD_MAX_GRID) nb = SGD_MAX_GRID;
+    if (nb > GROUPED_MAX_GRID) nb = GROUPED_MAX_GRID;
     hipLaunchKernelGGL(sgd_grouped_kernel, dim3(nb), dim3(256), 0, stream, p, g, buf, (bf16_t*)p16, block_group, n4, hp, momentum, max_norm, partials,
                        npart, grad_scale, ctl, norm_out);
     ECAMP_LAUNCH_CHECK();

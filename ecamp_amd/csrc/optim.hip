@@ -2,6 +2,7 @@
 // global gradient sum-of-squares (misc.py:280-292) and fused decoupled-weight-decay Adam (torch AdamW
 // semantics, main_pretrain.py:254) that also refreshes the bf16 shadow copy the MFMA GEMMs read.
 #include "common.h"
+#include "group_hyper.h"
 
 __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ x, long n4, float* __restrict__ out) {
     __shared__ float sh[4];
@@ -68,10 +69,6 @@ extern "C" int ecamp_adamw(float* p, const float* g, float* m, float* v, void* p
 // the arena; `block_group[i]` (uint8) names the param_group of block i (255 = frozen / unused -> skipped), and
 // each group carries its own (lr, weight_decay) so timm's decay / no-decay split (main_pretrain.py:253) and
 // `lr_scale` groups need no extra launches.
-struct GroupHyper {
-    float lr[8];
-    float wd[8];
-};
 __global__ __launch_bounds__(256) void adamw_grouped_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                             float* __restrict__ m, float* __restrict__ v,
                                                             bf16_t* __restrict__ p16, const unsigned char* __restrict__ grp,
@@ -126,7 +123,7 @@ extern "C" int ecamp_adamw_grouped(float* p, const float* g, float* m, float* v,
     }
     long n4 = n / 4;
     int nb = (int)((n4 + 255) / 256);
-    if (nb > 8192) nb = 8192;
+    if (nb > GROUPED_MAX_GRID) nb = GROUPED_MAX_GRID;
     double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
     hipLaunchKernelGGL(adamw_grouped_kernel, dim3(nb), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, block_group, n4, hp, beta1,
                        beta2, eps, (float)bc1, (float)(1.0 / sqrt(bc2)), grad_scale, grad_sumsq, ctl);

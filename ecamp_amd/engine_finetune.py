@@ -21,25 +21,17 @@ def make_optimizer(model, args):
 
 
 def train_step(model, optimizer, x, y, global_step, args):
-    """One iteration of train.py:438-465 -> (the loss as a device scalar, the learning rate of this step).  The scheduler is stepped
-    before the optimizer (train.py:462-463), so optimizer step k (1-based) runs at learning_rate * factor(k)."""
+    """One fine-tune iteration in training mode -> (loss as a device scalar, learning rate): engine_linprobe._train_step; the clip is
+    inside the fused step."""
     model.train()
-    loss = model.loss(model(x), y)
-    loss.backward()
-    lr = args.learning_rate * lr_factor(args.decay_type, global_step + 1, args.warmup_steps, args.num_steps)
-    for grp in optimizer.param_groups:
-        grp["lr"] = lr
-    optimizer.step()
-    optimizer.zero_grad()
-    return loss.detach(), lr
+    return _lp._train_step(model, optimizer, x, y, global_step, args)
 
 
 def train(model, train_loader, val_loader, args, log=print, writer=None, keep_losses=False):
-    """engine_linprobe.train with the fused optimizer and step of this module.  Validation runs the forward-only path (`evaluate`
+    """engine_linprobe's loop with the fused optimizer and step of this module.  Validation runs the forward-only path (`evaluate`
     is under no_grad) and the model is back in training mode at the next step."""
     model.train()
     try:
-        return _lp.train(model, train_loader, val_loader, args, log=log, writer=writer, keep_losses=keep_losses, make_optimizer=make_optimizer,
-                         train_step=train_step)
+        return _lp._train(model, train_loader, val_loader, args, log, writer, keep_losses, make_optimizer, train_step)
     finally:
         model.eval()

@@ -52,18 +52,26 @@ def make_optimizer(model, args):
     return torch.optim.SGD(head_parameters(model), lr=args.learning_rate, momentum=0.9, weight_decay=args.weight_decay)
 
 
-def train_step(model, optimizer, x, y, global_step, args):
-    """One iteration of train.py:438-465 -> the loss as a device scalar.  The scheduler is stepped before the optimizer (train.py:462-463),
-    so optimizer step k (1-based) runs at learning_rate * factor(k)."""
+def _train_step(model, optimizer, x, y, global_step, args, clip=None):
+    """One iteration of train.py:438-465 -> (the loss as a device scalar, the learning rate of this step).  The scheduler is stepped
+    before the optimizer (train.py:462-463), so optimizer step k (1-based) runs at learning_rate * factor(k).  `clip()` runs between
+    backward and the step, for an optimizer that does not clip inside its step.  (set_to_none: the fused optimizers keep `.grad` as views
+    whatever is asked.)"""
     loss = model.loss(model(x), y)
     loss.backward()
-    torch.nn.utils.clip_grad_norm_(head_parameters(model), args.max_grad_norm)
+    if clip is not None:
+        clip()
     lr = args.learning_rate * lr_factor(args.decay_type, global_step + 1, args.warmup_steps, args.num_steps)
     for grp in optimizer.param_groups:
         grp["lr"] = lr
     optimizer.step()
     optimizer.zero_grad(set_to_none=True)
     return loss.detach(), lr
+
+
+def train_step(model, optimizer, x, y, global_step, args):
+    """One probe iteration -> (loss as a device scalar, learning rate): `_train_step` with the head's gradients clipped before the step."""
+    return _train_step(model, optimizer, x, y, global_step, args, clip=lambda: torch.nn.utils.clip_grad_norm_(head_parameters(model), args.max_grad_norm))
 
 
 @torch.no_grad()
@@ -104,13 +112,16 @@ def checkpoint_path(args, multilabel):
     return os.path.join(args.output_dir, "%s_%s_checkpoint.bin" % (args.name, "bestauc" if multilabel else "bestacc"))
 
 
-def train(model, train_loader, val_loader, args, log=print, writer=None, keep_losses=False, make_optimizer=None, train_step=None):
-    """train.py:364-509 for the head: passes over `train_loader` until `num_steps` optimizer steps are done or the validation result
-    has not improved for PATIENCE validations; validation after every pass; the best checkpoint (mean AUROC, ties replace: `<=`;
-    accuracy: `<`) is written in the reference's flat layout.  -> dict(global_step, best, losses (device scalars, keep_losses only)).
-    `make_optimizer` / `train_step`: another optimizer and step under the same loop (engine_finetune); the defaults are this module's."""
-    make_optimizer = make_optimizer or globals()["make_optimizer"]
-    train_step = train_step or globals()["train_step"]
+def train(model, train_loader, val_loader, args, log=print, writer=None, keep_losses=False):
+    """Train the head (train.py:364-509) -> dict(global_step, best, losses): `_train` with this module's optimizer and step."""
+    return _train(model, train_loader, val_loader, args, log, writer, keep_losses, make_optimizer, train_step)
+
+
+def _train(model, train_loader, val_loader, args, log, writer, keep_losses, make_optimizer, train_step):
+    """train.py:364-509 under the optimizer and step of the calling engine: passes over `train_loader` until `num_steps` optimizer steps
+    are done or the validation result has not improved for PATIENCE validations; validation after every pass; the best checkpoint (mean
+    AUROC, ties replace: `<=`; accuracy: `<`) is written in the reference's flat layout.  -> dict(global_step, best, losses (device
+    scalars, keep_losses only))."""
     optimizer = make_optimizer(model, args)
     optimizer.zero_grad(set_to_none=True)
     print_freq = max(1, int(getattr(args, "print_freq", 50)))

@@ -14,10 +14,6 @@ drop_path_rate=0.1) is not applied, and `pos_embed` is held at the fixed sin-cos
 NOT implemented, and refused with a message before any device work: data-parallel fine-tuning (`--local_rank` other than -1),
 `--gradient_accumulation_steps` other than 1, and `--fp16` (IEEE half with loss scaling): use `--compute_dtype bf16`.
 """
-import os
-import random
-
-import numpy as np
 import torch
 
 from . import main_linprobe
@@ -28,7 +24,7 @@ DEVIATIONS = ("NOTE: stochastic depth (the reference's drop_path_rate=0.1) is NO
 
 
 def check_args(args):
-    """Refuse what is not implemented before any device or dataset is touched; everything else is main_linprobe's check."""
+    """Refuse what is not implemented before any device or dataset is touched; the checks behind are main_linprobe's shared ones."""
     if args.mode != "Finetune":
         raise SystemExit("--mode %s: this driver fine-tunes the encoder (--mode Finetune) or hands --mode LinearProbe to main_linprobe" % args.mode)
     if args.local_rank != -1:
@@ -38,12 +34,7 @@ def check_args(args):
     if args.fp16 or args.compute_dtype == "fp16":
         raise SystemExit("--fp16 --mode Finetune is not implemented here (IEEE half needs loss scaling around the fused SGD step): "
                          "use --compute_dtype bf16 (or fp32)")
-    args.mode = "LinearProbe"          # the remaining checks are shared
-    try:
-        args = main_linprobe.check_args(args)
-    finally:
-        args.mode = "Finetune"
-    return args
+    return main_linprobe.check_common(args)
 
 
 def build_model(args):
@@ -57,51 +48,10 @@ def main(args):
     if args.mode == "LinearProbe":
         return main_linprobe.main(args)
     args = check_args(args)
-    if not torch.cuda.is_available():
-        raise SystemExit("an MI355X is required: the encoder and the head are HIP kernels, there is no CPU path")
     from . import engine_finetune as engine
-    device = torch.device("cuda")
-    os.makedirs(args.output_dir, exist_ok=True)
-    log_path = os.path.join(args.output_dir, "log.txt")
-
-    def log(msg):
-        print(msg, flush=True)
-        with open(log_path, mode="a", encoding="utf-8") as f:
-            f.write(str(msg) + "\n")
-
-    random.seed(args.seed)
-    np.random.seed(args.seed)
-    torch.manual_seed(args.seed)
-    log(DEVIATIONS)
-    if args.synthetic:
-        log("WARNING: --synthetic: fine-tuning on RANDOM images (no dataset is read); the numbers are meaningless")
-    if args.stage == "train":
-        writer = None
-        try:
-            from torch.utils.tensorboard import SummaryWriter
-            writer = SummaryWriter(log_dir=os.path.join(args.output_dir, "logs"))
-        except Exception:   # tensorboard is optional
-            print("tensorboard not available: scalars go to log.txt only")
-        model = build_model(args)
-        if args.pretrained_path:
-            loaded = model.load_pretrained(args.pretrained_path)
-            log("loaded %d tensors from %s" % (len(loaded), args.pretrained_path))
-        model.to(device)
-        log("Training parameters %s" % args)
-        log("Total Parameter: \t%2.4fM" % (sum(p.numel() for _, p in model.finetune_parameters()) / 1e6))
-        engine.train(model, build_loader(args, "train"), build_loader(args, "val"), args, log=log, writer=writer)
-        if writer is not None:
-            writer.close()
-        del model
-    # test the best checkpoint (train.py:616-618: also after training)
-    path = engine.checkpoint_path(args, args.is_multilabel)
-    if not os.path.exists(path):
-        raise SystemExit("%s not found: --stage test scores the best checkpoint of a --stage train run with the same --name and --output_dir" % path)
-    model = build_model(args)
-    model.load_pretrained(path)
-    model.to(device)
-    model.eval()
-    return engine.test(model, build_loader(args, "test"), args, log=log)
+    return main_linprobe.run(args, engine, build_model, lambda model: sum(p.numel() for _, p in model.finetune_parameters()),
+                             [DEVIATIONS] + (["WARNING: --synthetic: fine-tuning on RANDOM images (no dataset is read); the numbers are meaningless"]
+                                             if args.synthetic else []), eval_mode=True)
 
 
 if __name__ == "__main__":

@@ -11,8 +11,8 @@ The reference's flag names are kept.  Added: --list_dir (the reference hard-code
 (--fp16 is --compute_dtype fp16; --fp16_opt_level is accepted and ignored), --pool {avg,cls}, --f32_residual, --synthetic,
 --synthetic_len, --num_workers, --print_freq.  `--stage train` trains, then tests the best checkpoint, as the reference does.
 
-NOT implemented here, and refused with a message: `--mode Finetune` (and with it stochastic depth), data-parallel probing
-(`--local_rank` other than -1); segmentation and detection fine-tuning have no counterpart in this project.
+NOT implemented here, and refused with a message: `--mode Finetune` (main_finetune's), data-parallel probing (`--local_rank` other
+than -1); segmentation and detection fine-tuning have no counterpart in this project.
 """
 import argparse
 import os
@@ -54,7 +54,7 @@ def get_args_parser():
     p.add_argument("--loss_scale", type=float, default=0, help="accepted and ignored: the head and its gradient are f32")
     p.add_argument("--dataset_path", type=str, default="")
     p.add_argument("--ratio", type=float, default=1)
-    p.add_argument("--mode", type=str, default="Finetune", help="LinearProbe; Finetune (the reference's default) is not implemented here")
+    p.add_argument("--mode", type=str, default="Finetune", help="LinearProbe (main_linprobe) or Finetune (main_finetune, the reference's default); each driver refuses the other's")
     # additions
     p.add_argument("--list_dir", type=str, default="", help="directory of train_list*.txt / val_list.txt / test_list.txt (default ./datasets/<task>)")
     p.add_argument("--compute_dtype", choices=["bf16", "fp16", "fp32"], default=None, help="format of the frozen encoder (default bf16)")
@@ -76,6 +76,11 @@ def check_args(args):
         raise SystemExit("--local_rank %d: data-parallel probing is not implemented here; run on one device (--local_rank -1)" % args.local_rank)
     if args.gradient_accumulation_steps != 1:
         raise SystemExit("--gradient_accumulation_steps other than 1 is not implemented here")
+    return check_common(args)
+
+
+def check_common(args):
+    """The checks and defaults that do not depend on `--mode` (main_finetune runs them behind its own refusals)."""
     if not 1 <= args.num_classes <= 64:
         raise SystemExit("--num_classes must lie in [1, 64]")
     if args.fp16 and args.compute_dtype not in (None, "fp16"):
@@ -114,11 +119,12 @@ def build_loader(args, split):
                       pin_memory=True)
 
 
-def main(args):
-    args = check_args(args)
+def run(args, engine, build_model, count_parameters, opening, eval_mode=False):
+    """`--stage train` (train, then test the best checkpoint, as the reference does) or `--stage test` of checked `args`, under `engine`
+    (engine_linprobe or engine_finetune).  `count_parameters(model)`: the elements being trained; `opening`: the first log lines;
+    `eval_mode`: put the model under test into eval() (a train_encoder model's forward reads `training`)."""
     if not torch.cuda.is_available():
         raise SystemExit("an MI355X is required: the encoder and the head are HIP kernels, there is no CPU path")
-    from . import engine_linprobe as engine
     device = torch.device("cuda")
     os.makedirs(args.output_dir, exist_ok=True)
     log_path = os.path.join(args.output_dir, "log.txt")
@@ -131,8 +137,8 @@ def main(args):
     random.seed(args.seed)
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
-    if args.synthetic:
-        log("WARNING: --synthetic: probing on RANDOM images (no dataset is read); the numbers are meaningless")
+    for line in opening:
+        log(line)
     if args.stage == "train":
         writer = None
         try:
@@ -146,7 +152,7 @@ def main(args):
             log("loaded %d tensors from %s" % (len(loaded), args.pretrained_path))
         model.to(device)
         log("Training parameters %s" % args)
-        log("Total Parameter: \t%2.4fM" % (sum(p.numel() for p in engine.head_parameters(model)) / 1e6))
+        log("Total Parameter: \t%2.4fM" % (count_parameters(model) / 1e6))
         engine.train(model, build_loader(args, "train"), build_loader(args, "val"), args, log=log, writer=writer)
         if writer is not None:
             writer.close()
@@ -158,7 +164,16 @@ def main(args):
     model = build_model(args)
     model.load_pretrained(path)
     model.to(device)
+    if eval_mode:
+        model.eval()
     return engine.test(model, build_loader(args, "test"), args, log=log)
+
+
+def main(args):
+    args = check_args(args)
+    from . import engine_linprobe as engine
+    return run(args, engine, build_model, lambda model: sum(p.numel() for p in engine.head_parameters(model)),
+               ["WARNING: --synthetic: probing on RANDOM images (no dataset is read); the numbers are meaningless"] if args.synthetic else [])
 
 
 if __name__ == "__main__":

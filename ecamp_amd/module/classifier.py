@@ -53,17 +53,12 @@ class ECAMPClassifier(nn.Module):
             self._noise = {key: (torch.arange(L, dtype=torch.float32, device=dev) / L).expand(B, L).contiguous()}
         return self._noise[key]
 
-    @torch.no_grad()
-    def forward_features(self, imgs, pool=None):
-        """imgs f32 [B, 3, R, R] -> f32 [B, D] (models_vit.py:78-97).  "avg": the mean of the patch tokens of the last block's output,
-        then `fc_norm` (global_pool=True; the encoder's own `norm` is not applied); "cls": `norm(x)[:, 0]`.  No gradient, and nothing
-        of the encoder depends on `training` (its blocks have no dropout; the reference's stochastic depth is not implemented), so
-        the modes, the Philox counter, the gradient arena and every `.grad` are left as they were."""
-        from .. import hip_ops as ops
-        from ..functions import NormFn, StemFn, VitBlockFn, f32_stream
-        pool = self.pool if pool is None else pool
-        if pool not in ("avg", "cls"):
-            raise ValueError("pool must be 'avg' or 'cls', got %r" % (pool,))
+    def _features(self, imgs, pool):
+        """The encoder body, imgs f32 [B, 3, R, R] -> f32 [B, D]: stem, blocks, then "avg": the mean of the patch tokens of the last
+        block's output and `fc_norm` (global_pool=True; the encoder's own `norm` is not applied); "cls": `norm(x)[:, 0]`
+        (models_vit.py:78-97).  Every patch is kept in place (identity noise, ratio 0: the Philox counter is not advanced).  Differentiable
+        down to the stem where gradients are enabled; under no_grad the same kernels in the same order, hence the same bits."""
+        from ..functions import NormFn, PoolNormFn, StemFn, VitBlockFn
         m = self.encoder
         A = m.prepare()
         imgs = imgs.to(A.device, dtype=torch.float32, non_blocking=True).contiguous()
@@ -76,17 +71,28 @@ class ECAMPClassifier(nn.Module):
             x = VitBlockFn.apply(x, blk, m, B, T, m.num_heads)
         if pool == "cls":
             return NormFn.apply(x, m.norm, m).view(B, T, -1)[:, 0].float().contiguous()
-        if m.f32_residual:
-            x = f32_stream(x)
-        return ops.pool_norm(x.view(B, T, -1), 1, T, self.fc_norm.weight.data, self.fc_norm.bias.data, self.fc_norm.eps)[1]
+        return PoolNormFn.apply(x, self.fc_norm.weight, self.fc_norm.bias, m, B, T, self.fc_norm.eps)
+
+    def forward_features(self, imgs, pool=None):
+        """`_features` forward only (`pool`: "avg" or "cls" instead of the model's own).  No gradient, and nothing of the encoder depends
+        on `training` (its blocks have no dropout; the reference's stochastic depth is not implemented), so the modes, the Philox
+        counter, the gradient arena and every `.grad` are left as they were."""
+        pool = self.pool if pool is None else pool
+        if pool not in ("avg", "cls"):
+            raise ValueError("pool must be 'avg' or 'cls', got %r" % (pool,))
+        with torch.no_grad():
+            return self._features(imgs, pool)
 
     def forward(self, imgs):
         """-> logits f32 [B, C].  Differentiable with respect to `head` only -- except on a `train_encoder=True` model in training mode
-        with gradients enabled, where the encoder stages run with their backwards (`_forward_finetune`)."""
+        with gradients enabled, where the encoder stages run with their backwards and fc_norm / head sit in `tail()`."""
         from ..functions import ClsHeadFn
         if self.train_encoder and self.training and torch.is_grad_enabled():
-            return self._forward_finetune(imgs)
-        return ClsHeadFn.apply(self.forward_features(imgs), self.head.weight, self.head.bias)
+            self.tail()
+            feat = self._features(imgs, self.pool)
+        else:
+            feat = self.forward_features(imgs)
+        return ClsHeadFn.apply(feat, self.head.weight, self.head.bias)
 
     def tail(self):
         """The flat buffer of `fc_norm` and `head` (train_encoder=True only; built where the parameters are, rebuilt after `.to()`)."""
@@ -100,27 +106,6 @@ class ECAMPClassifier(nn.Module):
         else:
             self._tail.attach_grads()
         return self._tail
-
-    def _forward_finetune(self, imgs):
-        """The differentiable twin of `forward_features` + head: the same kernels in the same order, every patch kept in place (identity
-        noise, ratio 0: the Philox counter is not advanced), so its logits are the forward-only path's bits."""
-        from ..functions import ClsHeadFn, NormFn, PoolNormFn, StemFn, VitBlockFn
-        m = self.encoder
-        A = m.prepare()
-        self.tail()
-        imgs = imgs.to(A.device, dtype=torch.float32, non_blocking=True).contiguous()
-        if imgs.dim() != 4 or imgs.shape[1:] != (3, m.img_size, m.img_size):
-            raise ValueError("imgs must be [B,3,%d,%d], got %s" % (m.img_size, m.img_size, tuple(imgs.shape)))
-        B = imgs.shape[0]
-        x, _, _, _, ids_keep = StemFn.apply(imgs, self._identity_noise(B, A.device), m, 0.0, m.cls_token)
-        T = ids_keep.shape[1] + 1
-        for blk in m.blocks:
-            x = VitBlockFn.apply(x, blk, m, B, T, m.num_heads)
-        if self.pool == "cls":
-            feat = NormFn.apply(x, m.norm, m).view(B, T, -1)[:, 0].float().contiguous()
-        else:
-            feat = PoolNormFn.apply(x, self.fc_norm.weight, self.fc_norm.bias, m, B, T, self.fc_norm.eps)
-        return ClsHeadFn.apply(feat, self.head.weight, self.head.bias)
 
     def finetune_parameters(self):
         """[(name, parameter)] of what `--mode Finetune` trains, named as the reference's flat layout names them: the encoder's cls_token,

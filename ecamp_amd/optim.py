@@ -33,24 +33,17 @@ def add_weight_decay(model, weight_decay=1e-5, skip_list=()):
     return [{"params": no_decay, "weight_decay": 0.0}, {"params": decay, "weight_decay": weight_decay}]
 
 
-class FusedAdamW(torch.optim.Optimizer):
-    """torch.optim.AdamW semantics (decoupled decay, bias correction, eps outside the sqrt) on the flat arenas.
-    `param_groups` behave as usual (lr schedulers write `group['lr']`); parameters whose gradient never arrives in
-    the reference (`_ecamp_unused`, the BERT pooler) are skipped entirely, exactly as torch skips `grad is None`."""
+class _FlatOptimizer(torch.optim.Optimizer):
+    """What the two fused optimizers share: at most 8 groups over ONE parameter arena (and, where `_TAIL_OK`, one arena.FlatTail), bound
+    on first use with a block table per space (arena.FlatSpace.block_table); pacing; `zero_grad` / `flush_grads`; and the checkpoint
+    packing of torch.optim, driven by three hooks: `_state_head`, `_state_views`, `_accept_state`."""
+    _TAIL_OK = False
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+    def __init__(self, params, defaults):
+        super().__init__(params, defaults)
         if len(self.param_groups) > 8:
-            raise ValueError("FusedAdamW supports at most 8 param groups")
-        b = {tuple(g["betas"]) for g in self.param_groups}
-        e = {g["eps"] for g in self.param_groups}
-        if len(b) != 1 or len(e) != 1:
-            raise ValueError("all groups must share betas and eps")
-        self._arena = None
-        self._step = 0
-        self._step_dev = None       # f32[1] on the device: the count of steps actually taken when a loss scaler decides skips there (`ctl`)
-        self.grad_scale = 1.0
-        self.bucketwise_steps = 0   # optimizer steps that ran bucket by bucket behind the gradient all-reduces
+            raise ValueError("%s supports at most 8 param groups" % type(self).__name__)
+        self._arena = self._tail = None
         self._inflight = collections.deque()
 
     def pace(self):
@@ -77,30 +70,91 @@ class FusedAdamW(torch.optim.Optimizer):
     def _bind(self):
         if self._arena is not None:
             return self._arena
-        arena = None
+        who = type(self).__name__
+        arena = tail = None
         for g in self.param_groups:
             for p in g["params"]:
-                a = getattr(p, "_ecamp_arena", None)
-                if a is None:
-                    raise RuntimeError("FusedAdamW: parameter is not in an ecamp_amd arena -- call model.prepare() (or run one "
-                                       "forward) after model.to('cuda') and before the first optimizer.step()")
-                arena = arena or a
-                if a is not arena:
-                    raise RuntimeError("FusedAdamW: parameters from different arenas")
-        nblk = arena.total // 64
-        table = torch.full((nblk,), 255, dtype=torch.uint8)
-        for gi, g in enumerate(self.param_groups):
+                a, t = getattr(p, "_ecamp_arena", None), getattr(p, "_ecamp_tail", None) if self._TAIL_OK else None
+                if a is None and t is None:
+                    raise RuntimeError(who + ": parameter is not in an ecamp_amd arena -- call model.prepare() (or run one forward) after "
+                                       "model.to('cuda') and before the first optimizer.step()")
+                if a is not None:
+                    arena = arena or a
+                    if a is not arena:
+                        raise RuntimeError(who + ": parameters from different arenas")
+                else:
+                    tail = tail or t
+                    if t is not tail:
+                        raise RuntimeError(who + ": parameters from different arenas (two tail buffers)")
+        self._bound(arena, tail)
+        self._table = arena.block_table(self.param_groups).to(arena.device)
+        self._tail_table = tail.block_table(self.param_groups).to(tail.device) if tail is not None else None
+        self._arena, self._tail = arena, tail
+        return arena
+
+    def zero_grad(self, set_to_none=False):
+        """p.grad stay views of the gradient arena / the tail buffer (set_to_none would detach them).  After the first step this is LAZY for
+        weight matrices: biases / LayerNorm / embedding gradients are zeroed now, a weight matrix keeps its old values until the next
+        backward pass OVERWRITES it (its first weight-gradient GEMM runs with beta = 0), or until `flush_grads()` / `step()` find
+        it untouched and zero it.  Read p.grad after backward, not between zero_grad() and backward.  ECAMP_LAZY_ZERO_GRAD=0 restores
+        the plain memset."""
+        self._bind().zero_grad()
+        if self._tail is not None:
+            self._tail.zero_grad()
+
+    def flush_grads(self):
+        """Make every p.grad consistent (zero the weight gradients no GEMM has written since zero_grad())."""
+        self._bind().flush_fresh()
+
+    # -- checkpoint format compatible with torch.optim (misc.py:295-338) ----------------------------------------
+    def state_dict(self):
+        self._bind()
+        head = self._state_head()
+        state, packed_groups, idx = {}, [], 0
+        for g in self.param_groups:
+            ids = []
             for p in g["params"]:
-                if getattr(p, "_ecamp_unused", False):
-                    continue
-                i = arena.index[id(p)]
-                o, n = arena.offsets[i], arena.sizes[i]
-                table[o // 64:(o + n + 63) // 64] = gi
-        self._table = table.to(arena.device)
+                if head is not None and not getattr(p, "_ecamp_unused", False):
+                    state[idx] = {**{k: v.clone() for k, v in head.items()}, **{k: v.clone() for k, v in self._state_views(p).items()}}
+                ids.append(idx)
+                idx += 1
+            packed_groups.append({**{k: v for k, v in g.items() if k != "params"}, "params": ids})
+        return {"state": state, "param_groups": packed_groups}
+
+    def load_state_dict(self, sd):
+        self._bind()
+        idx = 0
+        for g, sg in zip(self.param_groups, sd["param_groups"]):
+            for k, v in sg.items():
+                if k != "params":
+                    g[k] = v
+            for p in g["params"]:
+                st = sd["state"].get(idx, sd["state"].get(str(idx)))
+                if st is not None and self._accept_state(st):
+                    for k, v in self._state_views(p).items():
+                        v.copy_(st[k])
+                idx += 1
+
+
+class FusedAdamW(_FlatOptimizer):
+    """torch.optim.AdamW semantics (decoupled decay, bias correction, eps outside the sqrt) on the flat arenas.
+    `param_groups` behave as usual (lr schedulers write `group['lr']`); parameters whose gradient never arrives in
+    the reference (`_ecamp_unused`, the BERT pooler) are skipped entirely, exactly as torch skips `grad is None`."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        b = {tuple(g["betas"]) for g in self.param_groups}
+        e = {g["eps"] for g in self.param_groups}
+        if len(b) != 1 or len(e) != 1:
+            raise ValueError("all groups must share betas and eps")
+        self._step = 0
+        self._step_dev = None       # f32[1] on the device: the count of steps actually taken when a loss scaler decides skips there (`ctl`)
+        self.grad_scale = 1.0
+        self.bucketwise_steps = 0   # optimizer steps that ran bucket by bucket behind the gradient all-reduces
+
+    def _bound(self, arena, tail):
         self._m = ops.zeros((arena.total,), arena.device)
         self._v = ops.zeros((arena.total,), arena.device)
-        self._arena = arena
-        return arena
 
     @property
     def steps_taken(self):
@@ -169,67 +223,32 @@ class FusedAdamW(torch.optim.Optimizer):
         self.step(grad_sumsq=s)
         return s.sqrt().reshape(())
 
-    def zero_grad(self, set_to_none=False):
-        """p.grad stay views of the gradient arena (set_to_none would detach them).  After the first step this is LAZY for weight
-        matrices: biases / LayerNorm / embedding gradients are zeroed now, a weight matrix keeps its old values until the next
-        backward pass OVERWRITES it (its first weight-gradient GEMM runs with beta = 0), or until `flush_grads()` / `step()` find
-        it untouched and zero it.  Read p.grad after backward, not between zero_grad() and backward.  ECAMP_LAZY_ZERO_GRAD=0 restores
-        the plain memset."""
-        self._bind().zero_grad()
-
-    def flush_grads(self):
-        """Make every p.grad consistent (zero the weight gradients no GEMM has written since zero_grad())."""
-        self._bind().flush_fresh()
-
-    # -- checkpoint format compatible with torch.optim.AdamW (misc.py:295-338) ---------------------------------
-    def state_dict(self):
-        A = self._bind()
+    def _state_head(self):
+        """The leading entries of every parameter's state, None before the first step."""
         self._step = self.steps_taken
-        state, packed_groups, idx = {}, [], 0
-        for g in self.param_groups:
-            ids = []
-            for p in g["params"]:
-                i = A.index[id(p)]
-                o, n = A.offsets[i], A.sizes[i]
-                if self._step > 0 and not getattr(p, "_ecamp_unused", False):
-                    state[idx] = {"step": torch.tensor(float(self._step)), "exp_avg": self._m[o:o + n].view(p.shape).clone(),
-                                  "exp_avg_sq": self._v[o:o + n].view(p.shape).clone()}
-                ids.append(idx)
-                idx += 1
-            packed_groups.append({**{k: v for k, v in g.items() if k != "params"}, "params": ids})
-        return {"state": state, "param_groups": packed_groups}
+        return {"step": torch.tensor(float(self._step))} if self._step > 0 else None
 
-    def load_state_dict(self, sd):
-        A = self._bind()
-        idx = 0
-        for g, sg in zip(self.param_groups, sd["param_groups"]):
-            for k, v in sg.items():
-                if k != "params":
-                    g[k] = v
-            for p in g["params"]:
-                st = sd["state"].get(idx, sd["state"].get(str(idx)))
-                if st is not None:
-                    i = A.index[id(p)]
-                    o, n = A.offsets[i], A.sizes[i]
-                    self._m[o:o + n].view(p.shape).copy_(st["exp_avg"])
-                    self._v[o:o + n].view(p.shape).copy_(st["exp_avg_sq"])
-                    self._step, self._step_dev = int(float(st["step"])), None
-                idx += 1
+    def _state_views(self, p):
+        o, n = self._arena.span(p)
+        return {"exp_avg": self._m[o:o + n].view(p.shape), "exp_avg_sq": self._v[o:o + n].view(p.shape)}
+
+    def _accept_state(self, st):
+        self._step, self._step_dev = int(float(st["step"])), None
+        return True
 
 
-class FusedSGD(torch.optim.Optimizer):
+class FusedSGD(_FlatOptimizer):
     """torch.optim.SGD(momentum, dampening 0, no Nesterov, weight decay added to the gradient) behind
     torch.nn.utils.clip_grad_norm_(max_grad_norm) -- train.py:377-384,458 of the reference's Fine-tuning/Classification -- as fused HIP
     launches over the parameter arena: `ecamp_sumsq_grouped` leaves one partial sum of squares per workgroup, `ecamp_sgd_grouped` adds them
     in every workgroup, forms the clip coefficient and updates parameters, momentum and the 16-bit shadows.  Parameters outside the arena
     must sit in ONE arena.FlatTail (ECAMPClassifier's fc_norm and head): a second pair of launches updates them with the same partials,
     hence the same norm and coefficient.  Nothing is read back: `last_norm` is the global gradient norm as a device scalar.
-    max_grad_norm <= 0: no clipping.  Binding, block table, `zero_grad` / `flush_grads` / `pace` are FusedAdamW's."""
+    max_grad_norm <= 0: no clipping."""
+    _TAIL_OK = True
 
     def __init__(self, params, lr=1e-3, momentum=0.9, weight_decay=0.0, max_grad_norm=0.0):
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=0, weight_decay=weight_decay, nesterov=False))
-        if len(self.param_groups) > 8:
-            raise ValueError("FusedSGD supports at most 8 param groups")
         if len({g["momentum"] for g in self.param_groups}) != 1:
             raise ValueError("all groups must share momentum")
         if any(g.get("dampening", 0) != 0 or g.get("nesterov", False) for g in self.param_groups):
@@ -237,58 +256,17 @@ class FusedSGD(torch.optim.Optimizer):
         self.max_grad_norm = float(max_grad_norm)
         self.grad_scale = 1.0
         self.last_norm = None       # f32[1] on the device after a step: the global norm of the (un-scaled) gradients before clipping
-        self._arena = self._tail = None
         self._steps = 0
-        self._inflight = collections.deque()
 
-    pace = FusedAdamW.pace
-
-    @property
-    def arena(self):
-        return self._bind()
-
-    def _bind(self):
-        if self._arena is not None:
-            return self._arena
-        arena = tail = None
-        for g in self.param_groups:
-            for p in g["params"]:
-                a, t = getattr(p, "_ecamp_arena", None), getattr(p, "_ecamp_tail", None)
-                if a is None and t is None:
-                    raise RuntimeError("FusedSGD: parameter is not in an ecamp_amd arena -- call model.prepare() (or run one forward) after "
-                                       "model.to('cuda') and before the first optimizer.step()")
-                if a is not None:
-                    arena = arena or a
-                    if a is not arena:
-                        raise RuntimeError("FusedSGD: parameters from different arenas")
-                else:
-                    tail = tail or t
-                    if t is not tail:
-                        raise RuntimeError("FusedSGD: parameters from different arenas (two tail buffers)")
+    def _bound(self, arena, tail):
         if arena is None:
             raise RuntimeError("FusedSGD: no parameter of a model's arena among the groups (the tail buffer alone is not supported)")
         if arena.reducer is not None:
             raise RuntimeError("FusedSGD: data-parallel fine-tuning is not implemented")
-
-        def table(space):
-            t = torch.full((space.total // 64,), 255, dtype=torch.uint8)
-            for gi, g in enumerate(self.param_groups):
-                for p in g["params"]:
-                    if id(p) not in space.index or getattr(p, "_ecamp_unused", False):
-                        continue
-                    i = space.index[id(p)]
-                    o, n = space.offsets[i], space.sizes[i]
-                    t[o // 64:(o + n + 63) // 64] = gi
-            return t.to(space.device)
-
-        self._table = table(arena)
         self._buf = ops.zeros((arena.total,), arena.device)
-        self._tail_table = table(tail) if tail is not None else None
         self._slots = (ops.sumsq_grouped_slots(arena.total), ops.sumsq_grouped_slots(tail.total) if tail is not None else 0)
         self._partials = ops.zeros((sum(self._slots),), arena.device)
         self.last_norm = ops.zeros((1,), arena.device)
-        self._arena, self._tail = arena, tail
-        return arena
 
     @torch.no_grad()
     def step(self, closure=None, ctl=None):
@@ -313,49 +291,16 @@ class FusedSGD(torch.optim.Optimizer):
         self.pace()
         return loss
 
-    def zero_grad(self, set_to_none=False):
-        """p.grad stay views of the gradient arena / the tail buffer (see FusedAdamW.zero_grad: lazy for the weight matrices)."""
-        self._bind().zero_grad()
-        if self._tail is not None:
-            self._tail.zero_grad()
+    def _state_head(self):
+        return {} if self._steps > 0 else None
 
-    def flush_grads(self):
-        self._bind().flush_fresh()
+    def _state_views(self, p):
+        space, buf = (self._arena, self._buf) if id(p) in self._arena.index else (self._tail, self._tail.flat_buf)
+        o, n = space.span(p)
+        return {"momentum_buffer": buf[o:o + n].view(p.shape)}
 
-    def _slot(self, p):
-        """-> (momentum buffer, offset, size) of parameter p."""
-        if id(p) in self._arena.index:
-            i = self._arena.index[id(p)]
-            return self._buf, self._arena.offsets[i], self._arena.sizes[i]
-        i = self._tail.index[id(p)]
-        return self._tail.flat_buf, self._tail.offsets[i], self._tail.sizes[i]
-
-    # -- checkpoint format compatible with torch.optim.SGD ------------------------------------------------------
-    def state_dict(self):
-        self._bind()
-        state, packed_groups, idx = {}, [], 0
-        for g in self.param_groups:
-            ids = []
-            for p in g["params"]:
-                if self._steps > 0 and not getattr(p, "_ecamp_unused", False):
-                    buf, o, n = self._slot(p)
-                    state[idx] = {"momentum_buffer": buf[o:o + n].view(p.shape).clone()}
-                ids.append(idx)
-                idx += 1
-            packed_groups.append({**{k: v for k, v in g.items() if k != "params"}, "params": ids})
-        return {"state": state, "param_groups": packed_groups}
-
-    def load_state_dict(self, sd):
-        self._bind()
-        idx = 0
-        for g, sg in zip(self.param_groups, sd["param_groups"]):
-            for k, v in sg.items():
-                if k != "params":
-                    g[k] = v
-            for p in g["params"]:
-                st = sd["state"].get(idx, sd["state"].get(str(idx)))
-                if st is not None and st.get("momentum_buffer") is not None:
-                    buf, o, n = self._slot(p)
-                    buf[o:o + n].view(p.shape).copy_(st["momentum_buffer"])
-                    self._steps = max(self._steps, 1)
-                idx += 1
+    def _accept_state(self, st):
+        if st.get("momentum_buffer") is None:   # (torch.optim.SGD keeps None until its first step)
+            return False
+        self._steps = max(self._steps, 1)
+        return True

@@ -334,6 +334,30 @@ def test_the_default_is_still_the_probe_and_eval_runs_the_forward_only_path(dev)
     assert float(ft.encoder.arena.flat_g.abs().sum()) == 0       # nothing ran backward
 
 
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "f32"])
+@pytest.mark.parametrize("f32_residual", [False, True], ids=["res16", "res32"])
+@pytest.mark.parametrize("pool", ["avg", "cls"])
+def test_forward_only_bits_equal_the_differentiable_path_bits(dev, pool, f32_residual, dtype):
+    """One encoder body (ECAMPClassifier._features) with and without gradients: the logits of the training-mode forward are the bits of
+    `forward_features` through the head.  vit_tiny_patch16 at 32 x 32 pixels: four patches, five tokens, B = 3."""
+    from ecamp_amd import hip_ops as ops
+    from ecamp_amd.module.classifier import build_classifier
+    torch.manual_seed(0)
+    clf = build_classifier("vit_tiny_patch16", C, True, img_size=32, pool=pool, train_encoder=True, compute_dtype=dtype, f32_residual=f32_residual)
+    with torch.no_grad():
+        for k, v in _tail_values().items():
+            clf.get_parameter(k).copy_(v)
+    clf.to(dev).train()
+    imgs = torch.randn(3, 3, 32, 32, generator=torch.Generator().manual_seed(11))
+    a = clf(imgs)
+    assert a.requires_grad and a.grad_fn is not None
+    feats = clf.forward_features(imgs)
+    assert not feats.requires_grad and feats.shape == (3, 192)
+    b = ops.cls_head_fwd(feats, clf.head.weight.data, clf.head.bias.data)
+    assert torch.isfinite(b).all() and float(b.abs().max()) > 0
+    assert torch.equal(a.detach(), b)
+
+
 # ---------------------------------------------------------------------------------------------------------------- the driver
 def test_driver_trains_writes_the_flat_checkpoint_and_tests_it(dev, tmp_path, monkeypatch):
     from ecamp_amd import main_finetune
