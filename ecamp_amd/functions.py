@@ -6,6 +6,7 @@ launches an ATen compute kernel for them.
 Reference restated per stage (paths relative to ECAMP/Pre-training/):
   StemFn        model_ecamp.py:318 (bicubic), :218-230 (patch-embed, masking, cls)      K1-K4
   VitBlockFn    timm 0.4.12 Block (call sites model_ecamp.py:66-68,80-82,233-234,254-255) K5-K8
+                (+ its DropPath for fine-tuning: Fine-tuning/Classification/train.py:127, csrc/droppath.hip)
   NormFn        model_ecamp.py:69,235                                                    K5
   DecStemFn     model_ecamp.py:242-251                                                   K9,K10
   ImgLossFn     model_ecamp.py:256-262 (norm, pred), :153-165,:28-46,:196-215,:276-300   K11-K13
@@ -219,26 +220,45 @@ class StemFn(torch.autograd.Function):
 # =============================================================================================
 class VitBlockFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, blk, m, B, T, heads):
+    def forward(ctx, x, blk, m, B, T, heads, drop_path=0.0):
         """One body for both residual formats.  On the f32 residual stream (ECAMP(f32_residual=True)) x, x1 and x2 are f32: the
         LayerNorms read them and write 16-bit GEMM inputs, proj / fc2 store f32 (_vit_linear), and the result crosses the autograd edge
-        as a carrier."""
+        as a carrier.
+        `drop_path` > 0 (fine-tuning only, module/classifier.py): stochastic depth at this block's rate, timm Block's
+        `x + drop_path(attn(norm1(x)))` / `x + drop_path(mlp(norm2(x)))` -- proj and fc2 run without their residual epilogue and
+        ecamp_drop_path_fwd joins the branch to the stream per sample, under a Philox pair of its own per branch (attention first).
+        The branch output's buffer becomes the sum where the formats agree; only (p, seed, offset) are kept for the backward."""
         if m.f32_residual:
             x = f32_stream(x)
         D = x.shape[1]
         hd = D // heads
+        p = float(drop_path)
+        if p > 0 and m.fp8_forward:
+            raise RuntimeError("VitBlockFn: stochastic depth is not implemented beside the fp8 forward (fine-tuning does not use fp8_forward)")
         h, _, mean1, rstd1, h8 = _ln_fwd(m, x, blk.norm1, blk.attn.qkv.weight)
         qkv = _vit_linear(m, h, blk.attn.qkv, x8=h8)
         st = (T * 3 * D, 3 * D, hd)
         flat = qkv.view(-1)
         a, lse = ops.attn_fwd(flat, flat[D:], flat[2 * D:], B, heads, T, T, hd, st, st, st, hd ** -0.5)
         a = a.view(B * T, D)
-        x1 = _vit_linear(m, a, blk.attn.proj, residual=x)
+        rng1 = rng2 = None
+        if p > 0:
+            rng1 = m.next_rng()
+            y1 = _vit_linear(m, a, blk.attn.proj)
+            x1 = ops.drop_path_fwd(x, y1, B, T, p, rng1[0], rng1[1], out=y1 if y1.dtype == x.dtype else None)
+        else:
+            x1 = _vit_linear(m, a, blk.attn.proj, residual=x)
         h2, _, mean2, rstd2, h28 = _ln_fwd(m, x1, blk.norm2, blk.mlp.fc1.weight)
         u, pre, u8 = _vit_linear(m, h2, blk.mlp.fc1, x8=h28, next_w=blk.mlp.fc2.weight, act=m.gelu_act, save_pre=True)   # (act 2: `pre` holds gelu')
-        x2 = _vit_linear(m, u, blk.mlp.fc2, x8=u8, residual=x1)
+        if p > 0:
+            rng2 = m.next_rng()
+            y2 = _vit_linear(m, u, blk.mlp.fc2, x8=u8)
+            x2 = ops.drop_path_fwd(x1, y2, B, T, p, rng2[0], rng2[1], out=y2 if y2.dtype == x1.dtype else None)
+        else:
+            x2 = _vit_linear(m, u, blk.mlp.fc2, x8=u8, residual=x1)
         ctx.s = (x, mean1, rstd1, h, qkv, a, lse, x1, mean2, rstd2, h2, pre, u)
         ctx.cfg = (blk, m, B, T, heads)
+        ctx.drop = (p, rng1, rng2)
         return f32_carrier(x2, m.compute_dtype) if m.f32_residual else x2
 
     @staticmethod
@@ -254,20 +274,25 @@ class VitBlockFn(torch.autograd.Function):
         with _wgrad_block(A):
             dx = VitBlockFn._backward_body(ctx, dx2, A, G, D, hd, fc1, fc2, proj, qk)
         ctx.s = None
-        return (dx,) + _none(5)
+        return (dx,) + _none(6)   # (a call without `drop_path` has six inputs: autograd drops the spare trailing None)
 
     @staticmethod
     def _backward_body(ctx, dx2, A, G, D, hd, fc1, fc2, proj, qk):
         x, mean1, rstd1, h, qkv, a, lse, x1, mean2, rstd2, h2, pre, u = ctx.s
         blk, m, B, T, heads = ctx.cfg
-        _wgrad(A, dx2, u, fc2.weight, gb=G(fc2.bias))
-        dpre = ops.linear_dgrad(dx2, A.w(fc2.weight), gmul=pre, gmul_is_grad=m.gelu_act == 2)
+        p, rng1, rng2 = ctx.drop
+        # stochastic depth: the branch sees s_b * dx2 (weight, bias and data gradients of fc2), the residual path dx2 itself; the scaled
+        # tensor is an input of the block's grouped weight-gradient launch, which holds it as it holds dx2 without stochastic depth
+        dy2 = ops.drop_path_bwd(dx2, B, T, p, rng2[0], rng2[1]) if p > 0 else dx2
+        _wgrad(A, dy2, u, fc2.weight, gb=G(fc2.bias))
+        dpre = ops.linear_dgrad(dy2, A.w(fc2.weight), gmul=pre, gmul_is_grad=m.gelu_act == 2)
         _wgrad(A, dpre, h2, fc1.weight, gb=G(fc1.bias))
         dh2 = ops.linear_dgrad(dpre, A.w(fc1.weight))
         dx1 = _ln_bwd(dh2, x1, mean2, rstd2, blk.norm2.weight.data, G(blk.norm2.weight), G(blk.norm2.bias), dres=dx2)
         A.ready(fc2.weight, fc2.bias, fc1.weight, fc1.bias, blk.norm2.weight, blk.norm2.bias)
-        _wgrad(A, dx1, a, proj.weight, gb=G(proj.bias))
-        da = ops.linear_dgrad(dx1, A.w(proj.weight))
+        dy1 = ops.drop_path_bwd(dx1, B, T, p, rng1[0], rng1[1]) if p > 0 else dx1
+        _wgrad(A, dy1, a, proj.weight, gb=G(proj.bias))
+        da = ops.linear_dgrad(dy1, A.w(proj.weight))
         dqkv = torch.empty_like(qkv)
         st = (T * 3 * D, 3 * D, hd)
         f, df = qkv.view(-1), dqkv.view(-1)

@@ -419,6 +419,30 @@ def dropout_mask(shape, device, p, seed, offset):
     return out
 
 
+def drop_path_fwd(res, y, B, T, p, seed, offset, out=None):
+    """Stochastic depth (timm DropPath, scale_by_keep): out[b] = res[b] + s_b * y[b] over [B*T, D] rows, s_b = 0 or 1 / (1 - p); sample b is
+    kept iff dropout_mask((B,), dev, p, seed, offset)[b].  res and y 16-bit, both f32, or res f32 with a 16-bit y; `out` (res's dtype) is
+    allocated unless given, and may be `y` itself when the dtypes agree."""
+    _chk(res, y, out)
+    M, D = res.shape
+    assert M == B * T and y.shape == res.shape and res.is_contiguous() and y.is_contiguous()
+    if out is None:
+        out = torch.empty_like(res)
+    assert out.shape == res.shape and out.dtype == res.dtype and out.is_contiguous()
+    call("ecamp_drop_path_fwd", ptr(res), ptr(y), ptr(out), B, T, D, float(p), seed, offset, code(res.dtype), code(y.dtype), stream())
+    return out
+
+
+def drop_path_bwd(dout, B, T, p, seed, offset):
+    """Gradient of drop_path_fwd with respect to y: s_b * dout[b] (a new tensor; the gradient of res is dout itself)."""
+    _chk(dout)
+    M, D = dout.shape
+    assert M == B * T and dout.is_contiguous()
+    dy = torch.empty_like(dout)
+    call("ecamp_drop_path_bwd", ptr(dout), ptr(dy), B, T, D, float(p), seed, offset, code(dout.dtype), stream())
+    return dy
+
+
 def uniform(shape, device, seed, offset):
     out = torch.empty(shape, device=device, dtype=torch.float32)
     call("ecamp_uniform", ptr(out), out.numel(), seed, offset, stream())

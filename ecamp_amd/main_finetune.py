@@ -4,12 +4,13 @@ ECAMP/Fine-tuning/Classification in its default `--mode Finetune` (run_ft.sh), o
     python -m ecamp_amd.main_finetune --name ecamp --stage train --model vit_base_patch16 --task ChestX-ray14 --num_classes 14 \
         --pretrained_path <pre-training checkpoint> --dataset_path <images> --list_dir <directory of the list files> \
         --output_dir output/ChestX-ray14/1/ --data_volume 1 --num_steps 3000 --eval_batch_size 512 --img_size 224 \
-        --learning_rate 3e-2 --warmup_steps 50 --train_batch_size 96 --compute_dtype bf16
+        --learning_rate 3e-2 --warmup_steps 50 --train_batch_size 96 --compute_dtype bf16 --drop_path_rate 0.1
     python -m ecamp_amd.main_finetune --name ecamp --stage test ... (scores <output_dir>/<name>_best{auc,acc}_checkpoint.bin)
 
 The flags are main_linprobe's (the reference's names and its additions); `--mode` defaults to Finetune, and `--mode LinearProbe` hands
-over to main_linprobe.  Two deviations from the reference, stated in the first log line of every run: stochastic depth (its
-drop_path_rate=0.1) is not applied, and `pos_embed` is held at the fixed sin-cos table (timm's is a trained parameter).
+over to main_linprobe.  `--drop_path_rate R` applies stochastic depth at rates linear over the blocks from 0 to R (timm's rule); the
+reference hard-codes R = 0.1 (train.py:127), the default here is 0.0.  The first log line of every run states what deviates from the
+reference: stochastic depth when it is off, and `pos_embed`, which is held at the fixed sin-cos table (timm's is a trained parameter).
 
 NOT implemented, and refused with a message before any device work: data-parallel fine-tuning (`--local_rank` other than -1),
 `--gradient_accumulation_steps` other than 1, and `--fp16` (IEEE half with loss scaling): use `--compute_dtype bf16`.
@@ -23,6 +24,15 @@ DEVIATIONS = ("NOTE: stochastic depth (the reference's drop_path_rate=0.1) is NO
               "(the reference trains it)")
 
 
+def opening_line(args):
+    """The first log line of a run, a function of `args` alone: what deviates from the reference's recipe."""
+    rate = float(getattr(args, "drop_path_rate", 0.0))
+    if rate == 0:
+        return DEVIATIONS
+    return ("NOTE: stochastic depth IS applied at drop_path_rate=%g, rising linearly over the blocks from 0 (the reference's is 0.1), and pos_embed is "
+            "held fixed at the sin-cos table (the reference trains it)" % rate)
+
+
 def check_args(args):
     """Refuse what is not implemented before any device or dataset is touched; the checks behind are main_linprobe's shared ones."""
     if args.mode != "Finetune":
@@ -34,6 +44,9 @@ def check_args(args):
     if args.fp16 or args.compute_dtype == "fp16":
         raise SystemExit("--fp16 --mode Finetune is not implemented here (IEEE half needs loss scaling around the fused SGD step): "
                          "use --compute_dtype bf16 (or fp32)")
+    rate = float(getattr(args, "drop_path_rate", 0.0))
+    if not 0.0 <= rate < 1.0:
+        raise SystemExit("--drop_path_rate %g must lie in [0, 1)" % rate)
     return main_linprobe.check_common(args)
 
 
@@ -41,7 +54,7 @@ def build_model(args):
     from .module.classifier import build_classifier
     dtype = {"bf16": torch.bfloat16, "fp32": torch.float32}[args.compute_dtype]
     return build_classifier(args.model, args.num_classes, args.is_multilabel, img_size=args.img_size, pool=args.pool, train_encoder=True,
-                            compute_dtype=dtype, f32_residual=args.f32_residual)
+                            drop_path_rate=getattr(args, "drop_path_rate", 0.0), compute_dtype=dtype, f32_residual=args.f32_residual)
 
 
 def main(args):
@@ -50,7 +63,7 @@ def main(args):
     args = check_args(args)
     from . import engine_finetune as engine
     return main_linprobe.run(args, engine, build_model, lambda model: sum(p.numel() for _, p in model.finetune_parameters()),
-                             [DEVIATIONS] + (["WARNING: --synthetic: fine-tuning on RANDOM images (no dataset is read); the numbers are meaningless"]
+                             [opening_line(args)] + (["WARNING: --synthetic: fine-tuning on RANDOM images (no dataset is read); the numbers are meaningless"]
                                              if args.synthetic else []), eval_mode=True)
 
 

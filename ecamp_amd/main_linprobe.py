@@ -9,7 +9,8 @@ ECAMP/Fine-tuning/Classification (run_lp.sh), on one MI355X:
 
 The reference's flag names are kept.  Added: --list_dir (the reference hard-codes ./datasets/<task>), --compute_dtype {bf16,fp16,fp32}
 (--fp16 is --compute_dtype fp16; --fp16_opt_level is accepted and ignored), --pool {avg,cls}, --f32_residual, --synthetic,
---synthetic_len, --num_workers, --print_freq.  `--stage train` trains, then tests the best checkpoint, as the reference does.
+--synthetic_len, --num_workers, --print_freq, --drop_path_rate (main_finetune's stochastic depth; refused here unless 0: the frozen
+encoder of the probe is deterministic).  `--stage train` trains, then tests the best checkpoint, as the reference does.
 
 NOT implemented here, and refused with a message: `--mode Finetune` (main_finetune's), data-parallel probing (`--local_rank` other
 than -1); segmentation and detection fine-tuning have no counterpart in this project.
@@ -64,6 +65,9 @@ def get_args_parser():
     p.add_argument("--synthetic_len", default=64, type=int, help="samples of the synthetic training set (validation and test: half)")
     p.add_argument("--num_workers", default=8, type=int)
     p.add_argument("--print_freq", default=50, type=int, help="steps between two reads of the training loss")
+    p.add_argument("--drop_path_rate", default=0.0, type=float,
+                   help="--mode Finetune: stochastic depth, the rate of the last block (linear over the blocks from 0); the reference hard-codes 0.1 "
+                        "(train.py:127), the default here is 0.0: none")
     return p
 
 
@@ -72,6 +76,9 @@ def check_args(args):
     if args.mode != "LinearProbe":
         raise SystemExit("--mode %s is not implemented here: this driver trains the linear probe only (--mode LinearProbe); fine-tuning the "
                          "encoder needs stochastic depth, SGD and clipping over the parameter arena and an unmasked encoder backward" % args.mode)
+    if getattr(args, "drop_path_rate", 0.0) != 0:
+        raise SystemExit("--drop_path_rate %g with --mode LinearProbe: the probe's encoder is frozen and deterministic, stochastic depth belongs to "
+                         "--mode Finetune (main_finetune)" % args.drop_path_rate)
     if args.local_rank != -1:
         raise SystemExit("--local_rank %d: data-parallel probing is not implemented here; run on one device (--local_rank -1)" % args.local_rank)
     if args.gradient_accumulation_steps != 1:

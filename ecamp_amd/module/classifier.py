@@ -9,7 +9,12 @@ plain f32 parameters of this module, outside the wrapped model's arena and state
 `ECAMPClassifier(..., train_encoder=True)` is the `--mode Finetune` share (train.py:144-166): in training mode `forward` runs the same
 stages with their hand-written backwards (StemFn, VitBlockFn, then PoolNormFn or NormFn) so that the loss reaches every encoder
 parameter; `fc_norm` and `head` then live in a small flat buffer of their own (arena.FlatTail) which the fused SGD step updates beside
-the arena.  Stochastic depth (the reference's drop_path_rate=0.1) is not applied, and `pos_embed` stays the fixed sin-cos table.
+the arena.  `pos_embed` stays the fixed sin-cos table.
+
+Stochastic depth: `drop_path_rate` (default 0.0: none; the reference builds its ViT with drop_path_rate=0.1, train.py:127) gives block i
+the rate linspace(0, rate, depth)[i], timm's rule, and the differentiable training path hands each block its rate (VitBlockFn: timm
+DropPath per sample on both residual branches, csrc/droppath.hip).  Forward-only runs -- eval(), no_grad, `forward_features` -- apply
+none, as timm does outside training: they compute the bits of a rate-0 model and leave the Philox counter alone.
 """
 import os
 
@@ -24,8 +29,13 @@ def _is_encoder_key(k):
 
 
 class ECAMPClassifier(nn.Module):
-    def __init__(self, encoder, num_classes, multilabel=True, pool="avg", train_encoder=False):
+    def __init__(self, encoder, num_classes, multilabel=True, pool="avg", train_encoder=False, drop_path_rate=0.0):
         super().__init__()
+        rate = float(drop_path_rate)
+        if not 0.0 <= rate < 1.0:
+            raise ValueError("drop_path_rate must lie in [0, 1), got %r" % (drop_path_rate,))
+        if rate > 0 and getattr(encoder, "fp8_forward", False):
+            raise ValueError("drop_path_rate > 0 is not implemented beside fp8_forward (fine-tuning does not use the fp8 forward)")
         if pool not in ("avg", "cls"):
             raise ValueError("pool must be 'avg' (the reference's global_pool=True) or 'cls', got %r" % (pool,))
         if not 1 <= int(num_classes) <= 64:
@@ -42,6 +52,10 @@ class ECAMPClassifier(nn.Module):
         self._noise = {}
         self.train_encoder = bool(train_encoder)   # False: the linear probe, exactly; True: `forward` is differentiable down to the stem
         self._tail = None          # arena.FlatTail over fc_norm and head (train_encoder only; built on the device, on first use)
+        # stochastic depth per block: timm's torch.linspace(0, rate, depth), each value rounded to float32 once (the C ABI takes `float`);
+        # block 0 always has rate 0 and keeps the fused residual epilogues
+        self.drop_path_rate = rate
+        self.drop_path_rates = [float(v) for v in torch.linspace(0, rate, len(encoder.blocks), dtype=torch.float32).tolist()]
 
     # ---------------------------------------------------------------------------------------------
     def _identity_noise(self, B, dev):
@@ -53,11 +67,13 @@ class ECAMPClassifier(nn.Module):
             self._noise = {key: (torch.arange(L, dtype=torch.float32, device=dev) / L).expand(B, L).contiguous()}
         return self._noise[key]
 
-    def _features(self, imgs, pool):
+    def _features(self, imgs, pool, drop_path=False):
         """The encoder body, imgs f32 [B, 3, R, R] -> f32 [B, D]: stem, blocks, then "avg": the mean of the patch tokens of the last
         block's output and `fc_norm` (global_pool=True; the encoder's own `norm` is not applied); "cls": `norm(x)[:, 0]`
         (models_vit.py:78-97).  Every patch is kept in place (identity noise, ratio 0: the Philox counter is not advanced).  Differentiable
-        down to the stem where gradients are enabled; under no_grad the same kernels in the same order, hence the same bits."""
+        down to the stem where gradients are enabled; under no_grad the same kernels in the same order, hence the same bits.
+        `drop_path`: hand every block its stochastic-depth rate (`forward` does on the differentiable training path only; a block of rate
+        0 runs the body it always ran, and only blocks of a rate above 0 draw from the Philox counter, two pairs each)."""
         from ..functions import NormFn, PoolNormFn, StemFn, VitBlockFn
         m = self.encoder
         A = m.prepare()
@@ -67,16 +83,19 @@ class ECAMPClassifier(nn.Module):
         B = imgs.shape[0]
         x, _, _, _, ids_keep = StemFn.apply(imgs, self._identity_noise(B, A.device), m, 0.0, m.cls_token)
         T = ids_keep.shape[1] + 1
-        for blk in m.blocks:
-            x = VitBlockFn.apply(x, blk, m, B, T, m.num_heads)
+        for i, blk in enumerate(m.blocks):
+            if drop_path and self.drop_path_rates[i] > 0:
+                x = VitBlockFn.apply(x, blk, m, B, T, m.num_heads, self.drop_path_rates[i])
+            else:
+                x = VitBlockFn.apply(x, blk, m, B, T, m.num_heads)
         if pool == "cls":
             return NormFn.apply(x, m.norm, m).view(B, T, -1)[:, 0].float().contiguous()
         return PoolNormFn.apply(x, self.fc_norm.weight, self.fc_norm.bias, m, B, T, self.fc_norm.eps)
 
     def forward_features(self, imgs, pool=None):
-        """`_features` forward only (`pool`: "avg" or "cls" instead of the model's own).  No gradient, and nothing of the encoder depends
-        on `training` (its blocks have no dropout; the reference's stochastic depth is not implemented), so the modes, the Philox
-        counter, the gradient arena and every `.grad` are left as they were."""
+        """`_features` forward only (`pool`: "avg" or "cls" instead of the model's own).  No gradient, and no stochastic depth whatever
+        `training` says (timm applies DropPath in training only; the blocks have no other dropout): the bits are those of a
+        drop_path_rate=0 model, and the modes, the Philox counter, the gradient arena and every `.grad` are left as they were."""
         pool = self.pool if pool is None else pool
         if pool not in ("avg", "cls"):
             raise ValueError("pool must be 'avg' or 'cls', got %r" % (pool,))
@@ -85,11 +104,12 @@ class ECAMPClassifier(nn.Module):
 
     def forward(self, imgs):
         """-> logits f32 [B, C].  Differentiable with respect to `head` only -- except on a `train_encoder=True` model in training mode
-        with gradients enabled, where the encoder stages run with their backwards and fc_norm / head sit in `tail()`."""
+        with gradients enabled, where the encoder stages run with their backwards and fc_norm / head sit in `tail()`.  That path alone
+        depends on `training`: it is where stochastic depth (drop_path_rate > 0) is applied."""
         from ..functions import ClsHeadFn
         if self.train_encoder and self.training and torch.is_grad_enabled():
             self.tail()
-            feat = self._features(imgs, self.pool)
+            feat = self._features(imgs, self.pool, drop_path=self.drop_path_rate > 0)
         else:
             feat = self.forward_features(imgs)
         return ClsHeadFn.apply(feat, self.head.weight, self.head.bias)
@@ -200,17 +220,20 @@ _ENCODERS = {"vit_tiny_patch16": dict(embed_dim=192, depth=12, num_heads=3), "vi
              "vit_large_patch16": dict(embed_dim=1024, depth=24, num_heads=16)}
 
 
-def build_classifier(model_name, num_classes, multilabel, img_size=224, pool="avg", train_encoder=False, **kwargs):
+def build_classifier(model_name, num_classes, multilabel, img_size=224, pool="avg", train_encoder=False, drop_path_rate=0.0, **kwargs):
     """The reference's `--model` name -> an ECAMPClassifier around an ECAMP with that encoder at `img_size` (decoder and report side
-    as the pre-training factories build them, so a pre-training checkpoint's encoder keys fit)."""
+    as the pre-training factories build them, so a pre-training checkpoint's encoder keys fit).  `drop_path_rate`: the stochastic-depth
+    rate of the last block (ECAMPClassifier; the reference's is 0.1, train.py:127)."""
     from functools import partial
 
     from .bert_config import BertConfig
     from .model_ecamp import ECAMP
     if model_name not in _ENCODERS:
         raise ValueError("--model must be one of %s, got %r" % (", ".join(sorted(_ENCODERS)), model_name))
+    if not 0.0 <= float(drop_path_rate) < 1.0:
+        raise ValueError("drop_path_rate must lie in [0, 1), got %r" % (drop_path_rate,))
     if model_name == "vit_tiny_patch16":
         kwargs.setdefault("bert_config", BertConfig(num_hidden_layers=2))
     enc = ECAMP(img_size=img_size, patch_size=16, in_chans=3, decoder_embed_dim=512, decoder_depth=4, decoder_num_heads=16, mlp_ratio=4,
                 norm_layer=partial(nn.LayerNorm, eps=1e-6), **_ENCODERS[model_name], **kwargs)
-    return ECAMPClassifier(enc, num_classes, multilabel=multilabel, pool=pool, train_encoder=train_encoder)
+    return ECAMPClassifier(enc, num_classes, multilabel=multilabel, pool=pool, train_encoder=train_encoder, drop_path_rate=drop_path_rate)

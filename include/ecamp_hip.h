@@ -29,8 +29,9 @@ typedef struct ihipStream_t* ecampStream_t; /* == hipStream_t */
  * ecamp_layernorm_fwd_x32, ecamp_layernorm_bwd_z32, ecamp_assemble_tokens_x32, ecamp_unshuffle_fwd_x32).  ecamp_abi_version()
  * returns the value the library was BUILT with; a consumer compares it with the header it was compiled against -- the Python binding
  * (ecamp_amd/_lib.py) refuses a library of another version, which is what protects an A/B of two builds (ECAMP_LIB, tools/ab_lib.sh)
- * from calling an older build with a newer argument list.  ecamp_ce_eval was ADDED at version 5 without touching an existing
- * signature: a build that lacks it is refused by the binding all the same, which resolves every declared symbol when it loads. */
+ * from calling an older build with a newer argument list.  ecamp_ce_eval -- and later ecamp_drop_path_fwd / ecamp_drop_path_bwd -- were
+ * ADDED at version 5 without touching an existing signature: a build that lacks them is refused by the binding all the same, which
+ * resolves every declared symbol when it loads. */
 #define ECAMP_ABI_VERSION 5
 int ecamp_abi_version(void);
 const char* ecamp_last_error(void);
@@ -398,6 +399,21 @@ int ecamp_sumsq_grouped(const float* g, const uint8_t* block_group, int64_t n, f
 int ecamp_sgd_grouped(float* p, const float* g, float* buf, void* p16, const uint8_t* block_group, int64_t n, int32_t ngroups,
                       const float* lr_host, const float* wd_host, float momentum, float max_norm, const float* partials, int32_t npart,
                       float grad_scale, const float* ctl, float* norm_out, ecampStream_t stream);
+/* Stochastic depth on the ViT residual stream: timm's DropPath(scale_by_keep=True) inside timm's Block, which the reference fine-tunes
+ * with drop_path_rate=0.1 (Fine-tuning/Classification/train.py:127; rates linear over the blocks, timm vision_transformer.py).
+ *   out[b, t, :] = res[b, t, :] + s_b * y[b, t, :],   s_b = 0 or 1 / (1 - p)
+ * res, y, out [B*T, D] contiguous rows.  Sample b is kept iff element b of the library's dropout convention under (seed, offset) is: the
+ * kept set is ecamp_dropout_mask(keep, B, p, seed, offset).  No mask is stored; ecamp_drop_path_bwd regenerates it.  Dtype pairs
+ * (res_dtype, y_dtype): (1, 1) the 16-bit modes, (0, 0) the f32 parity mode, (0, 1) the f32 residual stream with a 16-bit branch; `out`
+ * has res's dtype.  f32 arithmetic, one rounding to the output format.  `out` may be `y` itself when the dtypes agree, and may overlap
+ * neither res nor (otherwise) y.  A dropped sample's y is not read and its output rows are res's bits.  D % 4 == 0 (16-byte accesses
+ * when D % 8 == 0 in 16 bits or D % 4 == 0 in f32, else 8-byte ones; pointers aligned accordingly), 0 <= p < 1.  Deterministic. */
+int ecamp_drop_path_fwd(const void* res, const void* y, void* out, int64_t B, int32_t T, int32_t D, float p, uint64_t seed, uint64_t offset,
+                        int32_t res_dtype, int32_t y_dtype, ecampStream_t stream);
+/* Its backward with respect to y: dy[b, t, :] = s_b * dout[b, t, :] in `dtype` (the gradient stream's format: 1, or 0 in the f32 mode);
+ * the gradient of res is dout itself.  dy may not overlap dout.  A dropped sample's dout is not read and exact +0 is written. */
+int ecamp_drop_path_bwd(const void* dout, void* dy, int64_t B, int32_t T, int32_t D, float p, uint64_t seed, uint64_t offset, int32_t dtype,
+                        ecampStream_t stream);
 
 /* ---- optional in-process timing (bench.py roofline): HIP-event pairs around every GEMM / attention launch ---- */
 int ecamp_prof_enable(int on);

@@ -9,6 +9,16 @@
   3  `ecamp_pool_norm_bwd` (dx [B, 197, 768] in bf16) beside a plain device copy of the same bytes.
 
     python tools/finetune_bench.py [--iters 20] [--warmup 3] [--batches 96,256] [--out profiles/finetune.txt]
+
+`--droppath` runs another leg INSTEAD and writes profiles/finetune_droppath.txt (`--droppath_out`); without it nothing above changes:
+
+  4  `ecamp_drop_path_fwd` / `ecamp_drop_path_bwd` alone on bf16 [B, 197, 768] beside `ecamp_add` on the same buffers, alternating in one
+     loop, outputs allocated once.  ecamp_add moves three streams (two read, one written), and so does the forward for a kept sample (a
+     dropped one moves two); the backward moves two (a dropped sample: one).  Expected: the forward at p = 0 -- the same bytes, one Philox
+     call per (workgroup, sample) -- at parity with ecamp_add.
+  5  the whole fine-tune step of leg 1 at drop_path_rate 0 against 0.1 on ONE model and optimizer, blocks of `--iters` steps alternating
+     between the two rates.
+  `--parity_log FILE`: the "[droppath]" lines that tests/test_droppath_model_gpu.py prints under `pytest -s` are copied behind the timings.
 """
 import argparse
 import os
@@ -56,6 +66,94 @@ def event_groups(fns, iters, warmup, group):
     return {name: [1e3 * p.elapsed_time(q) / group for p, q in pairs] for name, pairs in t.items()}
 
 
+def droppath_leg(args, say):
+    """Legs 4 and 5 (see the module docstring)."""
+    from ecamp_amd import _lib, engine_finetune
+    from ecamp_amd import hip_ops as ops
+    from ecamp_amd.module.classifier import build_classifier
+    dev = torch.device("cuda")
+    C, T, D = args.classes, 197, 768
+    BF16 = _lib.BF16
+    say("stochastic depth on %s: ViT-B/16 in bf16, R = 224, %d classes" % (torch.cuda.get_device_name(0), C))
+    say("4  kernels alone: bf16 [B, %d, %d], per call, from event pairs around 20 calls, the kernels alternating in one loop (%d groups after %d warm-up "
+        "groups); one stream = B x %d x %d x 2 bytes (at B = 96 the three streams, 87 MB, fit the 256 MB last-level cache: the rates are not HBM rates, "
+        "for any of the kernels)" % (T, D, args.iters, args.warmup, T, D))
+    seed, off = 0x9E3779B97F4A7C15, 5
+    for B in [int(b) for b in args.batches.split(",")]:
+        res = torch.randn(B * T, D, device=dev).to(torch.bfloat16)
+        y = torch.randn(B * T, D, device=dev).to(torch.bfloat16)
+        out = torch.empty_like(res)
+        one = res.numel() * 2
+        kept = int(ops.dropout_mask((B,), dev, 0.1, seed, off).sum().item())
+        st = ops.stream
+
+        def add():
+            _lib.call("ecamp_add", ops.ptr(res), ops.ptr(y), ops.ptr(out), res.numel(), BF16, st())
+
+        def fwd(p):
+            return lambda: _lib.call("ecamp_drop_path_fwd", ops.ptr(res), ops.ptr(y), ops.ptr(out), B, T, D, p, seed, off, BF16, BF16, st())
+
+        def bwd(p):
+            return lambda: _lib.call("ecamp_drop_path_bwd", ops.ptr(res), ops.ptr(out), B, T, D, p, seed, off, BF16, st())
+
+        names = [("ecamp_add", add, 3.0), ("drop_path_fwd p=0", fwd(0.0), 3.0), ("drop_path_fwd p=0.1", fwd(0.1), (3.0 * kept + 2.0 * (B - kept)) / B),
+                 ("drop_path_bwd p=0", bwd(0.0), 2.0), ("drop_path_bwd p=0.1", bwd(0.1), (2.0 * kept + 1.0 * (B - kept)) / B)]
+        us = event_groups([(n, f) for n, f, _ in names], args.iters, args.warmup, 20)
+        say("   B = %3d: one stream = %.1f MB; at p = 0.1 this (seed, offset) keeps %d of %d samples" % (B, one / 1e6, kept, B))
+        med_add, lo_add, hi_add = stats(us["ecamp_add"])
+        for n, _, streams in names:
+            med_u, lo_u, hi_u = stats(us[n])
+            say("     %-20s median %7.1f us (min %.1f, max %.1f) = %.2f x ecamp_add; %.2f streams = %.0f GB/s"
+                % (n, med_u, lo_u, hi_u, med_u / med_add, streams, streams * one / (med_u * 1e-6) / 1e9))
+        gap = stats(us["drop_path_fwd p=0"])[0] - med_add
+        say("     expectation: drop_path_fwd at p = 0 at parity with ecamp_add (same bytes): gap %+.1f us against ecamp_add's own min-max spread of %.1f us: %s"
+            % (gap, hi_add - lo_add, "met" if gap <= hi_add - lo_add else "NOT met"))
+        del res, y, out
+
+    torch.manual_seed(0)
+    clf = build_classifier("vit_base_patch16", C, True, img_size=224, compute_dtype=torch.bfloat16, train_encoder=True, drop_path_rate=0.1).to(dev)
+    step_args = argparse.Namespace(learning_rate=3e-2, weight_decay=1e-4, decay_type="cosine", warmup_steps=50, num_steps=3000, max_grad_norm=1.0)
+    opt = engine_finetune.make_optimizer(clf, step_args)
+    rates = {0.1: list(clf.drop_path_rates), 0.0: [0.0] * len(clf.drop_path_rates)}
+    say("5  the whole fine-tune step (forward + backward + clip + SGD) at drop_path_rate 0 against 0.1: one model, one optimizer, blocks of %d steps "
+        "alternating between the rates, host clock around a block that ends in a device synchronise, 5 blocks each after %d warm-up steps each" % (args.iters, args.warmup))
+    for B in [int(b) for b in args.batches.split(",")]:
+        imgs = torch.randn(B, 3, 224, 224, device=dev)
+        y = (torch.rand(B, C, device=dev) < 0.3).float()
+        n = [0]
+
+        def block(rate, steps):
+            clf.drop_path_rate, clf.drop_path_rates = rate, rates[rate]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                engine_finetune.train_step(clf, opt, imgs, y, n[0], step_args)
+                n[0] += 1
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / steps
+
+        for rate in (0.0, 0.1):
+            block(rate, args.warmup)
+        ms = {0.0: [], 0.1: []}
+        for _ in range(5):
+            for rate in (0.0, 0.1):
+                ms[rate].append(1e3 * block(rate, args.iters))
+        m0, lo0, hi0 = stats(ms[0.0])
+        m1, lo1, hi1 = stats(ms[0.1])
+        say("   B = %3d  rate 0: %.2f ms (min %.2f, max %.2f) = %.0f images/s;  rate 0.1: %.2f ms (min %.2f, max %.2f) = %.0f images/s;  "
+            "stochastic depth costs %+.2f ms = %+.1f %% (block-to-block spread at rate 0: %.2f ms)"
+            % (B, m0, lo0, hi0, B / (m0 * 1e-3), m1, lo1, hi1, B / (m1 * 1e-3), m1 - m0, 100.0 * (m1 - m0) / m0, hi0 - lo0))
+        sites = 2 * sum(r > 0 for r in rates[0.1])
+        say("            %d active sites; from bytes alone: per site the forward adds one write and one read of a bf16 [B, 197, 768] stream to the GEMM "
+            "epilogue it replaces, the backward one read and one write: about %.2f GB more per step" % (sites, sites * 4 * B * 197 * 768 * 2 / 1e9))
+        del imgs, y
+    if args.parity_log:
+        say("6  parity of the model test (tests/test_droppath_model_gpu.py, ecamp_tiny, B = 4, drop_path_rate 0.5, float64 reference under the same masks):")
+        for line in open(args.parity_log):
+            if "[droppath]" in line:
+                say("   " + line.strip().lstrip(".").strip())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
@@ -63,9 +161,24 @@ def main():
     ap.add_argument("--batches", type=str, default="96,256")
     ap.add_argument("--classes", type=int, default=14)
     ap.add_argument("--out", type=str, default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "finetune.txt"))
+    ap.add_argument("--droppath", action="store_true", help="run the stochastic-depth leg instead (profiles/finetune_droppath.txt)")
+    ap.add_argument("--droppath_out", type=str, default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "finetune_droppath.txt"))
+    ap.add_argument("--parity_log", type=str, default="", help="--droppath: a `pytest -s` log of tests/test_droppath_model_gpu.py whose [droppath] lines are copied")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("finetune_bench needs an MI355X: nothing here can be measured on a CPU")
+    if args.droppath:
+        lines = []
+
+        def say_dp(msg):
+            print(msg, flush=True)
+            lines.append(msg)
+
+        droppath_leg(args, say_dp)
+        os.makedirs(os.path.dirname(os.path.abspath(args.droppath_out)), exist_ok=True)
+        with open(args.droppath_out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     from ecamp_amd import engine_finetune, engine_linprobe
     from ecamp_amd import hip_ops as ops
     from ecamp_amd.module.classifier import build_classifier
