@@ -571,7 +571,8 @@ def test_unshuffle(dev, dtype):
 def test_sr_head_matrix_core_mode(dev, R, win):
     """mode 1 of ecamp_sr_fwd/bwd (bf16 4x4x4 MFMA stencils, used when compute_dtype is bf16) against torch autograd of the reference
     SR head (model_ecamp.py:28-46,291-299).  u, c1, ds, dc1 are rounded to bf16: loss within 2e-3, gradients within a few 1e-2 of
-    their scale on average; single pixels whose ReLU gate sits within rounding of zero may flip (that is what bf16 activations do)."""
+    their scale on average; single pixels whose ReLU gate sits within rounding of zero may flip (that is what bf16 activations do).
+    Per-element bounds against float64, more than one tile per workgroup and the IEEE-half build: tests/test_sr_head_gpu.py."""
     o = ops()
     B = 3
     pimg, big = gen(B, 3, R, R, seed=2), gen(B, 3, 2 * R, 2 * R, seed=3)
