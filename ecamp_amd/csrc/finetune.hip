@@ -1,9 +1,10 @@
 // Fine-tuning the encoder behind the classifier (Fine-tuning/Classification of the reference, `--mode Finetune`: train.py:377-384 SGD with
 // momentum, :456-461 clip_grad_norm_ + step): the two backward kernels between the loss and the last transformer block
 // (ecamp_cls_head_dgrad, ecamp_pool_norm_bwd) and SGD with the global-norm clip over a flat parameter buffer (ecamp_sumsq_grouped,
-// ecamp_sgd_grouped).  Conventions as classify.hip: f32 arithmetic, every sum in ONE fixed order (per-thread strides, LDS, partials in
-// index order), no float atomic, no workgroup waits for another, grids capped with a loop beyond the cap.  All four are HBM-bound:
-// 16-byte accesses, three or four loads in flight per thread, enough workgroups for 256 CUs.
+// ecamp_sgd_grouped), and the stem's batch reduction for a trained pos_embed (ecamp_pos_embed_grad, `--train_pos_embed`).  Conventions as
+// classify.hip: f32 arithmetic, every sum in ONE fixed order (per-thread strides, LDS, partials in index order), no float atomic, no
+// workgroup waits for another, grids capped with a loop beyond the cap.  All five are HBM-bound: 16-byte accesses, three or four loads
+// in flight per thread, enough workgroups for 256 CUs.
 #include "classify.h"
 #include "group_hyper.h"
 
@@ -221,6 +222,219 @@ extern "C" int ecamp_pool_norm_bwd(const float* dfeat, const float* pooled, cons
     else if (p.vec == 8) L(bf16_t, 8);
     else L(bf16_t, 4);
 #undef L
+    ECAMP_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// ecamp_pos_embed_grad: the three parameter gradients of the stem that are sums of rows of S[t, d] = sum_b dx[b, t, d] -- pos_embed (S
+// itself), cls_token (row 0) and the patch embedding's bias (rows 1 .. T-1 added up) -- from ONE pass over dx.  Two launches:
+//   1. the stream (where the bytes are: 29 MB at ViT-B, B = 96, in 16 bits).  S is T*D / VEC independent columns of 16-byte vectors; a
+//      workgroup takes PEG_CW of them x four batch lanes (one wave each, so a wave's load is 1 KB in one piece), and the batch is cut
+//      into `nsplit` ranges over workgroups until 256 CUs have work (peg_plan).  A lane adds its samples b0 + lane, b0 + lane + 4, ... in
+//      that order, four loads in flight; the lanes are added through LDS in lane order; the range's partial goes to ws[split][T*D].
+//   2. the small one: S = the ranges' partials added in range order, into dpos (row 0 also into dcls) with one 16-byte vector per thread,
+//      and the sum of its rows 1 .. T-1 into dbias, 64 token lanes per 16-column tile (pos_embed_grad_apply_kernel).
+constexpr int PEG_CW = 64;              // 16-byte column vectors per workgroup of launch 1
+constexpr int PEG_LANES = 4;            // batch lanes per workgroup of launch 1
+constexpr int PEG_TARGET_WG = 1024;     // as POOL_TARGET_WG: four workgroups per CU before the batch stops being split further
+constexpr int PEG_MAX_SPLIT = 16;
+
+struct PegPlan {
+    int vec, ntile, nsplit;
+    int64_t nv, bchunk;
+};
+
+// A function of (B, T, D, dtype) alone, so that the workspace size, both launches and with them every summation order agree.
+static PegPlan peg_plan(int64_t B, int T, int D, int dtype) {
+    PegPlan p;
+    p.vec = dtype == ECAMP_F32 ? 4 : 8;
+    p.nv = (int64_t)T * D / p.vec;
+    p.ntile = (int)((p.nv + PEG_CW - 1) / PEG_CW);
+    int64_t want = (PEG_TARGET_WG + p.ntile - 1) / p.ntile;
+    const int64_t most = (B + PEG_LANES * 4 - 1) / (PEG_LANES * 4);   // a lane keeps at least four samples: its loads in flight
+    if (want > most) want = most;
+    if (want > PEG_MAX_SPLIT) want = PEG_MAX_SPLIT;
+    if (want < 1) want = 1;
+    p.bchunk = (B + want - 1) / want;
+    p.nsplit = (int)((B + p.bchunk - 1) / p.bchunk);
+    return p;
+}
+
+static bool peg_shape_ok(int64_t B, int32_t T, int32_t D, int32_t dtype) {
+    if (dtype != ECAMP_F32 && dtype != ECAMP_BF16) return false;
+    return B >= 1 && T >= 2 && D >= 1 && D % (dtype == ECAMP_F32 ? 4 : 8) == 0;
+}
+
+template <typename T> struct PegVec;
+template <> struct PegVec<float> {
+    static constexpr int VEC = 4;
+    typedef float4 raw_t;
+    static __device__ __forceinline__ void add(float* a, const float4& v) { a[0] += v.x; a[1] += v.y; a[2] += v.z; a[3] += v.w; }
+};
+template <> struct PegVec<bf16_t> {
+    static constexpr int VEC = 8;
+    typedef uint4 raw_t;
+    static __device__ __forceinline__ void add(float* a, const uint4& v) {
+        a[0] += h16_lo(v.x); a[1] += h16_hi(v.x); a[2] += h16_lo(v.y); a[3] += h16_hi(v.y);
+        a[4] += h16_lo(v.z); a[5] += h16_hi(v.z); a[6] += h16_lo(v.w); a[7] += h16_hi(v.w);
+    }
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void pos_embed_grad_stream_kernel(const T* __restrict__ dx, float* __restrict__ part, int64_t B, int64_t nv,
+                                                                    int ntile, int nsplit, int64_t bchunk) {
+    typedef PegVec<T> V;
+    typedef typename V::raw_t raw_t;
+    constexpr int VEC = V::VEC;
+    __shared__ float sh[PEG_LANES - 1][VEC][PEG_CW];   // [lane][element][column]: a wave writes 64 consecutive floats
+    const int c = threadIdx.x & (PEG_CW - 1), lane = threadIdx.x / PEG_CW;
+    const int64_t items = (int64_t)ntile * nsplit;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int split = (int)(item / ntile);
+        const int64_t cv = (item % ntile) * PEG_CW + c;
+        const int64_t b0 = split * bchunk;
+        const int64_t b1 = b0 + bchunk < B ? b0 + bchunk : B;
+        float acc[VEC];
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
+        if (cv < nv) {
+            const raw_t* src = reinterpret_cast<const raw_t*>(dx) + cv;   // sample b of this column: src[b * nv]
+            int64_t b = b0 + lane;
+            for (; b + 3 * PEG_LANES < b1; b += 4 * PEG_LANES) {   // four loads in flight, added in sample order
+                raw_t v[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v[k] = src[(b + k * PEG_LANES) * nv];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) V::add(acc, v[k]);
+            }
+            for (; b < b1; b += PEG_LANES) V::add(acc, src[b * nv]);
+        }
+        if (lane > 0) {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) sh[lane - 1][k][c] = acc[k];
+        }
+        __syncthreads();
+        if (lane == 0 && cv < nv) {
+#pragma unroll
+            for (int l = 0; l < PEG_LANES - 1; ++l) {
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) acc[k] += sh[l][k][c];
+            }
+            float* dst = part + ((int64_t)split * nv + cv) * VEC;
+#pragma unroll
+            for (int k = 0; k < VEC; k += 4) *reinterpret_cast<float4*>(dst + k) = make_float4(acc[k], acc[k + 1], acc[k + 2], acc[k + 3]);
+        }
+        __syncthreads();   // (lane 0 has read sh before the next item writes it)
+    }
+}
+
+// S[t, d .. d + 3] of the float4 at element offset o of the table: the ranges' partials added in range order.
+__device__ __forceinline__ float4 peg_table(const float* __restrict__ part, int64_t o, int64_t TD, int nsplit) {
+    float4 s = *reinterpret_cast<const float4*>(part + o);
+    for (int k = 1; k < nsplit; ++k) {
+        const float4 v = *reinterpret_cast<const float4*>(part + k * TD + o);
+        s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+    }
+    return s;
+}
+
+__device__ __forceinline__ void peg_add4(float* p, const float4& s) {
+    float4 g = *reinterpret_cast<const float4*>(p);
+    g.x += s.x; g.y += s.y; g.z += s.z; g.w += s.w;
+    *reinterpret_cast<float4*>(p) = g;
+}
+
+// Launch 2, two kinds of workgroup in one grid (a single workgroup per 64-column tile walking all tokens took 18 us at T = 197 whatever
+// the batch: thirteen dependent trips to L2 per thread, on twelve CUs):
+//   [0, npos): dpos += S, one float4 of the table per thread (its first row also into dcls);
+//   [npos, npos + nbias): dbias of a PEG_BIAS_COLS-column tile: four 16-byte vectors x 64 token lanes, a lane adds S of the tokens
+//     1 + lane, 65 + lane, ... in that order (loads only: the table is read again, from L2), then the lanes are added through LDS in
+//     lane order, eight at a time and then the eight sums.
+constexpr int PEG_BIAS_COLS = 16;
+constexpr int PEG_APPLY_GRID = CLS_MAX_GRID / 2;   // the cap of either kind
+
+__global__ __launch_bounds__(256) void pos_embed_grad_apply_kernel(const float* __restrict__ part, float* __restrict__ dpos,
+                                                                   float* __restrict__ dcls, float* __restrict__ dbias, int Tn, int D, int nsplit,
+                                                                   int npos, int nbias) {
+    __shared__ float4 sh[256];
+    const int64_t TD = (int64_t)Tn * D;
+    if ((int)blockIdx.x < npos) {
+        const int64_t n4 = TD / 4;
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)npos * 256) {
+            const int64_t o = i * 4;
+            const float4 s = peg_table(part, o, TD, nsplit);
+            peg_add4(dpos + o, s);
+            if (dcls && o < D) peg_add4(dcls + o, s);   // row 0, the cls token (D % 4 == 0: a vector lies in one row)
+        }
+        return;
+    }
+    const int dl = threadIdx.x & 3, lane = threadIdx.x >> 2;
+    for (int tile = (int)blockIdx.x - npos; tile * PEG_BIAS_COLS < D; tile += nbias) {
+        const int d = tile * PEG_BIAS_COLS + dl * 4;
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (d < D) {
+            for (int t = 1 + lane; t < Tn; t += 64) {   // (the cls row carries no patch: no share of the bias gradient)
+                const float4 s = peg_table(part, (int64_t)t * D + d, TD, nsplit);
+                a.x += s.x; a.y += s.y; a.z += s.z; a.w += s.w;
+            }
+        }
+        sh[threadIdx.x] = a;
+        __syncthreads();
+        if (lane < 8) {
+            a = sh[lane * 32 + dl];
+            for (int k = 1; k < 8; ++k) {
+                const float4 v = sh[(lane * 8 + k) * 4 + dl];
+                a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+            }
+        }
+        __syncthreads();
+        if (lane < 8) sh[lane * 4 + dl] = a;
+        __syncthreads();
+        if (lane == 0 && d < D) {
+            a = sh[dl];
+            for (int k = 1; k < 8; ++k) {
+                const float4 v = sh[k * 4 + dl];
+                a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+            }
+            peg_add4(dbias + d, a);
+        }
+        __syncthreads();   // (sh is read before the next tile writes it)
+    }
+}
+
+extern "C" int64_t ecamp_pos_embed_grad_workspace_bytes(int64_t B, int32_t T, int32_t D, int32_t dtype) {
+    if (!peg_shape_ok(B, T, D, dtype)) return 0;
+    return (int64_t)peg_plan(B, T, D, dtype).nsplit * T * D * (int64_t)sizeof(float);   // partial sums [nsplit, T, D]
+}
+
+extern "C" int ecamp_pos_embed_grad(const void* dx, float* dpos, float* dcls, float* dbias, int64_t B, int32_t T, int32_t D, void* ws,
+                                    int32_t dtype, hipStream_t stream) {
+    ECAMP_CHECK_ARG(dx && dpos && ws, "pos_embed_grad: null pointer");
+    ECAMP_CHECK_ARG((dcls == nullptr) == (dbias == nullptr), "pos_embed_grad: null pointer (dcls and dbias are given together, or both null)");
+    ECAMP_CHECK_ARG(dtype == ECAMP_F32 || dtype == ECAMP_BF16, "pos_embed_grad: bad dtype %d", dtype);
+    ECAMP_CHECK_ARG(B >= 1, "pos_embed_grad: B=%lld must be positive", (long long)B);
+    ECAMP_CHECK_ARG(T >= 2, "pos_embed_grad: T=%d must be at least 2 (the cls row and one patch)", T);
+    ECAMP_CHECK_ARG(D >= 1 && D % (dtype == ECAMP_F32 ? 4 : 8) == 0, "pos_embed_grad: D=%d must be a positive multiple of %d", D,
+                    dtype == ECAMP_F32 ? 4 : 8);
+    ECAMP_CHECK_ARG(((reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(dpos) | reinterpret_cast<uintptr_t>(dcls) |
+                      reinterpret_cast<uintptr_t>(dbias) | reinterpret_cast<uintptr_t>(ws)) & 15) == 0,
+                    "pos_embed_grad: dx, dpos, dcls, dbias and ws must be 16-byte aligned");
+    const PegPlan p = peg_plan(B, T, D, dtype);
+    const int64_t items = (int64_t)p.ntile * p.nsplit;
+    const dim3 grid((unsigned)(items < CLS_MAX_GRID ? items : CLS_MAX_GRID)), block(256);
+    if (dtype == ECAMP_F32)
+        hipLaunchKernelGGL(pos_embed_grad_stream_kernel<float>, grid, block, 0, stream, (const float*)dx, (float*)ws, B, p.nv, p.ntile, p.nsplit, p.bchunk);
+    else
+        hipLaunchKernelGGL(pos_embed_grad_stream_kernel<bf16_t>, grid, block, 0, stream, (const bf16_t*)dx, (float*)ws, B, p.nv, p.ntile, p.nsplit,
+                           p.bchunk);
+    ECAMP_LAUNCH_CHECK();
+    const int64_t pos_wg = ((int64_t)T * D / 4 + 255) / 256;
+    const int npos = (int)(pos_wg < PEG_APPLY_GRID ? pos_wg : PEG_APPLY_GRID);
+    const int bias_wg = ceil_div(D, PEG_BIAS_COLS);
+    const int nbias = dbias ? (bias_wg < PEG_APPLY_GRID ? bias_wg : PEG_APPLY_GRID) : 0;
+    hipLaunchKernelGGL(pos_embed_grad_apply_kernel, dim3((unsigned)(npos + nbias)), dim3(256), 0, stream, (const float*)ws, dpos, dcls, dbias, T, D,
+                       p.nsplit, npos, nbias);
     ECAMP_LAUNCH_CHECK();
     return 0;
 }

@@ -211,6 +211,16 @@ class StemFn(torch.autograd.Function):
         dx = dx.contiguous()
         pe = m.patch_embed.proj
         _wgrad(A, dx, ctx.cols, pe.weight, shape=(m.embed_dim, -1))
+        if id(m.pos_embed) in A.index:
+            # a trained pos_embed (ECAMPClassifier(train_pos_embed=True)): its gradient is dx summed over the batch, and the gradients of
+            # the bias and of cls_token are sums of rows of that table -- one fixed-order pass over dx yields all three.  Token t of every
+            # sample must sit at position t of the table: every patch kept, in place (the classifier's identity noise).
+            if ctx.Lk != m.num_patches:
+                raise RuntimeError("StemFn.backward: a trained pos_embed needs every patch kept in place (mask_ratio 0, identity noise); "
+                                   "%d of %d patches were kept" % (ctx.Lk, m.num_patches))
+            ops.pos_embed_grad(dx.view(-1, Tt, m.embed_dim), A.grad(m.pos_embed).view(Tt, -1), A.grad(m.cls_token).view(-1), A.grad(pe.bias))
+            A.ready(pe.weight, pe.bias, m.cls_token, m.pos_embed)
+            return _none(5)
         ops.colsum(dx, A.grad(pe.bias), period=Tt, lo=1, hi=Tt)  # cls rows carry no patch: excluded from the bias gradient
         ops.colsum(dx, A.grad(m.cls_token).view(-1), period=Tt, lo=0, hi=1)
         A.ready(pe.weight, pe.bias, m.cls_token)

@@ -751,6 +751,21 @@ def pool_norm_bwd(dfeat, pooled, gamma, t0, t1, T, eps, dtype, want_affine=True)
     return dx, dgamma, dbeta
 
 
+def pos_embed_grad(dx, dpos, dcls=None, dbias=None):
+    """The stem's row-sum gradients from one pass over dx [B, T, D] (f32 or the active 16-bit format): with S = dx summed over the batch,
+    dpos f32 [T, D] += S, dcls f32 [D] += S[0], dbias f32 [D] += S[1:] summed over the tokens.  dcls and dbias are given together or not
+    at all.  Fixed summation order, no atomics; the workspace comes from the caching allocator."""
+    _chk(dx, dpos, dcls, dbias)
+    B, T, D = dx.shape
+    assert dx.is_contiguous() and dpos.dtype == torch.float32 and dpos.is_contiguous() and dpos.numel() == T * D
+    assert (dcls is None) == (dbias is None)
+    for g in (dcls, dbias):
+        assert g is None or (g.dtype == torch.float32 and g.is_contiguous() and g.numel() == D)
+    dt = code(dx.dtype)
+    ws = torch.empty((max(16, int(_lib.load().ecamp_pos_embed_grad_workspace_bytes(B, T, D, dt))),), device=dx.device, dtype=torch.uint8)
+    call("ecamp_pos_embed_grad", ptr(dx), ptr(dpos), ptr(dcls), ptr(dbias), B, T, D, ptr(ws), dt, stream())
+
+
 SUMSQ_MAX_SLOTS = 2048   # ecamp_sumsq_grouped fills at most this many partials per launch
 
 

@@ -10,7 +10,7 @@ ECAMP/Fine-tuning/Classification (run_lp.sh), on one MI355X:
 The reference's flag names are kept.  Added: --list_dir (the reference hard-codes ./datasets/<task>), --compute_dtype {bf16,fp16,fp32}
 (--fp16 is --compute_dtype fp16; --fp16_opt_level is accepted and ignored), --pool {avg,cls}, --f32_residual, --synthetic,
 --synthetic_len, --num_workers, --print_freq, --drop_path_rate (main_finetune's stochastic depth; refused here unless 0: the frozen
-encoder of the probe is deterministic).  `--stage train` trains, then tests the best checkpoint, as the reference does.
+encoder of the probe is deterministic), --train_pos_embed (main_finetune's trained position table; refused here).  `--stage train` trains, then tests the best checkpoint, as the reference does.
 
 NOT implemented here, and refused with a message: `--mode Finetune` (main_finetune's), data-parallel probing (`--local_rank` other
 than -1); segmentation and detection fine-tuning have no counterpart in this project.
@@ -68,6 +68,9 @@ def get_args_parser():
     p.add_argument("--drop_path_rate", default=0.0, type=float,
                    help="--mode Finetune: stochastic depth, the rate of the last block (linear over the blocks from 0); the reference hard-codes 0.1 "
                         "(train.py:127), the default here is 0.0: none")
+    p.add_argument("--train_pos_embed", action="store_true",
+                   help="--mode Finetune: train pos_embed as the reference does (timm's is a parameter among model.parameters()); the default "
+                        "here holds it at the fixed sin-cos table")
     return p
 
 
@@ -79,6 +82,9 @@ def check_args(args):
     if getattr(args, "drop_path_rate", 0.0) != 0:
         raise SystemExit("--drop_path_rate %g with --mode LinearProbe: the probe's encoder is frozen and deterministic, stochastic depth belongs to "
                          "--mode Finetune (main_finetune)" % args.drop_path_rate)
+    if getattr(args, "train_pos_embed", False):
+        raise SystemExit("--train_pos_embed with --mode LinearProbe: the probe's encoder is frozen, pos_embed included; a trained position table "
+                         "belongs to --mode Finetune (main_finetune)")
     if args.local_rank != -1:
         raise SystemExit("--local_rank %d: data-parallel probing is not implemented here; run on one device (--local_rank -1)" % args.local_rank)
     if args.gradient_accumulation_steps != 1:

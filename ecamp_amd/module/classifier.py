@@ -9,7 +9,11 @@ plain f32 parameters of this module, outside the wrapped model's arena and state
 `ECAMPClassifier(..., train_encoder=True)` is the `--mode Finetune` share (train.py:144-166): in training mode `forward` runs the same
 stages with their hand-written backwards (StemFn, VitBlockFn, then PoolNormFn or NormFn) so that the loss reaches every encoder
 parameter; `fc_norm` and `head` then live in a small flat buffer of their own (arena.FlatTail) which the fused SGD step updates beside
-the arena.  `pos_embed` stays the fixed sin-cos table.
+the arena.  `pos_embed` stays the fixed sin-cos table unless `train_pos_embed=True` (default False; timm's pos_embed is a trained
+parameter, so the reference trains it): `pos_embed.requires_grad` is then turned on before the encoder's arena is built, the arena places
+it like any other trained tensor (gradient view, block table, the fused SGD step with the one clip coefficient and weight decay), and
+StemFn's backward forms its gradient -- dx summed over the batch -- together with the bias and cls_token gradients in one fixed-order
+pass (`ecamp_pos_embed_grad`).  Forward, eval and checkpoints read and write the trained table.
 
 Stochastic depth: `drop_path_rate` (default 0.0: none; the reference builds its ViT with drop_path_rate=0.1, train.py:127) gives block i
 the rate linspace(0, rate, depth)[i], timm's rule, and the differentiable training path hands each block its rate (VitBlockFn: timm
@@ -29,8 +33,10 @@ def _is_encoder_key(k):
 
 
 class ECAMPClassifier(nn.Module):
-    def __init__(self, encoder, num_classes, multilabel=True, pool="avg", train_encoder=False, drop_path_rate=0.0):
+    def __init__(self, encoder, num_classes, multilabel=True, pool="avg", train_encoder=False, drop_path_rate=0.0, train_pos_embed=False):
         super().__init__()
+        if train_pos_embed and not train_encoder:
+            raise ValueError("train_pos_embed=True needs train_encoder=True (the linear probe's encoder is frozen)")
         rate = float(drop_path_rate)
         if not 0.0 <= rate < 1.0:
             raise ValueError("drop_path_rate must lie in [0, 1), got %r" % (drop_path_rate,))
@@ -51,6 +57,15 @@ class ECAMPClassifier(nn.Module):
         self.bad_label = None      # int32[1] on the device: 1 once ANY `loss` call since the last `check_labels` saw a label outside [0, C)
         self._noise = {}
         self.train_encoder = bool(train_encoder)   # False: the linear probe, exactly; True: `forward` is differentiable down to the stem
+        # a trained pos_embed must be in the arena: the flag is turned on before `prepare()` builds it (and survives `.to()`, which keeps
+        # requires_grad and drops the arena); an arena that was built without it is not rebuilt behind its owner's back
+        self.train_pos_embed = bool(train_pos_embed)
+        if self.train_pos_embed:
+            arena = getattr(encoder, "arena", None)
+            if arena is not None and id(encoder.pos_embed) not in arena.index:
+                raise RuntimeError("train_pos_embed=True: the encoder's parameter arena was already built without pos_embed; wrap the model "
+                                   "before its first forward / prepare()")
+            encoder.pos_embed.requires_grad_(True)
         self._tail = None          # arena.FlatTail over fc_norm and head (train_encoder only; built on the device, on first use)
         # stochastic depth per block: timm's torch.linspace(0, rate, depth), each value rounded to float32 once (the C ABI takes `float`);
         # block 0 always has rate 0 and keeps the fused residual epilogues
@@ -130,10 +145,11 @@ class ECAMPClassifier(nn.Module):
     def finetune_parameters(self):
         """[(name, parameter)] of what `--mode Finetune` trains, named as the reference's flat layout names them: the encoder's cls_token,
         patch_embed.proj.* and blocks.*, `norm.*` only when it is used (pool="cls"), `fc_norm.*` only when it is (pool="avg"), head.*.
-        `pos_embed` is the fixed sin-cos table (requires_grad=False, outside the arena); decoder and report side are not trained."""
+        `pos_embed` only with `train_pos_embed` (otherwise it is the fixed sin-cos table: requires_grad=False, outside the arena);
+        decoder and report side are not trained."""
         out = []
         for k, p in self.encoder.named_parameters():
-            if k == "cls_token" or k.startswith(("patch_embed.proj.", "blocks.")) or (k.startswith("norm.") and self.pool == "cls"):
+            if k == "cls_token" or (k == "pos_embed" and self.train_pos_embed) or k.startswith(("patch_embed.proj.", "blocks.")) or (k.startswith("norm.") and self.pool == "cls"):
                 out.append((k, p))
         if self.pool == "avg":
             out += [("fc_norm.weight", self.fc_norm.weight), ("fc_norm.bias", self.fc_norm.bias)]
@@ -220,10 +236,12 @@ _ENCODERS = {"vit_tiny_patch16": dict(embed_dim=192, depth=12, num_heads=3), "vi
              "vit_large_patch16": dict(embed_dim=1024, depth=24, num_heads=16)}
 
 
-def build_classifier(model_name, num_classes, multilabel, img_size=224, pool="avg", train_encoder=False, drop_path_rate=0.0, **kwargs):
+def build_classifier(model_name, num_classes, multilabel, img_size=224, pool="avg", train_encoder=False, drop_path_rate=0.0,
+                     train_pos_embed=False, **kwargs):
     """The reference's `--model` name -> an ECAMPClassifier around an ECAMP with that encoder at `img_size` (decoder and report side
     as the pre-training factories build them, so a pre-training checkpoint's encoder keys fit).  `drop_path_rate`: the stochastic-depth
-    rate of the last block (ECAMPClassifier; the reference's is 0.1, train.py:127)."""
+    rate of the last block (ECAMPClassifier; the reference's is 0.1, train.py:127).  `train_pos_embed`: train the position table as the
+    reference does (needs train_encoder=True)."""
     from functools import partial
 
     from .bert_config import BertConfig
@@ -232,8 +250,11 @@ def build_classifier(model_name, num_classes, multilabel, img_size=224, pool="av
         raise ValueError("--model must be one of %s, got %r" % (", ".join(sorted(_ENCODERS)), model_name))
     if not 0.0 <= float(drop_path_rate) < 1.0:
         raise ValueError("drop_path_rate must lie in [0, 1), got %r" % (drop_path_rate,))
+    if train_pos_embed and not train_encoder:
+        raise ValueError("train_pos_embed=True needs train_encoder=True (the linear probe's encoder is frozen)")
     if model_name == "vit_tiny_patch16":
         kwargs.setdefault("bert_config", BertConfig(num_hidden_layers=2))
     enc = ECAMP(img_size=img_size, patch_size=16, in_chans=3, decoder_embed_dim=512, decoder_depth=4, decoder_num_heads=16, mlp_ratio=4,
                 norm_layer=partial(nn.LayerNorm, eps=1e-6), **_ENCODERS[model_name], **kwargs)
-    return ECAMPClassifier(enc, num_classes, multilabel=multilabel, pool=pool, train_encoder=train_encoder, drop_path_rate=drop_path_rate)
+    return ECAMPClassifier(enc, num_classes, multilabel=multilabel, pool=pool, train_encoder=train_encoder, drop_path_rate=drop_path_rate,
+                           train_pos_embed=train_pos_embed)

@@ -29,7 +29,7 @@ typedef struct ihipStream_t* ecampStream_t; /* == hipStream_t */
  * ecamp_layernorm_fwd_x32, ecamp_layernorm_bwd_z32, ecamp_assemble_tokens_x32, ecamp_unshuffle_fwd_x32).  ecamp_abi_version()
  * returns the value the library was BUILT with; a consumer compares it with the header it was compiled against -- the Python binding
  * (ecamp_amd/_lib.py) refuses a library of another version, which is what protects an A/B of two builds (ECAMP_LIB, tools/ab_lib.sh)
- * from calling an older build with a newer argument list.  ecamp_ce_eval -- and later ecamp_drop_path_fwd / ecamp_drop_path_bwd -- were
+ * from calling an older build with a newer argument list.  ecamp_ce_eval -- and later ecamp_drop_path_fwd / ecamp_drop_path_bwd and ecamp_pos_embed_grad -- were
  * ADDED at version 5 without touching an existing signature: a build that lacks them is refused by the binding all the same, which
  * resolves every declared symbol when it loads. */
 #define ECAMP_ABI_VERSION 5
@@ -399,6 +399,19 @@ int ecamp_sumsq_grouped(const float* g, const uint8_t* block_group, int64_t n, f
 int ecamp_sgd_grouped(float* p, const float* g, float* buf, void* p16, const uint8_t* block_group, int64_t n, int32_t ngroups,
                       const float* lr_host, const float* wd_host, float momentum, float max_norm, const float* partials, int32_t npart,
                       float grad_scale, const float* ctl, float* norm_out, ecampStream_t stream);
+/* The stem's parameter gradients that are sums of rows of one table (`--train_pos_embed`: timm's pos_embed is a trained parameter,
+ * Fine-tuning/Classification/train.py:377-380).  dx [B, T, D] contiguous, the gradient at the stem's output, in `dtype` (0: f32, 1: the
+ * build's 16-bit format).  With S[t, d] = sum_b dx[b, t, d], formed ONCE by this call:
+ *   dpos[t, d] += S[t, d]                     dpos f32 [T, D]: pos_embed
+ *   dcls[d]    += S[0, d]                     dcls f32 [D]:    cls_token
+ *   dbias[d]   += sum_{t = 1 .. T-1} S[t, d]  dbias f32 [D]:   patch_embed.proj.bias (the cls row carries no patch)
+ * The outputs ACCUMULATE (parameter gradients in the arena, zeroed by zero_grad).  dcls and dbias are given together, or both NULL (only
+ * dpos is then touched).  One pass over dx, every sum in one fixed order that is a function of (B, T, D, dtype) alone: no atomics, two
+ * calls on equal inputs give equal bits.  B >= 1, T >= 2, D a positive multiple of 8 (16 bits) or 4 (f32); dx, dpos, dcls, dbias and ws
+ * 16-byte aligned.  ws: ecamp_pos_embed_grad_workspace_bytes(...) bytes of device memory, scratch (0 for a shape the launch refuses). */
+int64_t ecamp_pos_embed_grad_workspace_bytes(int64_t B, int32_t T, int32_t D, int32_t dtype);
+int ecamp_pos_embed_grad(const void* dx, float* dpos, float* dcls, float* dbias, int64_t B, int32_t T, int32_t D, void* ws, int32_t dtype,
+                         ecampStream_t stream);
 /* Stochastic depth on the ViT residual stream: timm's DropPath(scale_by_keep=True) inside timm's Block, which the reference fine-tunes
  * with drop_path_rate=0.1 (Fine-tuning/Classification/train.py:127; rates linear over the blocks, timm vision_transformer.py).
  *   out[b, t, :] = res[b, t, :] + s_b * y[b, t, :],   s_b = 0 or 1 / (1 - p)

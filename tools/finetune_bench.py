@@ -19,6 +19,16 @@
   5  the whole fine-tune step of leg 1 at drop_path_rate 0 against 0.1 on ONE model and optimizer, blocks of `--iters` steps alternating
      between the two rates.
   `--parity_log FILE`: the "[droppath]" lines that tests/test_droppath_model_gpu.py prints under `pytest -s` are copied behind the timings.
+
+`--pos_embed` runs another leg INSTEAD and writes profiles/finetune_pos_embed.txt (`--pos_embed_out`):
+
+  7  `ecamp_pos_embed_grad` (one fixed-order pass over dx = bf16 [B, 197, 768]: the gradients of pos_embed, cls_token and the patch
+     embedding's bias) beside the two `ecamp_colsum` calls it replaces in StemFn.backward (two passes with float atomics: bias and
+     cls_token only) and a plain device copy of the same bytes, alternating in one loop.
+  8  the whole fine-tune step of leg 1 without and with `train_pos_embed` on TWO models of equal weights with an optimizer each (the
+     arena's layout differs), blocks of `--iters` steps alternating between them.  The model without the flag runs the code of the
+     commit before the flag existed, launch for launch.
+  `--parity_log FILE`: the "[pos_embed]" lines that tests/test_posembed_*_gpu.py print under `pytest -s` are copied behind the timings.
 """
 import argparse
 import os
@@ -154,6 +164,95 @@ def droppath_leg(args, say):
                 say("   " + line.strip().lstrip(".").strip())
 
 
+def pos_embed_leg(args, say):
+    """Legs 7 and 8 (see the module docstring)."""
+    from ecamp_amd import engine_finetune
+    from ecamp_amd import hip_ops as ops
+    from ecamp_amd.module.classifier import build_classifier
+    dev = torch.device("cuda")
+    C, T, D = args.classes, 197, 768
+    say("a trained pos_embed on %s: ViT-B/16 in bf16, R = 224, %d classes" % (torch.cuda.get_device_name(0), C))
+    say("7  the stem's row-sum gradients from dx = bf16 [B, %d, %d], per call, from event pairs around 20 calls, alternating in one loop (%d groups after "
+        "%d warm-up groups).  pos_embed_grad: ONE read of dx, fixed order, three gradients (dpos, dcls, dbias), its workspace from the caching "
+        "allocator as in the product; 2 x colsum: TWO reads of dx, float atomics, two gradients (dbias, dcls) -- what StemFn.backward runs without "
+        "the flag; device copy: one read and one write of the same bytes" % (T, D, args.iters, args.warmup))
+    for B in [int(b) for b in args.batches.split(",")]:
+        dx = torch.randn(B, T, D, device=dev).to(torch.bfloat16)
+        dx2 = dx.view(B * T, D)
+        dst = torch.empty_like(dx)
+        dpos, dcls, dbias = ops.zeros((T, D), dev), ops.zeros((D,), dev), ops.zeros((D,), dev)
+        nbytes = dx.numel() * 2
+
+        def peg():
+            ops.pos_embed_grad(dx, dpos, dcls, dbias)
+
+        def colsums():
+            ops.colsum(dx2, dbias, period=T, lo=1, hi=T)
+            ops.colsum(dx2, dcls, period=T, lo=0, hi=1)
+
+        us = event_groups([("pos_embed_grad", peg), ("2 x colsum", colsums), ("device copy", lambda: dst.copy_(dx))], args.iters, args.warmup, 20)
+        say("   B = %3d: dx = %.1f MB (with the copy's destination %s the 256 MB last-level cache: %s)"
+            % (B, nbytes / 1e6, "inside" if 2 * nbytes < 256e6 else "beyond", "the rates are not HBM rates" if 2 * nbytes < 256e6 else "HBM rates"))
+        med_c = stats(us["2 x colsum"])[0]
+        for name, reads in (("pos_embed_grad", 1.0), ("2 x colsum", 2.0), ("device copy", 1.0)):
+            med_u, lo_u, hi_u = stats(us[name])
+            say("     %-15s median %7.1f us (min %.1f, max %.1f) = %.2f x the two colsums; %.0f read%s of dx = %.0f GB/s read"
+                % (name, med_u, lo_u, hi_u, med_u / med_c, reads, "" if reads == 1 else "s", reads * nbytes / (med_u * 1e-6) / 1e9))
+        med_k = stats(us["pos_embed_grad"])[0]
+        say("     pos_embed_grad against the two colsums it replaces: %+.1f us (%s)" % (med_k - med_c, "faster" if med_k < med_c else "SLOWER"))
+        del dx, dx2, dst
+
+    step_args = argparse.Namespace(learning_rate=3e-2, weight_decay=1e-4, decay_type="cosine", warmup_steps=50, num_steps=3000, max_grad_norm=1.0)
+    models = {}
+    for flag in (False, True):
+        torch.manual_seed(0)
+        clf = build_classifier("vit_base_patch16", C, True, img_size=224, compute_dtype=torch.bfloat16, train_encoder=True, train_pos_embed=flag).to(dev)
+        models[flag] = (clf, engine_finetune.make_optimizer(clf, step_args))
+    say("8  the whole fine-tune step (forward + backward + clip + SGD) without and with train_pos_embed: two models of equal initial weights, an optimizer "
+        "each, blocks of %d steps alternating between them, host clock around a block that ends in a device synchronise, 5 blocks each after %d warm-up "
+        "steps each.  `off` runs the launches of the commit before the flag existed" % (args.iters, args.warmup))
+    for B in [int(b) for b in args.batches.split(",")]:
+        imgs = torch.randn(B, 3, 224, 224, device=dev)
+        y = (torch.rand(B, C, device=dev) < 0.3).float()
+        n = {False: 0, True: 0}
+
+        def block(flag, steps):
+            clf, opt = models[flag]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                engine_finetune.train_step(clf, opt, imgs, y, n[flag], step_args)
+                n[flag] += 1
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / steps
+
+        for flag in (False, True):
+            block(flag, args.warmup)
+        ms = {False: [], True: []}
+        for _ in range(5):
+            for flag in (False, True):
+                ms[flag].append(1e3 * block(flag, args.iters))
+        m0, lo0, hi0 = stats(ms[False])
+        m1, lo1, hi1 = stats(ms[True])
+        say("   B = %3d  off: %.2f ms (min %.2f, max %.2f) = %.0f images/s;  on: %.2f ms (min %.2f, max %.2f) = %.0f images/s;  "
+            "a trained pos_embed costs %+.2f ms = %+.2f %% (block-to-block spread of `off`: %.2f ms)"
+            % (B, m0, lo0, hi0, B / (m0 * 1e-3), m1, lo1, hi1, B / (m1 * 1e-3), m1 - m0, 100.0 * (m1 - m0) / m0, hi0 - lo0))
+        del imgs, y
+    earlier = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "finetune_droppath.txt")
+    if os.path.exists(earlier):
+        say("   the same step as the commit before the flag measured it (profiles/finetune_droppath.txt, leg 5, its `rate 0` blocks: the same model, "
+            "optimizer and shapes, another run on another day):")
+        for line in open(earlier):
+            if "rate 0:" in line:
+                say("     " + line.strip().split(";  rate 0.1")[0])
+    if args.parity_log:
+        say("9  the GPU tests' own figures (tests/test_posembed_kernel_gpu.py: worst |got - exact| over the derived bound; tests/test_posembed_model_gpu.py: "
+            "ecamp_tiny, B = 4, float64 reference with pos_embed trained):")
+        for line in open(args.parity_log):
+            if "[pos_embed]" in line:
+                say("   " + line[line.index("[pos_embed]"):].strip())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
@@ -163,10 +262,24 @@ def main():
     ap.add_argument("--out", type=str, default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "finetune.txt"))
     ap.add_argument("--droppath", action="store_true", help="run the stochastic-depth leg instead (profiles/finetune_droppath.txt)")
     ap.add_argument("--droppath_out", type=str, default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "finetune_droppath.txt"))
-    ap.add_argument("--parity_log", type=str, default="", help="--droppath: a `pytest -s` log of tests/test_droppath_model_gpu.py whose [droppath] lines are copied")
+    ap.add_argument("--parity_log", type=str, default="", help="--droppath / --pos_embed: a `pytest -s` log of that leg's GPU tests whose [droppath] / [pos_embed] lines are copied")
+    ap.add_argument("--pos_embed", action="store_true", help="run the trained-pos_embed leg instead (profiles/finetune_pos_embed.txt)")
+    ap.add_argument("--pos_embed_out", type=str, default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "finetune_pos_embed.txt"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("finetune_bench needs an MI355X: nothing here can be measured on a CPU")
+    if args.pos_embed:
+        lines = []
+
+        def say_pe(msg):
+            print(msg, flush=True)
+            lines.append(msg)
+
+        pos_embed_leg(args, say_pe)
+        os.makedirs(os.path.dirname(os.path.abspath(args.pos_embed_out)), exist_ok=True)
+        with open(args.pos_embed_out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     if args.droppath:
         lines = []
 
