@@ -138,6 +138,7 @@ class ParamArena(FlatSpace):
             p._ecamp_arena = self
         self.unused = [i for i, p in enumerate(self.params) if getattr(p, "_ecamp_unused", False)]
         self.on_ready = None  # callback(list of slot ids) set by the data-parallel reducer
+        self.deferred = None  # a list that ready() appends to instead of reporting, while a weight-gradient block is open (functions._wgrad_block)
         self.reducer = None   # the GradReducer itself (parallel.DistributedDataParallel): the loss scaler / optimizer check it
         # Lazy zero_grad: a weight matrix whose gradient is produced by ONE weight-gradient GEMM per backward pass is never zeroed --
         # the first GEMM after zero_grad() OVERWRITES it (no 733 MB memset, no read of the zeros); everything else (biases, LayerNorm,
@@ -299,5 +300,7 @@ class ParamArena(FlatSpace):
         self._fresh = set(self._gemm_written) - set(self.unused)
 
     def ready(self, *ps):
-        if self.on_ready is not None:
+        if self.deferred is not None:
+            self.deferred.extend(ps)
+        elif self.on_ready is not None:
             self.on_ready([self.index[id(p)] for p in ps])

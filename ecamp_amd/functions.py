@@ -21,6 +21,7 @@ Linear probe (paths relative to ECAMP/Fine-tuning/Classification/; module/classi
   PoolNormFn    models_vit.py:92-93 (fine-tuning: the pooled features with their backward)
 """
 import math
+import os
 
 import torch
 
@@ -31,33 +32,43 @@ def _none(n):
     return (None,) * n
 
 
-_BLOCK = None   # [arena, [(dy, x, gw, gb, accumulate)], [parameters reported ready], first group issued] while a block's backward collects its weight gradients
+_BLOCK = None   # the _wgrad_block whose backward is collecting its weight gradients
 
 
 class _wgrad_block:
-    """`with _wgrad_block(arena):` around the backward of one transformer block: its weight gradients (2-4 linear layers over the
-    same rows) are collected and issued as ONE grouped launch on the side stream when the block's backward has been queued
-    (ops.wgrad_group_async; per-layer launches when the group does not qualify).  `arena.ready(...)` calls made inside are held
-    back until then: the data-parallel reducer may only see a parameter once its gradient GEMM is in a stream."""
+    """`with _wgrad_block(arena):` around the backward of one transformer block: its weight gradients (2-4 linear layers over the same
+    rows) are collected and issued as ONE grouped launch on the weight-gradient stream (ops.wgrad_group_async; per-layer launches when
+    the group does not qualify) the moment the FOURTH is collected -- in VitBlockFn right behind the qkv layer's, ahead of the last
+    data-gradient GEMM and the LayerNorm backward -- and whatever is pending at exit (a block of fewer than four; layers past the fourth)
+    is issued there.  The measured step is the step with that early issue.  `arena.ready(...)` calls made inside are held back by the
+    arena (`arena.deferred`) and forwarded once at exit, in call order, behind the last issue: the data-parallel reducer may only see a
+    parameter once its gradient GEMM is in a stream.  After an exception nothing is issued and nothing is reported."""
 
     def __init__(self, arena):
-        self.arena = arena
+        self.arena, self.items, self.ready, self.prev = arena, [], [], None
 
     def __enter__(self):
         global _BLOCK
-        self.prev, _BLOCK = _BLOCK, [self.arena, [], [], False]
-        self._ready = self.arena.ready
-        self.arena.ready = lambda *ps, _b=_BLOCK: _b[2].extend(ps)
+        self.prev, _BLOCK = _BLOCK, self
+        self.outer_ready, self.arena.deferred = self.arena.deferred, self.ready
         return self
+
+    def collect(self, item):
+        self.items.append(item)
+        if len(self.items) == 4:
+            self.issue()
+
+    def issue(self):
+        _issue(self.items)
+        del self.items[:]
 
     def __exit__(self, et, ev, tb):
         global _BLOCK
-        blk, _BLOCK = _BLOCK, self.prev
-        del self.arena.ready          # back to the class method
+        _BLOCK, self.arena.deferred = self.prev, self.outer_ready
         if et is None:
-            _issue(blk[1])
-            if blk[2]:
-                self.arena.ready(*blk[2])
+            self.issue()
+            if self.ready:
+                self.arena.ready(*self.ready)   # (to the enclosing block's list, if there is one)
         return False
 
 
@@ -69,10 +80,7 @@ def _issue(items, workgroups=0):
             ops.linear_wgrad_async(dy, x, gw, gb=gb, accumulate=acc)
 
 
-_MLM_CHUNK_ROWS = int(__import__("os").environ.get("ECAMP_MLM_CHUNK_ROWS", "0"))   # > 0: MlmHeadFn._chunked (the decoder + CE + its backward, `rows` at a time)
-_FIRST_GROUP = int(__import__("os").environ.get("ECAMP_WGRAD_GROUP_SIZE", "4"))   # layers in a block's first launch, issued as soon as they
-# are collected (1: the first layer alone, 2: the MLP pair, 4: nothing early -- the whole block as ONE launch when its backward has been queued;
-# with the segment-major item table of round 3 that measured 38.3 against 38.65 ms per step for the pair launches, same box)
+_MLM_CHUNK_ROWS = int(os.environ.get("ECAMP_MLM_CHUNK_ROWS", "0"))   # > 0: MlmHeadFn._chunked (the decoder + CE + its backward, `rows` at a time)
 
 
 def _wgrad(A, dy, x, w, gb=None, alpha_dev=None, shape=None):
@@ -80,12 +88,8 @@ def _wgrad(A, dy, x, w, gb=None, alpha_dev=None, shape=None):
     the gradient arena -- overwriting on the first backward after zero_grad(), accumulating afterwards (ParamArena.gradw) -- and
     db += column sums of dy inside the same GEMM.  Inside a `_wgrad_block` it joins the block's grouped launch."""
     gw, acc = A.gradw(w, shape)
-    if _BLOCK is not None and _BLOCK[0] is A and alpha_dev is None and len(_BLOCK[1]) < 4:
-        _BLOCK[1].append((dy, x, gw, gb, acc))
-        if not _BLOCK[3] and len(_BLOCK[1]) == _FIRST_GROUP:
-            _BLOCK[3] = True
-            _issue(_BLOCK[1])
-            del _BLOCK[1][:]
+    if _BLOCK is not None and _BLOCK.arena is A and alpha_dev is None:
+        _BLOCK.collect((dy, x, gw, gb, acc))
         return
     ops.linear_wgrad_async(dy, x, gw, alpha_dev=alpha_dev, gb=gb, accumulate=acc)
 

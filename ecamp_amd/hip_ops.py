@@ -2,10 +2,11 @@
 (`torch.empty`) and the current HIP stream handle; every FLOP / byte moved below happens in libecamp_hip.so.
 No CPU fallback exists: CPU tensors raise."""
 import ctypes
+import os
 
 import torch
 
-from . import _lib
+from . import _lib, streams
 from ._lib import BF16, F32, call
 
 _I64x3 = ctypes.c_int64 * 3
@@ -189,7 +190,7 @@ def linear_wgrad(dy, x, gw, alpha=1.0, alpha_dev=None, gb=None, accumulate=True)
          accumulate=bool(accumulate), split_k=_split_k(N, K, M, dy.dtype), rowsum=gb)
 
 
-WGRAD_GROUP = __import__("os").environ.get("ECAMP_WGRAD_GROUP", "1") != "0"   # one launch per transformer block for its weight gradients
+WGRAD_GROUP = os.environ.get("ECAMP_WGRAD_GROUP", "1") != "0"   # one launch per transformer block for its weight gradients
 
 
 def wgrad_group_supported(items):
@@ -826,169 +827,30 @@ def loss_scale_update(sumsq_, state, opt_step, ctl, norm_out, growth, backoff, i
 # --------------------------------------------------------------------------------------------- side-stream weight gradients
 # Weight gradients are leaves of the backward dependency graph: nothing in backward waits for them.  Launching them on a
 # second HIP stream lets their workgroups fill the tail-quantisation gaps of the dgrad / attention / LayerNorm kernels on the
-# main stream (and vice versa).  The main stream re-joins at the end of backward (autograd engine callback).
-OVERLAP_WGRAD = __import__("os").environ.get("ECAMP_OVERLAP_WGRAD", "1") != "0"
-_side = {}
-
-
-def side_stream(device):
-    st = _side.get(device)
-    if st is None:
-        st = _side[device] = torch.cuda.Stream(device=device)
-    return st
-
-
-def _join_side():
-    dev = torch.cuda.current_device()
-    for key in (torch.device("cuda", dev), ("branch", dev)):
-        st = _side.get(key)
-        if st is not None:
-            torch.cuda.current_stream().wait_stream(st)
-    _side["cb"] = False
-
+# main stream (and vice versa).  The main stream re-joins at the end of backward (streams.on_wgrad_stream: stream, held operands, join).
+OVERLAP_WGRAD = os.environ.get("ECAMP_OVERLAP_WGRAD", "1") != "0"
 
 # The image decoder + pixel losses and the report side both hang off the encoder's latent and nothing else: run on two streams,
 # the workgroups of one fill the tail rounds of the other's persistent GEMMs (forward AND backward: autograd replays each
 # stage's backward on the stream its forward ran on).  Measured on MI355X at B=256, same-box A/B of 30-step runs on three boxes
 # (round 3, after the phase-schedule GEMM and the one-launch-per-block weight gradients): step 37.4-37.5 -> 36.6-36.65 ms, forward
 # 14.3 -> 14.0, forward+backward 35.9 -> 35.1 (in round 2 the same switch bought 0.15 ms: the slower GEMMs left fewer gaps that
-# the weight-gradient stream did not already fill).  On by default; ECAMP_OVERLAP_BRANCHES=0 serialises the two branches.
-OVERLAP_BRANCHES = __import__("os").environ.get("ECAMP_OVERLAP_BRANCHES", "1") != "0"
-
-
-def side_streams(device):
-    """Every stream other than the main one that may hold unfinished gradient work of `device` (wgrad side stream, branch stream)."""
-    idx = torch.device(device).index if torch.device(device).index is not None else torch.cuda.current_device()
-    out = []
-    for key in (torch.device("cuda", idx), ("branch", idx)):
-        st = _side.get(key)
-        if st is not None:
-            out.append(st)
-    return out
-
-
-def branch_stream(device):
-    key = ("branch", torch.device(device).index if torch.device(device).index is not None else torch.cuda.current_device())
-    st = _side.get(key)
-    if st is None:
-        st = _side[key] = torch.cuda.Stream(device=device)
-    return st
-
-
-# ---- tensors a second stream reads ------------------------------------------------------------------------------------------------
-# `t.record_stream(side)` hands the question "when may this block be reused?" to the caching allocator: it answers with an event and keeps
-# the block out of circulation until a LATER allocation call finds the event complete.  Which call that is depends on how far the host
-# runs ahead of the GPU at that moment, so the allocator's steady state never quite arrives: round 6's bench record showed hipMalloc calls
-# inside the timed steps in every run (7-107 even with the host's lead bounded), and one burst of them on a fresh box cost the host 87 ms
-# and the GPU a step of 2x the median.  Instead the tensors are HELD here (a Python reference) until events recorded behind the step on
-# every stream have completed, then dropped: the block goes back to the allocator the ordinary way, reusable at once by its own stream, and
-# the step's allocation pattern is the same every step.  `seal()` is called where a step ends (FusedAdamW.pace) and by `hold` itself every
-# 512 tensors or 8 GB (loops that never reach an optimizer); `reap()` drops what the GPU has finished.  ECAMP_HOLD_TENSORS=0: record_stream as before.
-HOLD_TENSORS = __import__("os").environ.get("ECAMP_HOLD_TENSORS", "1") != "0"
-_held_cur = []
-_held_done = __import__("collections").deque()   # ([events], [tensors], bytes) in seal order
-_held_bytes = 0                                   # bytes of the sealed sets still held
-_cur_bytes = 0                                    # bytes of the open set
-_cur_readers = []                                 # the streams named as readers of the open set (hold's first argument)
-
-
-def held_bytes():
-    """Bytes of the tensors held behind steps the GPU has not finished (FusedAdamW.pace lets the host run fewer steps ahead when that is large)."""
-    return _held_bytes
-
-
-def hold(st, *tensors):
-    """`st` (a side stream) reads `tensors`, which live in another stream's pool: keep them alive until that has happened.  Contract: every
-    read of them by `st` has ALREADY been queued when this is called (the weight-gradient launches) -- a tensor that a side stream reads again
-    later (the branch stream's backward nodes) must use record_stream, whose event is taken when the tensor is freed."""
-    if not HOLD_TENSORS:
-        for t in tensors:
-            if t is not None:
-                t.record_stream(st)
-        return
-    global _cur_bytes
-    if all(st is not r for r in _cur_readers):
-        _cur_readers.append(st)
-    for t in tensors:
-        if t is not None:
-            _held_cur.append(t)
-            _cur_bytes += t.numel() * t.element_size()
-    if len(_held_cur) >= 512 or _cur_bytes > (8 << 30):   # loops that never reach an optimizer step (evaluation, tests): bounded all the same
-        seal()
-    elif _held_done and (len(_held_cur) & 31) == 0:
-        reap()
-
-
-def seal():
-    """Close the current set of held tensors behind an event on every stream that may read them (main, weight-gradient, branch); drop the
-    sets whose events have all completed."""
-    global _held_cur, _held_bytes, _cur_bytes
-    if _held_cur:
-        dev = _held_cur[0].device
-        evs = []
-        streams = [torch.cuda.current_stream(dev)]
-        for st in list(_cur_readers) + side_streams(dev):   # every stream named as a reader, and the side streams whatever was named
-            if all(st is not q and st != q for q in streams):
-                streams.append(st)
-        for st in streams:
-            ev = torch.cuda.Event()
-            ev.record(st)
-            evs.append(ev)
-        del _cur_readers[:]
-        _held_done.append((evs, _held_cur, _cur_bytes))
-        _held_bytes += _cur_bytes
-        _held_cur, _cur_bytes = [], 0
-    reap()
-
-
-def reap(block_first=False):
-    """Drop held sets the GPU is done with (oldest first).  block_first: wait for the oldest one (tests)."""
-    global _held_bytes
-    while _held_done:
-        evs, _, nb = _held_done[0]
-        if block_first:
-            for e in evs:
-                e.synchronize()
-            block_first = False
-        if not all(e.query() for e in evs):
-            break
-        _held_done.popleft()
-        _held_bytes -= nb
+# the weight-gradient stream did not already fill).  On by default; ECAMP_OVERLAP_BRANCHES=0 serialises the two branches
+# (ECAMP.forward: streams.fork_branch / join_branch).
+OVERLAP_BRANCHES = os.environ.get("ECAMP_OVERLAP_BRANCHES", "1") != "0"
 
 
 def wgrad_group_async(items, workgroups=0):
-    """wgrad_group on the weight-gradient side stream (see linear_wgrad_async)."""
+    """wgrad_group on the weight-gradient stream (see linear_wgrad_async)."""
     if not OVERLAP_WGRAD:
         return wgrad_group(items, workgroups=workgroups)
-    dev = items[0][0].device
-    st = side_stream(dev)
-    st.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(st):
-        wgrad_group(items, workgroups=workgroups)
-    for dy, x, _, _, _ in items:
-        hold(st, dy, x)
-    if not _side.get("cb"):
-        try:
-            torch.autograd.Variable._execution_engine.queue_callback(_join_side)
-            _side["cb"] = True
-        except RuntimeError:  # not inside a backward pass: join immediately
-            _join_side()
+    streams.on_wgrad_stream(items[0][0].device, lambda: wgrad_group(items, workgroups=workgroups), [(dy, x) for dy, x, _, _, _ in items])
 
 
 def linear_wgrad_async(dy, x, gw, alpha=1.0, alpha_dev=None, gb=None, accumulate=True):
     if not OVERLAP_WGRAD:
         return linear_wgrad(dy, x, gw, alpha, alpha_dev, gb, accumulate)
-    st = side_stream(dy.device)
-    st.wait_stream(torch.cuda.current_stream())  # dy, x (and earlier accumulations into gw) are ready
-    with torch.cuda.stream(st):
-        linear_wgrad(dy, x, gw, alpha, alpha_dev, gb, accumulate)
-    hold(st, dy, x, alpha_dev)  # the caching allocator must not recycle these while the side stream reads them
-    if not _side.get("cb"):
-        try:
-            torch.autograd.Variable._execution_engine.queue_callback(_join_side)
-            _side["cb"] = True
-        except RuntimeError:  # not inside a backward pass: join immediately
-            _join_side()
+    streams.on_wgrad_stream(dy.device, lambda: linear_wgrad(dy, x, gw, alpha, alpha_dev, gb, accumulate), [(dy, x, alpha_dev)])
 
 
 # --------------------------------------------------------------------------------------------- dataset image transform on the device

@@ -388,22 +388,15 @@ class ECAMP(nn.Module):
                 xd = VitBlockFn.apply(xd, blk, self, B, self.num_patches + 1, self.decoder_num_heads)
             return ImgLossFn.apply(xd, imgs, big, mask, column, row, self, B)
 
-        from .. import hip_ops as ops
+        from .. import hip_ops as ops, streams
         if image_side_only:
             img_losses = image_decoder()
             return img_losses[0], img_losses[1], None, None
         if ops.OVERLAP_BRANCHES and latent.is_cuda:
-            # the two consumers of `latent` on two streams (see hip_ops.branch_stream)
-            main, bs = torch.cuda.current_stream(dev), ops.branch_stream(dev)
-            bs.wait_stream(main)
-            with torch.cuda.stream(bs):
-                img_losses = image_decoder()
-            for t in (latent, imgs, big, mask, ids_restore, ids_keep, column, row):
-                t.record_stream(bs)   # (not hip_ops.hold: the branch's BACKWARD nodes read these again on `bs`, later than any fence taken here)
+            # the two consumers of `latent` on two streams (streams.fork_branch / join_branch)
+            img_losses = streams.fork_branch(dev, image_decoder, (latent, imgs, big, mask, ids_restore, ids_keep, column, row))
             mlm_loss = self.forward_report_decoder(latent, ids_keep, ids, labels, attention_mask, type_ids, weights, B, T, eval_head=eval_head)
-            main.wait_stream(bs)
-            for t in img_losses:   # three scalars allocated on the branch stream and read by the CALLER on the main one, later than any point this
-                t.record_stream(main)   # function could fence: the allocator's own bookkeeping (no effect on its steady state at this size)
+            streams.join_branch(dev, img_losses)
         else:
             img_losses = image_decoder()
             mlm_loss = self.forward_report_decoder(latent, ids_keep, ids, labels, attention_mask, type_ids, weights, B, T, eval_head=eval_head)

@@ -7,6 +7,7 @@ import os
 import torch
 
 from . import hip_ops as ops
+from .streams import held
 
 # How many (micro-)steps the host may queue ahead of the GPU.  The host queues a step in ~15 ms, the GPU runs it in ~36: unbounded, the
 # host's lead grows by 20 ms per step, and every tensor a side stream reads (record_stream: the weight-gradient stream's x and dy, i.e.
@@ -15,7 +16,7 @@ from . import hip_ops as ops
 # a small lead (BENCH_r05's 40.7 ms mean).  Two steps in flight keep the GPU fed through a host hiccup of ~70 ms and reach their steady state within a 5-step warm-up
 # (three: +35 ms of slack, but the lead is still growing when the driver's timed region starts).  0 = unbounded (the old behaviour).
 MAX_STEPS_IN_FLIGHT = int(os.environ.get("ECAMP_MAX_STEPS_IN_FLIGHT", "2"))
-# ... and fewer than that (never fewer than one) while the tensors held for the side streams (hip_ops.hold: ~21 GB per step at B = 256) pass this
+# ... and fewer than that (never fewer than one) while the tensors held for the side streams (streams.Held: ~21 GB per step at B = 256) pass this
 MAX_HELD_BYTES = int(float(os.environ.get("ECAMP_MAX_HELD_GB", "96")) * 2 ** 30)
 
 
@@ -51,16 +52,16 @@ class _FlatOptimizer(torch.optim.Optimizer):
         MAX_STEPS_IN_FLIGHT back has finished on the GPU (see MAX_STEPS_IN_FLIGHT).  No device-wide synchronisation."""
         if not torch.cuda.is_available():
             return
-        ops.seal()   # tensors the side streams read during this step: held until the GPU is past here (hip_ops.hold)
+        held.seal()   # tensors the second streams read during this step: held until the GPU is past here (streams.Held)
         if MAX_STEPS_IN_FLIGHT <= 0:
             return
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream())
         self._inflight.append(ev)
-        while len(self._inflight) > MAX_STEPS_IN_FLIGHT or (len(self._inflight) > 1 and ops.held_bytes() > MAX_HELD_BYTES):
+        while len(self._inflight) > MAX_STEPS_IN_FLIGHT or (len(self._inflight) > 1 and held.bytes > MAX_HELD_BYTES):
             self._inflight.popleft().synchronize()
-            ops.reap()
-        ops.reap()   # the step that wait was for is complete: its held tensors go back to the allocator now
+            held.reap()
+        held.reap()   # the step that wait was for is complete: its held tensors go back to the allocator now
 
     @property
     def arena(self):

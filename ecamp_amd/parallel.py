@@ -23,6 +23,8 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
+from . import streams
+
 # RCCL runs one workgroup per channel beside the backward pass.  A spinning co-tenant of 16 / 32 / 64 / 96 workgroups costs the step
 # +1.6 / +1.7 / +1.9 / +2.9 ms and 128 workgroups +13 ms (a cliff: no CU is left without a resident stranger;
 # profiles/r03_cotenant_ab.txt, two boxes), while the exchange has 22 ms of backward to hide 4.8-15.2 ms of link time in -- so the
@@ -113,7 +115,6 @@ class GradReducer:
         # gloo on device tensors (two ranks sharing ONE GPU in the model-level equivalence test; RCCL refuses duplicate devices):
         # buckets are staged through host memory, synchronously -- a test / debugging path, never the production one
         self.host_staged = backend == "gloo" and flat_g.is_cuda
-        self._cb_queued = False
         self.main_stream = None   # the step's compute stream (set by the wrapper's forward); the collectives also wait for it
         self.timing = False       # record event pairs around every collective (bench.py's `rccl` record)
         self.after_bucket = None  # callback(lo, hi, slots), run right behind a bucket's collective on the stream that carries it (with a
@@ -133,7 +134,6 @@ class GradReducer:
         self.pending = [sum(1 for s in sl if s not in self.unused) for (_, _, sl) in self.buckets]
         self.launched = [False] * len(self.buckets)
         self.works = []
-        self._cb_queued = False
 
     def _launch(self, b):
         comm = not (self.world == 1 and not self.force_comm)
@@ -145,11 +145,10 @@ class GradReducer:
         buf = self.flat_g[lo:hi]
         op = dist.ReduceOp.AVG if self.use_avg else dist.ReduceOp.SUM
         if self.host_staged:
-            from . import hip_ops
             cur = torch.cuda.current_stream()
             if self.main_stream is not None and self.main_stream != cur:
                 cur.wait_stream(self.main_stream)
-            for wst in hip_ops.side_streams(self.flat_g.device):
+            for wst in streams.others(self.flat_g.device):
                 cur.wait_stream(wst)
             host = buf.cpu() if self.grad_dtype is None else buf.to(self.grad_dtype).cpu()
             dist.all_reduce(host, op=op, group=self.group)
@@ -169,8 +168,7 @@ class GradReducer:
             self.side.wait_stream(cur)
             if self.main_stream is not None and self.main_stream != cur:
                 self.side.wait_stream(self.main_stream)
-            from . import hip_ops
-            for wst in hip_ops.side_streams(self.flat_g.device):
+            for wst in streams.others(self.flat_g.device):
                 self.side.wait_stream(wst)
             with torch.cuda.stream(self.side):
                 t0 = None
@@ -228,14 +226,9 @@ class GradReducer:
         if not self.enabled:
             return
         self.dirty = True
-        if not self._cb_queued:
-            self._cb_queued = True
-            try:
-                torch.autograd.Variable._execution_engine.queue_callback(self.finalize)
-            except RuntimeError:
-                # not inside a backward pass (unit tests drive finalize() themselves).  `dirty` stays set: the loss scaler calls
-                # finalize() before the gradients are read, and FusedAdamW refuses to step on an un-reduced arena (assert_reduced)
-                self._cb_queued = False
+        # outside a backward pass nothing is queued (unit tests drive finalize() themselves).  `dirty` stays set: the loss scaler calls
+        # finalize() before the gradients are read, and FusedAdamW refuses to step on an un-reduced arena (assert_reduced)
+        streams.at_backward_end(self.finalize)
         for s in slots:
             if s in self.unused:
                 continue

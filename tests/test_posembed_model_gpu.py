@@ -247,6 +247,25 @@ def test_a_built_arena_without_the_table_is_refused_and_masking_is_refused(dev):
         x.float().sum().backward()
 
 
+def test_the_pass_after_a_backward_that_raised_joins_the_weight_gradient_stream_once(dev, monkeypatch):
+    """The refused masked pass above launches the stem's weight gradient on the weight-gradient stream, asks for the join at the end of
+    the pass and then raises: the engine drops that callback.  The next, ordinary pass must ask again and be joined exactly once
+    (streams.at_backward_end remembers the pass, not a flag that only the dropped callback would have cleared)."""
+    from ecamp_amd import hip_ops, streams
+    from ecamp_amd.functions import StemFn
+    monkeypatch.setattr(hip_ops, "OVERLAP_WGRAD", True)
+    clf = R.build(torch.float32, dev)
+    m = clf.encoder
+    m.prepare()
+    x = StemFn.apply(R.imgs(2).to(dev), None, m, 0.75, m.cls_token)[0]
+    with pytest.raises(RuntimeError, match="every patch kept in place"):
+        x.float().sum().backward()
+    joins, join = [], streams.join
+    monkeypatch.setattr(streams, "join", lambda: (joins.append(1), join())[1])
+    R.backward(clf)
+    assert len(joins) == 1
+
+
 # ---------------------------------------------------------------------------------------------------------------- the driver
 def test_driver_trains_the_table_writes_it_and_tests_the_checkpoint(dev, tmp_path):
     from ecamp_amd import main_finetune

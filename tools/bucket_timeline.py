@@ -6,7 +6,7 @@ usage: bucket_timeline.py [bucket_mb [tail_bucket_mb [tail_span_mb]]]   (default
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from ecamp_amd import optim, hip_ops
+from ecamp_amd import optim, streams
 from ecamp_amd.data import synthetic_batch
 from ecamp_amd.module import model_ecamp
 from ecamp_amd.parallel import DistributedDataParallel
@@ -36,7 +36,7 @@ def stamp(tag):
     probe.wait_stream(cur)
     if red.main_stream is not None:
         probe.wait_stream(red.main_stream)
-    for s in hip_ops.side_streams(dev):
+    for s in streams.others(dev):
         probe.wait_stream(s)
     e = torch.cuda.Event(enable_timing=True)
     e.record(probe)

@@ -8,4 +8,4 @@ run() {
 import json,sys
 r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(r['value'], r['ms_per_step'], r['step_ms']['max'], r['roofline']['gemm_ms_per_step'], r['roofline']['serialized_ms_per_step'])"
 }
-for s in "X=default" "ECAMP_OVERLAP_WGRAD=0" "ECAMP_OVERLAP_BRANCHES=0" "X=default" "ECAMP_WGRAD_GROUP=0" "ECAMP_GELU_SAVED_GRAD=0" "X=default" "ECAMP_HOLD_TENSORS=0" "ECAMP_MAX_STEPS_IN_FLIGHT=0" "ECAMP_FUSED_GRAD_NORM=0" "X=default"; do run "$s"; done
+for s in "X=default" "ECAMP_OVERLAP_WGRAD=0" "ECAMP_OVERLAP_BRANCHES=0" "X=default" "ECAMP_WGRAD_GROUP=0" "ECAMP_GELU_SAVED_GRAD=0" "X=default" "ECAMP_MAX_STEPS_IN_FLIGHT=0" "ECAMP_FUSED_GRAD_NORM=0" "X=default"; do run "$s"; done
