@@ -493,6 +493,13 @@ extern "C" int ecamp_sumsq_grouped(const float* g, const uint8_t* block_group, i
 // with ecamp_adamw_grouped's block table.  Every workgroup adds partials[0 .. npart) itself -- a few thousand floats from L2, in one
 // order: thread t takes slots t, t + 256, ... in turn, then the 256 sums go through block_sum_256 -- so every workgroup holds the same
 // bits of the norm and nothing waits for a reduction launch.  A zero momentum buffer reproduces torch's first step (buf = d).
+// (partials_sum_256 is that order, shared with sgd_scale_update_kernel below: the loss scaler's decision and the step see one `s`.)
+__device__ __forceinline__ float partials_sum_256(const float* partials, int npart, float* sh) {
+    float s = 0.f;
+    for (int k = threadIdx.x; k < npart; k += 256) s += partials[k];
+    return block_sum_256(s, sh);
+}
+
 __global__ __launch_bounds__(256) void sgd_grouped_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
                                                           bf16_t* __restrict__ p16, const unsigned char* __restrict__ grp, long n4, GroupHyper hp,
                                                           float momentum, float max_norm, const float* __restrict__ partials, int npart,
@@ -502,9 +509,7 @@ __global__ __launch_bounds__(256) void sgd_grouped_kernel(float* __restrict__ p,
         if (ctl[1] != 0.f) return;
         gscale = ctl[0];
     }
-    float s = 0.f;
-    for (int k = threadIdx.x; k < npart; k += 256) s += partials[k];
-    s = block_sum_256(s, sh);
+    const float s = partials_sum_256(partials, npart, sh);
     const float norm = sqrtf(s) * gscale;
     const float coef = max_norm > 0.f ? fminf(1.0f, max_norm / (norm + 1e-6f)) : 1.0f;
     if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = norm;
@@ -548,6 +553,54 @@ extern "C" int ecamp_sgd_grouped(float* p, const float* g, float* buf, void* p16
     if (nb > GROUPED_MAX_GRID) nb = GROUPED_MAX_GRID;
     hipLaunchKernelGGL(sgd_grouped_kernel, dim3(nb), dim3(256), 0, stream, p, g, buf, (bf16_t*)p16, block_group, n4, hp, momentum, max_norm, partials,
                        npart, grad_scale, ctl, norm_out);
+    ECAMP_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// apex's LossScaler.update_scale for loss_scale="dynamic" (what `--fp16 --fp16_opt_level O2` puts around the reference's SGD step,
+// train.py:398,452-465), decided on the device from the partials ecamp_sumsq_grouped left over the SCALED gradients: one workgroup adds
+// them in sgd_grouped_kernel's order (partials_sum_256: the same bits of `s` there and here), thread 0 writes the `ctl` that step reads,
+// the norm of the un-scaled gradients and the next state.  state = {scale, clean steps since the last change, steps skipped in total,
+// steps skipped in a row}; the counters are f32, exact to 2^24 steps.  window == 0: a static scale.
+__global__ __launch_bounds__(256) void sgd_scale_update_kernel(const float* __restrict__ partials, int npart, float* __restrict__ state,
+                                                               float* __restrict__ ctl, float* __restrict__ norm_out, float growth, float backoff,
+                                                               float window, float max_scale) {
+    __shared__ float sh[4];
+    const float s = partials_sum_256(partials, npart, sh);
+    if (threadIdx.x != 0) return;
+    const float scale = state[0], inv = 1.0f / scale;
+    const bool found = !(fabsf(s) <= 3.402823466e+38f);   // inf, nan, or finite slots whose sum left f32
+    ctl[0] = inv;
+    ctl[1] = found ? 1.f : 0.f;
+    ctl[2] = 0.f;
+    ctl[3] = 0.f;
+    if (norm_out) norm_out[0] = sqrtf(s) * inv;             // sgd_grouped_kernel's expression under this ctl; inf / nan on overflow
+    if (found) {
+        if (window != 0.f) state[0] = scale * backoff;
+        state[1] = 0.f;
+        state[2] += 1.f;
+        state[3] += 1.f;
+    } else {
+        const float clean = state[1] + 1.f;
+        state[3] = 0.f;
+        if (clean == window) {
+            state[0] = fminf(max_scale, scale * growth);
+            state[1] = 0.f;
+        } else state[1] = clean;
+    }
+}
+
+extern "C" int ecamp_sgd_scale_update(const float* partials, int32_t npart, float* state, float* ctl, float* norm_out, float growth, float backoff,
+                                      int32_t window, float max_scale, hipStream_t stream) {
+    ECAMP_CHECK_ARG(partials && state && ctl, "sgd_scale_update: null pointer");
+    ECAMP_CHECK_ARG(npart >= 1 && npart <= 2 * SUMSQ_MAX_SLOTS, "sgd_scale_update: npart=%d must lie in [1, %d]", npart, 2 * SUMSQ_MAX_SLOTS);
+    ECAMP_CHECK_ARG(growth >= 1.f, "sgd_scale_update: growth=%g must be at least 1", (double)growth);
+    ECAMP_CHECK_ARG(backoff > 0.f && backoff <= 1.f, "sgd_scale_update: backoff=%g must lie in (0, 1]", (double)backoff);
+    ECAMP_CHECK_ARG(window >= 0, "sgd_scale_update: window=%d must not be negative (0: a static scale)", window);
+    ECAMP_CHECK_ARG(max_scale > 0.f, "sgd_scale_update: max_scale=%g must be positive", (double)max_scale);
+    hipLaunchKernelGGL(sgd_scale_update_kernel, dim3(1), dim3(256), 0, stream, partials, npart, state, ctl, norm_out, growth, backoff, (float)window,
+                       max_scale);
     ECAMP_LAUNCH_CHECK();
     return 0;
 }

@@ -52,19 +52,23 @@ def make_optimizer(model, args):
     return torch.optim.SGD(head_parameters(model), lr=args.learning_rate, momentum=0.9, weight_decay=args.weight_decay)
 
 
-def _train_step(model, optimizer, x, y, global_step, args, clip=None):
+def _train_step(model, optimizer, x, y, global_step, args, clip=None, scaler=None):
     """One iteration of train.py:438-465 -> (the loss as a device scalar, the learning rate of this step).  The scheduler is stepped
     before the optimizer (train.py:462-463), so optimizer step k (1-based) runs at learning_rate * factor(k).  `clip()` runs between
     backward and the step, for an optimizer that does not clip inside its step.  (set_to_none: the fused optimizers keep `.grad` as views
-    whatever is asked.)"""
+    whatever is asked.)  `scaler` (optim.SGDLossScaler, engine_finetune's IEEE-half mode): the loss is multiplied by its scale before
+    backward and the optimizer takes `step_scaled(scaler)`; the loss returned is the un-scaled one."""
     loss = model.loss(model(x), y)
-    loss.backward()
+    (loss if scaler is None else scaler.scale_loss(loss)).backward()
     if clip is not None:
         clip()
     lr = args.learning_rate * lr_factor(args.decay_type, global_step + 1, args.warmup_steps, args.num_steps)
     for grp in optimizer.param_groups:
         grp["lr"] = lr
-    optimizer.step()
+    if scaler is None:
+        optimizer.step()
+    else:
+        optimizer.step_scaled(scaler)
     optimizer.zero_grad(set_to_none=True)
     return loss.detach(), lr
 
@@ -117,11 +121,12 @@ def train(model, train_loader, val_loader, args, log=print, writer=None, keep_lo
     return _train(model, train_loader, val_loader, args, log, writer, keep_losses, make_optimizer, train_step)
 
 
-def _train(model, train_loader, val_loader, args, log, writer, keep_losses, make_optimizer, train_step):
+def _train(model, train_loader, val_loader, args, log, writer, keep_losses, make_optimizer, train_step, report=None):
     """train.py:364-509 under the optimizer and step of the calling engine: passes over `train_loader` until `num_steps` optimizer steps
     are done or the validation result has not improved for PATIENCE validations; validation after every pass; the best checkpoint (mean
-    AUROC, ties replace: `<=`; accuracy: `<`) is written in the reference's flat layout.  -> dict(global_step, best, losses (device
-    scalars, keep_losses only))."""
+    AUROC, ties replace: `<=`; accuracy: `<`) is written in the reference's flat layout.  `report(optimizer, log)` (optional) runs where
+    the loop reads the loss anyway, behind its line: an engine's own device values go to the log there.  -> dict(global_step, best, losses
+    (device scalars, keep_losses only))."""
     optimizer = make_optimizer(model, args)
     optimizer.zero_grad(set_to_none=True)
     print_freq = max(1, int(getattr(args, "print_freq", 50)))
@@ -146,6 +151,8 @@ def _train(model, train_loader, val_loader, args, log, writer, keep_losses, make
                 if writer is not None:
                     writer.add_scalar("train/loss", scalar_value=val, global_step=global_step)
                     writer.add_scalar("train/lr", scalar_value=lr, global_step=global_step)
+                if report is not None:
+                    report(optimizer, log)
             if global_step >= t_total:
                 break
         if n_batches == 0:

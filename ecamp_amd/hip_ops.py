@@ -798,6 +798,15 @@ def sgd_grouped(p, g, buf, p16, block_group, lrs, wds, momentum, max_norm, parti
          float(max_norm), ptr(partials), int(npart), float(grad_scale), ptr(ctl), ptr(norm_out), stream())
 
 
+def sgd_scale_update(partials, npart, state, ctl, norm_out, growth, backoff, window, max_scale):
+    """apex's dynamic loss-scale rule around `sgd_grouped`, decided on the device (include/ecamp_hip.h): `partials[0:npart]` are the sums of
+    squares of the SCALED gradients, `state` the device f32[4] {scale, clean steps, skipped, skipped in a row}, `ctl` the device f32[4]
+    `sgd_grouped` then reads, `norm_out` an optional device f32[1] for the norm of the un-scaled gradients.  Nothing is read back."""
+    _chk(partials, state, ctl, norm_out)
+    call("ecamp_sgd_scale_update", ptr(partials), int(npart), ptr(state), ptr(ctl), ptr(norm_out), float(growth), float(backoff), int(window),
+         float(max_scale), stream())
+
+
 # --------------------------------------------------------------------------------------------- optimizer side
 def sumsq(x, out):
     call("ecamp_sumsq", ptr(x), x.numel(), ptr(out), stream())

@@ -15,8 +15,18 @@ reference does (timm's is a parameter: in the SGD, in the clip, in the checkpoin
 `--drop_path_rate 0.1 --train_pos_embed` is the reference's model-side recipe.  The first log line of every run states what deviates from
 the reference: stochastic depth when it is off, and `pos_embed` when it is held fixed.
 
+`--fp16_loss_scale {dynamic,<power of two>}` (default: none) makes `--fp16` / `--compute_dtype fp16` fine-tune in IEEE half, the format of
+the reference's `--fp16 --fp16_opt_level O2`: half activations and 16-bit weight shadows over f32 masters (the head stays f32, where apex
+O2's is half), the loss multiplied by a scale before backward, the gradients un-scaled inside the fused SGD step.  `dynamic` is apex's rule
+from the reference's start of 2^20 (train.py:398): a step whose scaled gradients are not finite is skipped and the scale halved, 2000 clean
+steps in a row double it (at most 2^24); the decision is taken on the device and the schedule advances over a skipped step, as the
+reference's does.  A number is a static scale (a power of two, so that un-scaling is exact).  A run_ft.sh line then needs only
+`--fp16_loss_scale dynamic` (and the list and dataset paths) added.  The log carries the scale and the skipped steps wherever it carries
+the loss; a scale that has fallen below 1 ends the run (the forward pass overflows half: `--f32_residual`).
+
 NOT implemented, and refused with a message before any device work: data-parallel fine-tuning (`--local_rank` other than -1),
-`--gradient_accumulation_steps` other than 1, and `--fp16` (IEEE half with loss scaling): use `--compute_dtype bf16`.
+`--gradient_accumulation_steps` other than 1, and `--fp16` / `--compute_dtype fp16` WITHOUT `--fp16_loss_scale` (IEEE half needs loss
+scaling: opt in, or use `--compute_dtype bf16`).
 """
 import torch
 
@@ -34,7 +44,27 @@ def opening_line(args):
              "stochastic depth IS applied at drop_path_rate=%g, rising linearly over the blocks from 0 (the reference's is 0.1)" % rate)
     pos = ("pos_embed IS trained (as the reference does)" if getattr(args, "train_pos_embed", False) else
            "pos_embed is held fixed at the sin-cos table (the reference trains it)")
-    return "NOTE: %s, and %s" % (depth, pos)
+    line = "NOTE: %s, and %s" % (depth, pos)
+    if getattr(args, "fp16_loss_scale", None) is not None and (getattr(args, "fp16", False) or getattr(args, "compute_dtype", None) == "fp16"):
+        from . import engine_finetune
+        line += ("; IEEE half (fp16) activations and 16-bit weight shadows over f32 masters and an f32 head (apex O2's head is half), under %s; "
+                 "the residual stream is %s" % (engine_finetune.make_scaler(args).describe(),
+                                                "f32 (--f32_residual)" if getattr(args, "f32_residual", False) else "half (--f32_residual keeps it in f32)"))
+    return line
+
+
+def loss_scale_of(text):
+    """`--fp16_loss_scale`: "dynamic", or a static scale 2^k >= 1 (un-scaling by a power of two is exact in f32) -> "dynamic" / float."""
+    if text == "dynamic":
+        return text
+    try:
+        v = float(text)
+    except ValueError:
+        v = 0.0
+    import math
+    if not (1.0 <= v < float("inf")) or math.frexp(v)[0] != 0.5:
+        raise SystemExit("--fp16_loss_scale %s: must be `dynamic` or a positive power of two (1, 2, 4, ... 65536 ...: un-scaling is then exact)" % text)
+    return v
 
 
 def check_args(args):
@@ -45,9 +75,15 @@ def check_args(args):
         raise SystemExit("--local_rank %d: data-parallel fine-tuning is not implemented here; run on one device (--local_rank -1)" % args.local_rank)
     if args.gradient_accumulation_steps != 1:
         raise SystemExit("--gradient_accumulation_steps %d: gradient accumulation is not implemented here (only 1)" % args.gradient_accumulation_steps)
-    if args.fp16 or args.compute_dtype == "fp16":
-        raise SystemExit("--fp16 --mode Finetune is not implemented here (IEEE half needs loss scaling around the fused SGD step): "
-                         "use --compute_dtype bf16 (or fp32)")
+    half = args.fp16 or args.compute_dtype == "fp16"
+    if getattr(args, "fp16_loss_scale", None) is not None:
+        loss_scale_of(args.fp16_loss_scale)
+        if not half:
+            raise SystemExit("--fp16_loss_scale %s with --compute_dtype %s: a loss scale belongs to IEEE half (--fp16 / --compute_dtype fp16); "
+                             "bf16 and fp32 need none" % (args.fp16_loss_scale, args.compute_dtype or "bf16"))
+    elif half:
+        raise SystemExit("--fp16 --mode Finetune is not implemented here without a loss scale (IEEE half needs loss scaling around the fused SGD "
+                         "step): add --fp16_loss_scale dynamic (the reference's apex recipe), or use --compute_dtype bf16 (or fp32)")
     rate = float(getattr(args, "drop_path_rate", 0.0))
     if not 0.0 <= rate < 1.0:
         raise SystemExit("--drop_path_rate %g must lie in [0, 1)" % rate)
@@ -56,7 +92,7 @@ def check_args(args):
 
 def build_model(args):
     from .module.classifier import build_classifier
-    dtype = {"bf16": torch.bfloat16, "fp32": torch.float32}[args.compute_dtype]
+    dtype = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}[args.compute_dtype]
     return build_classifier(args.model, args.num_classes, args.is_multilabel, img_size=args.img_size, pool=args.pool, train_encoder=True,
                             drop_path_rate=getattr(args, "drop_path_rate", 0.0), train_pos_embed=getattr(args, "train_pos_embed", False),
                             compute_dtype=dtype, f32_residual=args.f32_residual)

@@ -10,7 +10,8 @@ ECAMP/Fine-tuning/Classification (run_lp.sh), on one MI355X:
 The reference's flag names are kept.  Added: --list_dir (the reference hard-codes ./datasets/<task>), --compute_dtype {bf16,fp16,fp32}
 (--fp16 is --compute_dtype fp16; --fp16_opt_level is accepted and ignored), --pool {avg,cls}, --f32_residual, --synthetic,
 --synthetic_len, --num_workers, --print_freq, --drop_path_rate (main_finetune's stochastic depth; refused here unless 0: the frozen
-encoder of the probe is deterministic), --train_pos_embed (main_finetune's trained position table; refused here).  `--stage train` trains, then tests the best checkpoint, as the reference does.
+encoder of the probe is deterministic), --train_pos_embed (main_finetune's trained position table; refused here), --fp16_loss_scale (main_finetune's loss scale of IEEE-half
+fine-tuning; ignored here: the head and its gradient are f32).  `--stage train` trains, then tests the best checkpoint, as the reference does.
 
 NOT implemented here, and refused with a message: `--mode Finetune` (main_finetune's), data-parallel probing (`--local_rank` other
 than -1); segmentation and detection fine-tuning have no counterpart in this project.
@@ -71,6 +72,10 @@ def get_args_parser():
     p.add_argument("--train_pos_embed", action="store_true",
                    help="--mode Finetune: train pos_embed as the reference does (timm's is a parameter among model.parameters()); the default "
                         "here holds it at the fixed sin-cos table")
+    p.add_argument("--fp16_loss_scale", type=str, default=None, metavar="{dynamic,<power of two>}",
+                   help="--mode Finetune with --fp16 / --compute_dtype fp16: fine-tune in IEEE half under a loss scale.  dynamic: the reference's "
+                        "apex recipe (from 2^20, halved when a step overflows and that step skipped, doubled after 2000 clean steps); a power "
+                        "of two: that scale, static.  Without it fp16 fine-tuning is refused; --mode LinearProbe ignores it")
     return p
 
 

@@ -2,6 +2,7 @@
 optim_factory.add_weight_decay, call site main_pretrain.py:253) and AdamW(betas=(0.9, 0.95)) (:254) as ONE fused
 HIP launch over the parameter arena (ecamp_adamw_grouped), which also refreshes the bf16 shadow weights."""
 import collections
+import math
 import os
 
 import torch
@@ -273,6 +274,19 @@ class FusedSGD(_FlatOptimizer):
     def step(self, closure=None, ctl=None):
         """`ctl` (device f32[4], hip_ops.loss_scale_update): the gradient scale and whether this step happens at all are read on the device."""
         loss = closure() if closure is not None else None
+        self._step(ctl, None)
+        return loss
+
+    @torch.no_grad()
+    def step_scaled(self, scaler):
+        """The step under an `SGDLossScaler` whose scale multiplied the loss: between the sums of squares and the updates ONE
+        `ecamp_sgd_scale_update` launch decides from the partials whether the scaled gradients overflowed, writes the `ctl` both updates
+        read (1 / scale; a skip leaves parameters, momentum, shadows and the tail alone), `last_norm` (the norm of the un-scaled
+        gradients; inf / nan on a skipped step) and the scaler's next state.  Nothing is read back, and the step count advances whether or
+        not the device skipped -- as the reference's scheduler and global_step do around apex (train.py:462-465)."""
+        self._step(None, scaler)
+
+    def _step(self, ctl, scaler):
         A, T = self._bind(), self._tail
         A.flush_fresh()
         lrs = [g["lr"] for g in self.param_groups]
@@ -282,15 +296,17 @@ class FusedSGD(_FlatOptimizer):
         ops.sumsq_grouped(A.flat_g, self._table, self._partials)
         if T is not None:
             ops.sumsq_grouped(T.flat_g, self._tail_table, self._partials[n0:])
+        norm_out = self.last_norm
+        if scaler is not None:   # (a skipped sgd_grouped writes no norm: the scaler's launch does, with the same bits on a clean step)
+            ctl, norm_out = scaler.update(self._partials, n0 + n1, self.last_norm), None
         ops.sgd_grouped(A.flat_p, A.flat_g, self._buf, A.flat_p16, self._table, lrs, wds, mom, self.max_grad_norm, self._partials, n0 + n1,
-                        self.grad_scale, ctl, self.last_norm)
+                        self.grad_scale, ctl, norm_out)
         if T is not None:
             ops.sgd_grouped(T.flat_p, T.flat_g, T.flat_buf, None, self._tail_table, lrs, wds, mom, self.max_grad_norm, self._partials, n0 + n1,
                             self.grad_scale, ctl, None)
         self._steps += 1
         A.version += 1   # the 16-bit shadows changed
         self.pace()
-        return loss
 
     def _state_head(self):
         return {} if self._steps > 0 else None
@@ -305,3 +321,100 @@ class FusedSGD(_FlatOptimizer):
             return False
         self._steps = max(self._steps, 1)
         return True
+
+
+class SGDLossScaler:
+    """apex's dynamic loss scaling (LossScaler.update_scale under `amp.initialize(opt_level="O2")`, the reference's `--fp16` recipe:
+    Fine-tuning/Classification/train.py:398 starts it at 2^20) for `FusedSGD.step_scaled`, with the decision on the device:
+
+        scaler.scale_loss(loss).backward();  optimizer.step_scaled(scaler)
+
+    state = {scale, clean steps since the last change, steps skipped in total, steps skipped in a row}.  A step whose scaled gradients
+    are not finite is skipped and the scale multiplied by `backoff`; after `window` clean steps in a row the scale grows by `growth`, up to
+    `max_scale`.  `window=0` is a static scale (it never moves; a non-finite step is still skipped, where apex's static mode would step
+    into the NaNs).  The state moves to the device on first use (ecamp_sgd_scale_update keeps it there) and no step reads it back:
+    `scale`, `skipped_steps`, `skipped_in_a_row`, `clean_steps` and `last_found_inf` wait for the device only when asked.  `host_update`
+    is the same rule on the host, for a state that has not moved to the device."""
+
+    def __init__(self, init_scale=2.0 ** 20, growth=2.0, backoff=0.5, window=2000, max_scale=2.0 ** 24):
+        if not init_scale > 0 or not growth >= 1 or not 0 < backoff <= 1 or int(window) != window or window < 0 or not max_scale > 0:
+            raise ValueError("SGDLossScaler: init_scale > 0, growth >= 1, 0 < backoff <= 1, an integer window >= 0 and max_scale > 0 are required")
+        self.growth, self.backoff, self.window, self.max_scale = float(growth), float(backoff), int(window), float(max_scale)
+        self.init_scale = float(init_scale)
+        self._host = [self.init_scale, 0.0, 0.0, 0.0]
+        self._found = False
+        self._dev = self._ctl = None
+
+    @staticmethod
+    def rule(state, found, growth, backoff, window, max_scale):
+        """One update of [scale, clean, skipped, skipped in a row] in f32 arithmetic, as the kernel's thread 0 applies it -> the new list."""
+        import numpy as np
+        f = np.float32
+        scale, clean, skipped, row = (f(v) for v in state)
+        if found:
+            with np.errstate(under="ignore"):
+                return [float(scale * f(backoff) if window != 0 else scale), 0.0, float(skipped + f(1)), float(row + f(1))]
+        clean = clean + f(1)
+        if clean == f(window):
+            with np.errstate(over="ignore"):
+                return [float(min(f(max_scale), scale * f(growth))), 0.0, float(skipped), 0.0]
+        return [float(scale), float(clean), float(skipped), 0.0]
+
+    def host_update(self, found):
+        """The rule on the host copy of the state -> the new scale."""
+        if self._dev is not None:
+            raise RuntimeError("SGDLossScaler.host_update: the state lives on the device (ecamp_sgd_scale_update moves it)")
+        self._host = self.rule(self._host, bool(found), self.growth, self.backoff, self.window, self.max_scale)
+        self._found = bool(found)
+        return self._host[0]
+
+    def state(self, device=None):
+        """The device f32[4] (created from the host copy on first use, on `device`)."""
+        if self._dev is None:
+            if device is None:
+                raise RuntimeError("SGDLossScaler: no device state yet (scale_loss / FusedSGD.step_scaled create it)")
+            self._dev = torch.tensor(self._host, device=device, dtype=torch.float32)
+            self._ctl = torch.tensor([1.0 / self._host[0], 0.0, 0.0, 0.0], device=device, dtype=torch.float32)
+        return self._dev
+
+    @property
+    def ctl(self):
+        """The device f32[4] the last update wrote for `ecamp_sgd_grouped`: {1 / scale of that step, skipped, 0, 0}."""
+        return self._ctl
+
+    def scale_loss(self, loss):
+        """loss * scale, the scale read on the device."""
+        return loss * self.state(loss.device)[0]
+
+    def update(self, partials, npart, norm_out=None):
+        """One `ecamp_sgd_scale_update` over `partials[0:npart]` (sums of squares of the scaled gradients) -> `ctl`."""
+        state = self.state(partials.device)
+        ops.sgd_scale_update(partials, npart, state, self._ctl, norm_out, self.growth, self.backoff, self.window, self.max_scale)
+        return self._ctl
+
+    def _read(self):
+        if self._dev is not None:
+            self._host = [float(v) for v in self._dev.tolist()]
+            self._found = bool(self._ctl[1].item() != 0)
+        return self._host
+
+    scale = property(lambda self: self._read()[0])
+    clean_steps = property(lambda self: int(self._read()[1]))
+    skipped_steps = property(lambda self: int(self._read()[2]))
+    skipped_in_a_row = property(lambda self: int(self._read()[3]))
+
+    @property
+    def last_found_inf(self):
+        self._read()
+        return self._found
+
+    def describe(self):
+        """The rule in words, from the constructor's arguments alone (the driver's opening line)."""
+        def num(v):   # 1048576 (2^20), not 1.04858e+06
+            m, e = math.frexp(v)
+            return "%d (2^%d)" % (v, e - 1) if m == 0.5 and v >= 1 else "%g" % v
+
+        if self.window == 0:
+            return "a static loss scale of %s (a step whose gradients are not finite is skipped)" % num(self.init_scale)
+        return ("a dynamic loss scale from %s: x %g and the step skipped when the scaled gradients are not finite, x %g after %d clean steps "
+                "in a row, at most %s" % (num(self.init_scale), self.backoff, self.growth, self.window, num(self.max_scale)))

@@ -399,6 +399,23 @@ int ecamp_sumsq_grouped(const float* g, const uint8_t* block_group, int64_t n, f
 int ecamp_sgd_grouped(float* p, const float* g, float* buf, void* p16, const uint8_t* block_group, int64_t n, int32_t ngroups,
                       const float* lr_host, const float* wd_host, float momentum, float max_norm, const float* partials, int32_t npart,
                       float grad_scale, const float* ctl, float* norm_out, ecampStream_t stream);
+/* Dynamic loss scaling around ecamp_sgd_grouped, decided on the device (IEEE-half fine-tuning: what apex's `--fp16 --fp16_opt_level O2`
+ * puts around the reference's step, train.py:398,452-465).  ONE workgroup adds partials[0 .. npart) -- the slots ecamp_sumsq_grouped
+ * filled over the SCALED gradients, 1 <= npart <= 4096 -- in exactly ecamp_sgd_grouped's order, so both hold the same bits of the sum s.
+ *   found = !(|s| <= FLT_MAX)            (inf, nan, or finite slots whose sum leaves f32)
+ *   ctl[0..4) = {1 / scale, found, 0, 0}  (what ecamp_sgd_grouped reads: a found step leaves every byte alone)
+ *   norm_out[0] = sqrt(s) / scale        (nullable; the norm of the un-scaled gradients, computed as sqrt(s) * ctl[0] like the step's own
+ *                                         norm_out and bit-equal to it; inf / nan when found)
+ * state f32[4] = {scale, clean steps since the last change, steps skipped in total, steps skipped in a row} then moves as apex's
+ * LossScaler.update_scale does for loss_scale="dynamic":
+ *   found:      scale *= backoff; clean = 0; both skipped counters += 1
+ *   otherwise:  clean += 1; skipped in a row = 0; when clean == window: scale = min(max_scale, scale * growth), clean = 0
+ * (apex: growth 2, backoff 0.5, window 2000, max_scale 2^24, no floor; the reference starts at 2^20).  window == 0 is a STATIC scale: it
+ * never changes (no backoff either; the counters still move), and a non-finite step is still skipped -- apex's static mode would step into the NaNs instead.  The counters are f32,
+ * exact to 2^24 steps.  The host reads nothing.  Refused before the device is touched: a null partials, state or ctl, npart outside
+ * [1, 4096], growth < 1, backoff outside (0, 1], window < 0, max_scale <= 0. */
+int ecamp_sgd_scale_update(const float* partials, int32_t npart, float* state, float* ctl, float* norm_out, float growth, float backoff,
+                           int32_t window, float max_scale, ecampStream_t stream);
 /* The stem's parameter gradients that are sums of rows of one table (`--train_pos_embed`: timm's pos_embed is a trained parameter,
  * Fine-tuning/Classification/train.py:377-380).  dx [B, T, D] contiguous, the gradient at the stem's output, in `dtype` (0: f32, 1: the
  * build's 16-bit format).  With S[t, d] = sum_b dx[b, t, d], formed ONCE by this call:

@@ -29,6 +29,14 @@
      arena's layout differs), blocks of `--iters` steps alternating between them.  The model without the flag runs the code of the
      commit before the flag existed, launch for launch.
   `--parity_log FILE`: the "[pos_embed]" lines that tests/test_posembed_*_gpu.py print under `pytest -s` are copied behind the timings.
+
+`--fp16` runs another leg INSTEAD and writes profiles/finetune_fp16.txt (`--fp16_out`):
+
+  10 the whole fine-tune step of leg 1 in bf16 beside the same step in IEEE half under the loss scaler (`--fp16 --fp16_loss_scale dynamic`:
+     loss x scale, `FusedSGD.step_scaled`) on TWO models of equal weights with an optimizer each, blocks of `--iters` steps alternating.
+  11 `ecamp_sgd_scale_update` alone beside an empty launch (`ecamp_dev_spin`, one workgroup, zero cycles), alternating in one loop.
+  `--parity_log FILE`: the "[fp16-finetune]" lines that tests/test_sgd_scale_kernel_gpu.py and tests/test_fp16_finetune_model_gpu.py print under
+  `pytest -s` are copied behind the timings.
 """
 import argparse
 import os
@@ -253,6 +261,76 @@ def pos_embed_leg(args, say):
                 say("   " + line[line.index("[pos_embed]"):].strip())
 
 
+def fp16_leg(args, say):
+    """Legs 10 and 11 (see the module docstring)."""
+    from ecamp_amd import _lib, engine_finetune
+    from ecamp_amd import hip_ops as ops
+    from ecamp_amd.module.classifier import build_classifier
+    dev = torch.device("cuda")
+    C = args.classes
+    say("IEEE-half fine-tuning under the on-device loss scaler on %s: ViT-B/16, R = 224, %d classes" % (torch.cuda.get_device_name(0), C))
+    models = {}
+    for name, dtype in (("bf16", torch.bfloat16), ("fp16", torch.float16)):
+        torch.manual_seed(0)
+        clf = build_classifier("vit_base_patch16", C, True, img_size=224, compute_dtype=dtype, train_encoder=True).to(dev)
+        step_args = argparse.Namespace(learning_rate=3e-2, weight_decay=1e-4, decay_type="cosine", warmup_steps=50, num_steps=3000, max_grad_norm=1.0,
+                                       compute_dtype=name, fp16_loss_scale="dynamic" if name == "fp16" else None)
+        models[name] = (clf, engine_finetune.make_optimizer(clf, step_args), step_args)
+    scaler = models["fp16"][1].loss_scaler
+    say("10 the whole fine-tune step (forward + backward + clip + SGD) in bf16 and in fp16 with the loss scaler (%s): two models of equal initial "
+        "weights, an optimizer each, blocks of %d steps alternating between them, host clock around a block that ends in a device synchronise, 5 blocks "
+        "each after %d warm-up steps each" % (scaler.describe(), args.iters, args.warmup))
+    for B in [int(b) for b in args.batches.split(",")]:
+        imgs = torch.randn(B, 3, 224, 224, device=dev)
+        y = (torch.rand(B, C, device=dev) < 0.3).float()
+        n = {"bf16": 0, "fp16": 0}
+
+        def block(name, steps):
+            clf, opt, step_args = models[name]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                engine_finetune.train_step(clf, opt, imgs, y, n[name], step_args)
+                n[name] += 1
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / steps
+
+        for name in models:
+            block(name, args.warmup)
+        ms = {name: [] for name in models}
+        for _ in range(5):
+            for name in models:
+                ms[name].append(1e3 * block(name, args.iters))
+        m0, lo0, hi0 = stats(ms["bf16"])
+        m1, lo1, hi1 = stats(ms["fp16"])
+        say("   B = %3d  bf16: %.2f ms (min %.2f, max %.2f) = %.0f images/s;  fp16 + scaler: %.2f ms (min %.2f, max %.2f) = %.0f images/s;  "
+            "fp16 - bf16 = %+.2f ms = %+.2f %% (block-to-block spread of bf16: %.2f ms); after %d fp16 steps: scale %.10g, %d skipped"
+            % (B, m0, lo0, hi0, B / (m0 * 1e-3), m1, lo1, hi1, B / (m1 * 1e-3), m1 - m0, 100.0 * (m1 - m0) / m0, hi0 - lo0, n["fp16"], scaler.scale,
+               scaler.skipped_steps))
+        del imgs, y
+
+    opt = models["fp16"][1]
+    npart = sum(opt._slots)
+    part = torch.rand(npart, device=dev) + 0.5
+    state = torch.tensor([2.0 ** 20, 0.0, 0.0, 0.0], device=dev)
+    ctl, norm = ops.zeros((4,), dev), ops.zeros((1,), dev)
+    st = ops.stream
+    us = event_groups([("sgd_scale_update", lambda: ops.sgd_scale_update(part, npart, state, ctl, norm, 2.0, 0.5, 2000, 2.0 ** 24)),
+                       ("empty launch", lambda: _lib.call("ecamp_dev_spin", 1, 256, 0, st()))], args.iters, args.warmup, 20)
+    say("11 ecamp_sgd_scale_update alone over the %d slots of this model's step (arena %d + tail %d) beside an empty launch (ecamp_dev_spin, one "
+        "workgroup of 256 threads, zero cycles: the floor of a single-workgroup kernel), per call, from event pairs around 20 back-to-back calls, "
+        "alternating in one loop (%d groups after %d warm-up groups)" % (npart, opt._slots[0], opt._slots[1], args.iters, args.warmup))
+    med_e = stats(us["empty launch"])[0]
+    for name in ("sgd_scale_update", "empty launch"):
+        med_u, lo_u, hi_u = stats(us[name])
+        say("   %-17s median %6.2f us (min %.2f, max %.2f) = %.2f x the empty launch" % (name, med_u, lo_u, hi_u, med_u / med_e))
+    if args.parity_log:
+        say("12 the GPU tests' own figures (tests/test_sgd_scale_kernel_gpu.py; tests/test_fp16_finetune_model_gpu.py: ecamp_tiny, B = 4, float64 references):")
+        for line in open(args.parity_log):
+            if "[fp16-finetune]" in line:
+                say("   " + line[line.index("[fp16-finetune]"):].strip())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
@@ -265,9 +343,23 @@ def main():
     ap.add_argument("--parity_log", type=str, default="", help="--droppath / --pos_embed: a `pytest -s` log of that leg's GPU tests whose [droppath] / [pos_embed] lines are copied")
     ap.add_argument("--pos_embed", action="store_true", help="run the trained-pos_embed leg instead (profiles/finetune_pos_embed.txt)")
     ap.add_argument("--pos_embed_out", type=str, default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "finetune_pos_embed.txt"))
+    ap.add_argument("--fp16", action="store_true", help="run the IEEE-half / loss-scaler leg instead (profiles/finetune_fp16.txt)")
+    ap.add_argument("--fp16_out", type=str, default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "finetune_fp16.txt"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("finetune_bench needs an MI355X: nothing here can be measured on a CPU")
+    if args.fp16:
+        lines = []
+
+        def say_h(msg):
+            print(msg, flush=True)
+            lines.append(msg)
+
+        fp16_leg(args, say_h)
+        os.makedirs(os.path.dirname(os.path.abspath(args.fp16_out)), exist_ok=True)
+        with open(args.fp16_out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     if args.pos_embed:
         lines = []
 
