@@ -31,26 +31,69 @@ __device__ __forceinline__ double rs_bicubic(double x) {
     return 0.0;
 }
 
-// one thread per (sample, axis, output index): bounds {first input index, tap count} and `kmax` fixed-point taps (zero past the count)
-__global__ __launch_bounds__(256) void resample_coef_kernel(const RsTab* __restrict__ tab, int2* __restrict__ bounds, int* __restrict__ coef, long B, int out,
-                                                            int kmax, int* __restrict__ err) {
+// Pillow's BILINEAR filter (Resample.c bilinear_filter: the triangle 1 - |x|, support 1): the classification transforms
+// (ECAMP/Fine-tuning/Classification/utils/data_utils.py:20-34 through torchvision's defaults)
+__device__ __forceinline__ double rs_bilinear(double x) {
+#pragma clang fp contract(off)
+    if (x < 0.0) x = -x;
+    if (x < 1.0) return 1.0 - x;
+    return 0.0;
+}
+
+#define RS_BILINEAR 0
+#define RS_BICUBIC 1
+template <int F> struct RsFilter;
+template <> struct RsFilter<RS_BILINEAR> {
+    static constexpr double support = 1.0;
+    static __device__ __forceinline__ double f(double x) { return rs_bilinear(x); }
+};
+template <> struct RsFilter<RS_BICUBIC> {
+    static constexpr double support = 2.0;
+    static __device__ __forceinline__ double f(double x) { return rs_bicubic(x); }
+};
+
+// one thread per (sample, axis, output index): bounds {first input index, tap count} and `kmax` fixed-point taps (zero past the count).
+// `tab`: rows of `stride` int64.  stride 6 (ecamp_resample_crops_u8): the RsTab row, every axis resized from its size to `out`.  stride 10
+// (ecamp_resample_boxes_u8): {off, h, w, flip, row0, full_w, shift_w, full_h, shift_h, 0} -- output index x of an axis is index
+// u = x + shift of a resize of that axis from its size to `full`; u outside [0, full) has no tap (the passes then write (2^21) >> 22 = 0:
+// CenterCrop's zero padding).  The RsTab share of such a row is copied to `tab_out` for the two passes.
+template <int F>
+__global__ __launch_bounds__(256) void resample_coef_kernel(const long* __restrict__ tab, int stride, RsTab* __restrict__ tab_out, int2* __restrict__ bounds,
+                                                            int* __restrict__ coef, long B, int out, int kmax, int* __restrict__ err) {
 #pragma clang fp contract(off)
     const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= B * 2 * out) return;
     const int xx = (int)(id % out), axis = (int)((id / out) & 1);
     const long b = id / (2 * out);
-    const int inSize = (int)(axis == 0 ? tab[b].w : tab[b].h);
-    double scale = (double)inSize / (double)out, filterscale = scale;
-    if (filterscale < 1.0) filterscale = 1.0;
-    const double support = 2.0 * filterscale;
-    const int ksize = (int)ceil(support) * 2 + 1;
+    const long* t = tab + b * stride;
+    const int inSize = (int)(axis == 0 ? t[2] : t[1]);
+    int full = out, u = xx;
+    if (stride == 10) {
+        full = (int)t[5 + 2 * axis];
+        u = xx + (int)t[6 + 2 * axis];
+        if (xx == 0 && axis == 0) tab_out[b] = RsTab{t[0], t[1], t[2], t[3], t[4], 0};
+    }
     int* k = coef + id * kmax;
-    if (ksize > kmax || inSize <= 0) {   // the host sized the tables for a smaller scale factor: refuse loudly (caller reads err)
+    if (full <= 0 || inSize <= 0) {
         if (xx == 0) atomicExch(err, 1);
         bounds[id] = make_int2(0, 0);
         return;
     }
-    const double center = 0 + (xx + 0.5) * scale;
+    double scale = (double)inSize / (double)full, filterscale = scale;
+    if (filterscale < 1.0) filterscale = 1.0;
+    const double support = RsFilter<F>::support * filterscale;
+    const int ksize = (int)ceil(support) * 2 + 1;
+    if (ksize > kmax) {   // the host sized the tables for a smaller scale factor: refuse loudly (caller reads err)
+        if (xx == 0) atomicExch(err, 1);
+        bounds[id] = make_int2(0, 0);
+        return;
+    }
+    if (u < 0 || u >= full) {   // padding: no tap
+        for (int x = 0; x < kmax; ++x) k[x] = 0;
+        bounds[id] = make_int2(0, 0);
+        return;
+    }
+    const double center = 0 + (u + 0.5) * scale;
     const double ss = 1.0 / filterscale;
     int xmin = (int)(center - support + 0.5);
     if (xmin < 0) xmin = 0;
@@ -58,11 +101,11 @@ __global__ __launch_bounds__(256) void resample_coef_kernel(const RsTab* __restr
     if (xmax > inSize) xmax = inSize;
     xmax -= xmin;
     double ww = 0.0;
-    for (int x = 0; x < xmax; ++x) ww += rs_bicubic((x + xmin - center + 0.5) * ss);
+    for (int x = 0; x < xmax; ++x) ww += RsFilter<F>::f((x + xmin - center + 0.5) * ss);
     for (int x = 0; x < kmax; ++x) {
         int q = 0;
         if (x < xmax) {
-            double w = rs_bicubic((x + xmin - center + 0.5) * ss);
+            double w = RsFilter<F>::f((x + xmin - center + 0.5) * ss);
             if (ww != 0.0) w /= ww;
             q = w < 0 ? (int)(-0.5 + w * (double)(1 << RS_PRECISION_BITS)) : (int)(0.5 + w * (double)(1 << RS_PRECISION_BITS));
         }
@@ -119,6 +162,11 @@ __global__ __launch_bounds__(512) void resample_v_kernel(const unsigned char* __
     dst[(b * out + yy) * out + (t.flip ? out - 1 - xx : xx)] = rs_clip8(ss);
 }
 
+static void rs_lds_optin() {
+    static bool optin = false;
+    if (!optin) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(resample_h_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); optin = true; }
+}
+
 // workspace: bounds int2 [B][2][out] | coef int32 [B][2][out][kmax] | err int32 (16 B) | intermediate uint8 [tmp_rows][out]
 static size_t rs_align(size_t v) { return (v + 255) & ~(size_t)255; }
 extern "C" int64_t ecamp_resample_crops_workspace_bytes(int64_t B, int32_t out, int32_t kmax, int64_t tmp_rows) {
@@ -141,11 +189,53 @@ extern "C" int ecamp_resample_crops_u8(const uint8_t* src, const int64_t* table,
     unsigned char* tmp = w + 256;
     const RsTab* tab = reinterpret_cast<const RsTab*>(table);
     const long n = B * 2 * out;
-    hipLaunchKernelGGL(resample_coef_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, tab, bounds, coef, (long)B, (int)out, (int)kmax, (int*)err_flag);
+    hipLaunchKernelGGL(resample_coef_kernel<RS_BICUBIC>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, reinterpret_cast<const long*>(table), 6, (RsTab*)nullptr, bounds,
+                       coef, (long)B, (int)out, (int)kmax, (int*)err_flag);
     // rows per sample are data (the table lives on the device): the grid covers the tallest crop of the batch (max_h, the host knows it)
     const size_t shm = (size_t)kmax * out * sizeof(int);
-    static bool optin = false;
-    if (!optin) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(resample_h_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); optin = true; }
+    rs_lds_optin();
+    const unsigned chunks = (unsigned)((max_h + RS_ROWS - 1) / RS_ROWS);
+    hipLaunchKernelGGL(resample_h_kernel, dim3(chunks, (unsigned)B), dim3(512), shm, stream, src, tab, bounds, coef, tmp, (int)out, (int)kmax);
+    hipLaunchKernelGGL(resample_v_kernel, dim3((unsigned)out, (unsigned)B), dim3(512), 0, stream, tmp, tab, bounds, coef, dst, (int)out, (int)kmax);
+    ECAMP_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- the classification transforms (data_utils.py:20-34): RandomResizedCrop((s, s)) / flip, and Resize(int) + CenterCrop((s, s)) ----
+// One resample per axis with two more numbers: `full`, the size the axis is resized to, and `shift`, where the s output pixels start in
+// that resized axis (negative, or past `full`: CenterCrop's zero padding).  Training is full = out, shift = 0 on the crop box.  Same
+// coefficient kernel (template over the filter), same two passes; the passes read the RsTab rows the coefficient kernel copies out.
+// workspace: as above | RsTab [B]
+extern "C" int64_t ecamp_resample_boxes_workspace_bytes(int64_t B, int32_t out, int32_t kmax, int64_t tmp_rows) {
+    const int64_t base = ecamp_resample_crops_workspace_bytes(B, out, kmax, tmp_rows);
+    return base == 0 ? 0 : base + (int64_t)rs_align((size_t)B * sizeof(RsTab));
+}
+
+extern "C" int ecamp_resample_boxes_u8(const uint8_t* src, const int64_t* table, uint8_t* dst, int64_t B, int32_t out, int32_t kmax, int64_t tmp_rows,
+                                       int32_t max_h, int32_t filter, void* ws, int64_t ws_bytes, int32_t* err_flag, hipStream_t stream) {
+    ECAMP_CHECK_ARG(src && table && dst && ws && err_flag, "resample_boxes_u8: null argument");
+    ECAMP_CHECK_ARG(filter == RS_BILINEAR || filter == RS_BICUBIC, "resample_boxes_u8: filter %d (0: bilinear, 1: bicubic)", filter);
+    ECAMP_CHECK_ARG(B > 0 && B <= 65535 && out > 0 && out <= 512 && kmax >= (filter == RS_BICUBIC ? 5 : 3) && (size_t)kmax * out * sizeof(int) <= 160 * 1024 && tmp_rows > 0 &&
+                        max_h > 0 && max_h <= tmp_rows,
+                    "resample_boxes_u8: B=%ld (<= 65535) out=%d (<= 512) kmax=%d (taps x out x 4 B must fit the 160 KB LDS) tmp_rows=%ld max_h=%d", (long)B, out, kmax,
+                    (long)tmp_rows, max_h);
+    ECAMP_CHECK_ARG(ws_bytes >= ecamp_resample_boxes_workspace_bytes(B, out, kmax, tmp_rows), "resample_boxes_u8: workspace of %ld bytes is too small", (long)ws_bytes);
+    unsigned char* w = reinterpret_cast<unsigned char*>(ws);
+    int2* bounds = reinterpret_cast<int2*>(w);
+    w += rs_align((size_t)B * 2 * out * sizeof(int2));
+    int* coef = reinterpret_cast<int*>(w);
+    w += rs_align((size_t)B * 2 * out * kmax * sizeof(int));
+    unsigned char* tmp = w + 256;
+    RsTab* tab = reinterpret_cast<RsTab*>(tmp + rs_align((size_t)tmp_rows * out));
+    const long n = B * 2 * out;
+    const dim3 cg((unsigned)((n + 255) / 256));
+    const long* t10 = reinterpret_cast<const long*>(table);
+    if (filter == RS_BILINEAR)
+        hipLaunchKernelGGL(resample_coef_kernel<RS_BILINEAR>, cg, dim3(256), 0, stream, t10, 10, tab, bounds, coef, (long)B, (int)out, (int)kmax, (int*)err_flag);
+    else
+        hipLaunchKernelGGL(resample_coef_kernel<RS_BICUBIC>, cg, dim3(256), 0, stream, t10, 10, tab, bounds, coef, (long)B, (int)out, (int)kmax, (int*)err_flag);
+    const size_t shm = (size_t)kmax * out * sizeof(int);
+    rs_lds_optin();
     const unsigned chunks = (unsigned)((max_h + RS_ROWS - 1) / RS_ROWS);
     hipLaunchKernelGGL(resample_h_kernel, dim3(chunks, (unsigned)B), dim3(512), shm, stream, src, tab, bounds, coef, tmp, (int)out, (int)kmax);
     hipLaunchKernelGGL(resample_v_kernel, dim3((unsigned)out, (unsigned)B), dim3(512), 0, stream, tmp, tab, bounds, coef, dst, (int)out, (int)kmax);

@@ -286,6 +286,45 @@ extern "C" int ecamp_im2col_gather(const float* imgs, const int32_t* ids_keep, v
     return 0;
 }
 
+// K2a from the uint8 grayscale image itself (the classifier's device image pipeline: uint8 [B, R, R] at the model's own size): the
+// three channel slabs of a row are the same p*p values lut[byte] -- bit for bit im2col_gather_kernel on lut[image] expanded to three
+// planes, without the f32 [B, 3, R, R] image in between (one byte read per pixel instead of twelve written and twelve read).
+template <typename T>
+__global__ void im2col_u8_kernel(const unsigned char* __restrict__ img, const float* __restrict__ lut, const int* __restrict__ ids_keep, T* __restrict__ out,
+                                 long B, int Lk, int R, int p) {
+    const int G = R / p, P = p * p, P4 = P / 4, Tt = Lk + 1;
+    const long n = B * Tt * P4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const int k4 = (int)(i % P4);
+        const long row = i / P4;
+        const int t = (int)(row % Tt);
+        const long b = row / Tt;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        if (t > 0) {
+            const int patch = ids_keep[b * Lk + t - 1];
+            const int gy = patch / G, gx = patch % G;
+            const int k = k4 * 4, py = k / p, px = k % p;
+            const unsigned m = *reinterpret_cast<const unsigned*>(img + (b * (long)R + gy * p + py) * R + gx * p + px);   // 4-byte aligned: R, p, px % 4 == 0
+            v[0] = lut[m & 255u]; v[1] = lut[(m >> 8) & 255u]; v[2] = lut[(m >> 16) & 255u]; v[3] = lut[m >> 24];
+        }
+        T* o = out + row * (3L * P) + k4 * 4;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) st4<T>(o + c * P, v);
+    }
+}
+extern "C" int ecamp_im2col_u8(const uint8_t* img, const float* lut, const int32_t* ids_keep, void* out, int64_t B, int32_t Lk, int32_t R, int32_t p,
+                               int32_t dtype, hipStream_t stream) {
+    ECAMP_CHECK_ARG(img && lut && ids_keep && out && B > 0 && Lk >= 0 && p > 0 && p % 4 == 0 && R > 0 && R % p == 0 && ((uintptr_t)img & 3) == 0 && ((uintptr_t)out & 15) == 0,
+                    "im2col_u8: bad args (p %% 4 == 0, R %% p == 0, img 4-byte and out 16-byte aligned)");
+    ECAMP_CHECK_ARG(dtype == ECAMP_F32 || dtype == ECAMP_BF16, "im2col_u8: dtype %d", dtype);
+    const long n = B * (Lk + 1) * (long)(p * p / 4);
+    const int nb = (int)std::min<long>((n + 255) / 256, 8192);
+    if (dtype == ECAMP_F32) hipLaunchKernelGGL(im2col_u8_kernel<float>, dim3(nb), dim3(256), 0, stream, img, lut, ids_keep, (float*)out, (long)B, Lk, R, p);
+    else hipLaunchKernelGGL(im2col_u8_kernel<bf16_t>, dim3(nb), dim3(256), 0, stream, img, lut, ids_keep, (bf16_t*)out, (long)B, Lk, R, p);
+    ECAMP_LAUNCH_CHECK();
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // K2b/K4  in place on the patch-embed GEMM output x[B, Lk+1, D]:
 //      x[b,0,:] = cls + pos[0] ;  x[b,t,:] += pos[1 + ids_keep[b,t-1]]     (model_ecamp.py:222,228-230)

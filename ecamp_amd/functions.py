@@ -186,19 +186,23 @@ def _post_ln_bwd(m, dout, z, mean, rstd, ln, ph, seed, offset):
 # =============================================================================================
 class StemFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, big, noise, m, mask_ratio, anchor):
+    def forward(ctx, big, noise, m, mask_ratio, anchor, lut=None):
+        """`lut` (hip_ops.image_lut of the caller's mean / std; ECAMPClassifier's): a uint8 `big` at the model's own size is then gathered
+        into the patch columns straight from its bytes (ecamp_im2col_u8) -- the same `cols`, bit for bit, without the f32 [B, 3, R, R] image,
+        which is returned as None.  Without a table (pre-training) the uint8 image goes through ecamp_bicubic_resize_u8 as before."""
         A = m.arena
         cd = m.compute_dtype
         B = big.shape[0]
         R, p, D = m.img_size, m.patch_size, m.embed_dim
         L = m.num_patches
         Lk = int(L * (1 - mask_ratio))
-        imgs = ops.bicubic_resize(big, R, R) if (big.shape[-1] != R or ops.is_u8_image(big)) else big
+        fused = lut is not None and ops.is_u8_image(big) and big.shape[-1] == R and big.shape[-2] == R
+        imgs = None if fused else ops.bicubic_resize(big, R, R) if (big.shape[-1] != R or ops.is_u8_image(big)) else big
         if noise is None:
             seed, off = m.next_rng()
             noise = ops.uniform((B, L), big.device, seed, off)
         ids_restore, ids_keep, mask = ops.mask_indices(noise, Lk)
-        cols = ops.im2col_gather(imgs, ids_keep, p, cd)
+        cols = ops.im2col_u8(big.reshape(B, R, R), lut, ids_keep, p, cd) if fused else ops.im2col_gather(imgs, ids_keep, p, cd)
         pw = m.patch_embed.proj.weight
         x = ops.linear_fwd(cols, A.w(pw).view(D, -1), m.patch_embed.proj.bias.data)
         if m.f32_residual:   # f32 tokens = 16-bit patch embedding + f32 position table (autocast: half conv + f32 pos_embed)
@@ -206,7 +210,7 @@ class StemFn(torch.autograd.Function):
         else:
             ops.assemble_tokens_(x, m.cls_token.data, m.pos_embed.data, ids_keep, B, Lk, D)
         ctx.m, ctx.cols, ctx.Lk = m, cols, Lk
-        ctx.mark_non_differentiable(imgs, mask, ids_restore, ids_keep)
+        ctx.mark_non_differentiable(*(t for t in (imgs, mask, ids_restore, ids_keep) if t is not None))
         return x, imgs, mask, ids_restore, ids_keep
 
     @staticmethod
@@ -224,11 +228,11 @@ class StemFn(torch.autograd.Function):
                                    "%d of %d patches were kept" % (ctx.Lk, m.num_patches))
             ops.pos_embed_grad(dx.view(-1, Tt, m.embed_dim), A.grad(m.pos_embed).view(Tt, -1), A.grad(m.cls_token).view(-1), A.grad(pe.bias))
             A.ready(pe.weight, pe.bias, m.cls_token, m.pos_embed)
-            return _none(5)
+            return _none(6)
         ops.colsum(dx, A.grad(pe.bias), period=Tt, lo=1, hi=Tt)  # cls rows carry no patch: excluded from the bias gradient
         ops.colsum(dx, A.grad(m.cls_token).view(-1), period=Tt, lo=0, hi=1)
         A.ready(pe.weight, pe.bias, m.cls_token)
-        return _none(5)
+        return _none(6)
 
 
 # =============================================================================================

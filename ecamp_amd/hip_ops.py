@@ -457,12 +457,13 @@ IMG_MEAN, IMG_STD = 0.4721, 0.3037   # the reference's Normalize (pretrain_datas
 _IMG_LUT = {}
 
 
-def image_lut(device):
-    """lut[u] = ((float)u / 255 - mean) / std: ToTensor + Normalize of every byte value in their own f32 arithmetic (256 floats, built once)."""
-    key = str(device)
+def image_lut(device, mean=IMG_MEAN, std=IMG_STD):
+    """lut[u] = ((float)u / 255 - mean) / std: ToTensor + Normalize of every byte value in their own f32 arithmetic (256 floats, built once
+    per device and pair of constants; the default pair is pre-training's, the classifier passes finetune_datasets.FT_MEAN / FT_STD)."""
+    key = (str(device), float(mean), float(std))
     t = _IMG_LUT.get(key)
     if t is None:
-        t = _IMG_LUT[key] = torch.arange(256, dtype=torch.float32).div(255.0).sub(IMG_MEAN).div(IMG_STD).to(device)
+        t = _IMG_LUT[key] = torch.arange(256, dtype=torch.float32).div(255.0).sub(float(mean)).div(float(std)).to(device)
     return t
 
 
@@ -503,6 +504,19 @@ def im2col_gather(imgs, ids_keep, p, dtype):
     Lk = ids_keep.shape[1]
     out = torch.empty((B * (Lk + 1), C * p * p), device=imgs.device, dtype=dtype)
     call("ecamp_im2col_gather", ptr(imgs), ptr(ids_keep), ptr(out), B, Lk, C, R, p, code(dtype), stream())
+    return out
+
+
+def im2col_u8(img, lut, ids_keep, p, dtype):
+    """im2col_gather straight from a uint8 grayscale image [B, R, R] at the model's own size, normalised through `lut` (image_lut): the bits
+    of im2col_gather on lut[img] expanded to three planes, without that f32 image."""
+    _chk(img, lut, ids_keep)
+    assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[1] == img.shape[2] and img.is_contiguous()
+    assert lut.dtype == torch.float32 and lut.numel() == 256 and lut.is_contiguous()
+    B, R, _ = img.shape
+    Lk = ids_keep.shape[1]
+    out = torch.empty((B * (Lk + 1), 3 * p * p), device=img.device, dtype=dtype)
+    call("ecamp_im2col_u8", ptr(img), ptr(lut), ptr(ids_keep), ptr(out), B, Lk, R, p, code(dtype), stream())
     return out
 
 
@@ -874,4 +888,23 @@ def resample_crops_u8(flat, table, out_t, out, kmax, tmp_rows, max_h, ws, err):
     assert flat.dtype == torch.uint8 and table.dtype == torch.int64 and table.is_contiguous() and out_t.dtype == torch.uint8 and out_t.is_contiguous()
     call("ecamp_resample_crops_u8", ptr(flat), ptr(table), ptr(out_t), table.shape[0], int(out), int(kmax), int(tmp_rows), int(max_h), ptr(ws), ws.numel(),
          ptr(err), stream())
+    return out_t
+
+
+BILINEAR, BICUBIC = 0, 1   # the `filter` argument of ecamp_resample_boxes_u8
+
+
+def resample_boxes_workspace_bytes(B, out, kmax, tmp_rows):
+    return int(_lib.load().ecamp_resample_boxes_workspace_bytes(int(B), int(out), int(kmax), int(tmp_rows)))
+
+
+def resample_boxes_u8(flat, table, out_t, out, kmax, tmp_rows, max_h, ws, err, filter=BILINEAR):
+    """B boxes (flat uint8 + int64 table [B, 10]: off, h, w, flip, row0, full_w, shift_w, full_h, shift_h, 0; both on the device) -> out_t
+    uint8 [B, out, out]: Pillow's resize of every axis to `full` (BILINEAR or BICUBIC), the `out` pixels from `shift` on, zero outside, +
+    flip -- byte for byte the classification transforms (csrc/augment.hip; module/finetune_datasets.py)."""
+    _chk(flat, table, out_t, ws, err)
+    assert flat.dtype == torch.uint8 and table.dtype == torch.int64 and table.is_contiguous() and table.shape[1] == 10
+    assert out_t.dtype == torch.uint8 and out_t.is_contiguous() and tuple(out_t.shape) == (table.shape[0], out, out)
+    call("ecamp_resample_boxes_u8", ptr(flat), ptr(table), ptr(out_t), table.shape[0], int(out), int(kmax), int(tmp_rows), int(max_h), int(filter), ptr(ws),
+         ws.numel(), ptr(err), stream())
     return out_t

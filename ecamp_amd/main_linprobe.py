@@ -9,7 +9,8 @@ ECAMP/Fine-tuning/Classification (run_lp.sh), on one MI355X:
 
 The reference's flag names are kept.  Added: --list_dir (the reference hard-codes ./datasets/<task>), --compute_dtype {bf16,fp16,fp32}
 (--fp16 is --compute_dtype fp16; --fp16_opt_level is accepted and ignored), --pool {avg,cls}, --f32_residual, --synthetic,
---synthetic_len, --num_workers, --print_freq, --drop_path_rate (main_finetune's stochastic depth; refused here unless 0: the frozen
+--synthetic_len, --num_workers, --print_freq, --image_shard_dir (the image pipeline on the device, over pre-decoded uint8 shards; see its
+help), --drop_path_rate (main_finetune's stochastic depth; refused here unless 0: the frozen
 encoder of the probe is deterministic), --train_pos_embed (main_finetune's trained position table; refused here), --fp16_loss_scale (main_finetune's loss scale of IEEE-half
 fine-tuning; ignored here: the head and its gradient are f32).  `--stage train` trains, then tests the best checkpoint, as the reference does.
 
@@ -25,6 +26,8 @@ import torch
 
 TASKS = ["ChestX-ray14", "CheXpert", "RSNA", "SIIM", "COVIDx", "Aptos", "SpineXR", "ODIR5K", "MURED"]
 SINGLE_LABEL_TASKS = ("COVIDx", "Aptos")   # train.py:118-121: everything else is multilabel
+IMAGE_PIPELINE_LINE = ("NOTE: the image pipeline runs on the device (--image_shard_dir %s): crop, BILINEAR resample, flip and normalisation of the "
+                       "pre-decoded uint8 shards; the bytes of the host transforms for grayscale sources")
 
 
 def get_args_parser():
@@ -76,6 +79,11 @@ def get_args_parser():
                    help="--mode Finetune with --fp16 / --compute_dtype fp16: fine-tune in IEEE half under a loss scale.  dynamic: the reference's "
                         "apex recipe (from 2^20, halved when a step overflows and that step skipped, doubled after 2000 clean steps); a power "
                         "of two: that scale, static.  Without it fp16 fine-tuning is refused; --mode LinearProbe ignores it")
+    p.add_argument("--image_shard_dir", type=str, default="", metavar="DIR",
+                   help="run the image pipeline on the device: DIR holds one uint8 shard per list file (<list file name>.u8 + .idx.npy, made by "
+                        "tools/make_image_shard.py --list_dir ... --dataset_path ... --out_dir DIR); loader workers send the bytes of the crop box, "
+                        "the device resamples them with Pillow's BILINEAR arithmetic and the model reads uint8 images.  The same bytes as the "
+                        "host transforms for grayscale sources; colour sources are refused when the shard is made")
     return p
 
 
@@ -107,11 +115,27 @@ def check_common(args):
     args.is_multilabel = args.task not in SINGLE_LABEL_TASKS
     if args.stage == "train" and not (args.pretrained_path or args.synthetic):
         raise SystemExit("--stage train needs --pretrained_path <pre-training checkpoint> (or --synthetic, which probes a random encoder)")
-    if not args.synthetic and not args.dataset_path:
+    shard_dir = getattr(args, "image_shard_dir", "")
+    if shard_dir and args.synthetic:
+        raise SystemExit("--image_shard_dir with --synthetic: the synthetic stand-in reads no images, there is nothing to resample on the device")
+    if not args.synthetic and not args.dataset_path and not shard_dir:   # (the shards hold the images: --dataset_path is then not read)
         raise SystemExit("--dataset_path is required (or --synthetic)")
     if not args.list_dir:
         args.list_dir = os.path.join("datasets", args.task)
+    if shard_dir:
+        check_image_shards(args)
     return args
+
+
+def check_image_shards(args):
+    """`--image_shard_dir`: every split this run reads needs its shard, with as many images as its list has lines -- found out here,
+    from two small files per split, before any device work."""
+    from .module import finetune_datasets as fd
+    for split in (("train", "val", "test") if args.stage == "train" else ("test",)):
+        try:
+            fd.check_shard(fd.shard_path(args.image_shard_dir, split, args.data_volume), os.path.join(args.list_dir, fd.list_file(split, args.data_volume)))
+        except (FileNotFoundError, ValueError) as e:
+            raise SystemExit("--image_shard_dir %s, %s split: %s" % (args.image_shard_dir, split, e))
 
 
 def build_model(args):
@@ -126,6 +150,12 @@ def build_loader(args, split):
 
     from .module import finetune_datasets as fd
     train = split == "train"
+    batch_size = args.train_batch_size if train else args.eval_batch_size
+    if getattr(args, "image_shard_dir", ""):
+        ds = fd.ShardListDataset(args.image_shard_dir, args.list_dir, split, data_volume=args.data_volume, img_size=args.img_size, ratio=args.ratio)
+        print("%s set: %d samples (image shard %s)" % (split, len(ds), ds.shard_path))
+        loader = DataLoader(ds, shuffle=train, batch_size=batch_size, num_workers=args.num_workers, pin_memory=True, collate_fn=fd.collate_boxes)
+        return fd.DeviceImageLoader(loader, torch.device("cuda"), args.img_size)
     if args.synthetic:
         n = args.synthetic_len if train else max(1, args.synthetic_len // 2)
         ds = fd.SyntheticClassificationDataset(n, args.img_size, args.num_classes, args.is_multilabel, seed=args.seed + {"train": 0, "val": 1, "test": 2}[split])
@@ -133,8 +163,7 @@ def build_loader(args, split):
         tf = fd.train_transform(args.img_size) if train else fd.eval_transform(args.img_size, args.ratio)
         ds = fd.ListDataset(args.dataset_path, args.list_dir, split, data_volume=args.data_volume, transform=tf)
     print("%s set: %d samples" % (split, len(ds)))
-    return DataLoader(ds, shuffle=train, batch_size=args.train_batch_size if train else args.eval_batch_size, num_workers=args.num_workers,
-                      pin_memory=True)
+    return DataLoader(ds, shuffle=train, batch_size=batch_size, num_workers=args.num_workers, pin_memory=True)
 
 
 def run(args, engine, build_model, count_parameters, opening, eval_mode=False):
@@ -157,6 +186,8 @@ def run(args, engine, build_model, count_parameters, opening, eval_mode=False):
     torch.manual_seed(args.seed)
     for line in opening:
         log(line)
+    if getattr(args, "image_shard_dir", ""):
+        log(IMAGE_PIPELINE_LINE % args.image_shard_dir)
     if args.stage == "train":
         writer = None
         try:

@@ -83,7 +83,8 @@ class ECAMPClassifier(nn.Module):
         return self._noise[key]
 
     def _features(self, imgs, pool, drop_path=False):
-        """The encoder body, imgs f32 [B, 3, R, R] -> f32 [B, D]: stem, blocks, then "avg": the mean of the patch tokens of the last
+        """The encoder body, imgs f32 [B, 3, R, R] (or the uint8 grayscale bytes [B, R, R] / [B, 1, R, R] before ToTensor / Normalize: the
+        same bits) -> f32 [B, D]: stem, blocks, then "avg": the mean of the patch tokens of the last
         block's output and `fc_norm` (global_pool=True; the encoder's own `norm` is not applied); "cls": `norm(x)[:, 0]`
         (models_vit.py:78-97).  Every patch is kept in place (identity noise, ratio 0: the Philox counter is not advanced).  Differentiable
         down to the stem where gradients are enabled; under no_grad the same kernels in the same order, hence the same bits.
@@ -92,11 +93,23 @@ class ECAMPClassifier(nn.Module):
         from ..functions import NormFn, PoolNormFn, StemFn, VitBlockFn
         m = self.encoder
         A = m.prepare()
-        imgs = imgs.to(A.device, dtype=torch.float32, non_blocking=True).contiguous()
-        if imgs.dim() != 4 or imgs.shape[1:] != (3, m.img_size, m.img_size):
-            raise ValueError("imgs must be [B,3,%d,%d], got %s" % (m.img_size, m.img_size, tuple(imgs.shape)))
+        R = m.img_size
+        lut = None
+        if imgs.dtype == torch.uint8:
+            # the device image pipeline's item (finetune_datasets.DeviceImageLoader): the grayscale bytes before ToTensor / Normalize; the
+            # stem normalises them through the table of the classification constants while it gathers the patches (ecamp_im2col_u8)
+            if tuple(imgs.shape[1:]) not in ((R, R), (1, R, R)):
+                raise ValueError("uint8 imgs must be [B,%d,%d] or [B,1,%d,%d], got %s" % (R, R, R, R, tuple(imgs.shape)))
+            from .. import hip_ops as ops
+            from .finetune_datasets import FT_MEAN, FT_STD
+            imgs = imgs.to(A.device, non_blocking=True).reshape(imgs.shape[0], R, R).contiguous()
+            lut = ops.image_lut(A.device, FT_MEAN, FT_STD)
+        else:
+            imgs = imgs.to(A.device, dtype=torch.float32, non_blocking=True).contiguous()
+            if imgs.dim() != 4 or imgs.shape[1:] != (3, R, R):
+                raise ValueError("imgs must be f32 [B,3,%d,%d] (or uint8 [B,%d,%d]), got %s" % (R, R, R, R, tuple(imgs.shape)))
         B = imgs.shape[0]
-        x, _, _, _, ids_keep = StemFn.apply(imgs, self._identity_noise(B, A.device), m, 0.0, m.cls_token)
+        x, _, _, _, ids_keep = StemFn.apply(imgs, self._identity_noise(B, A.device), m, 0.0, m.cls_token, lut)
         T = ids_keep.shape[1] + 1
         for i, blk in enumerate(m.blocks):
             if drop_path and self.drop_path_rates[i] > 0:

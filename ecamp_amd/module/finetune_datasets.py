@@ -149,3 +149,172 @@ class SyntheticClassificationDataset(Dataset):
         band = torch.arange(R) * C // R                      # the class whose band a row belongs to
         img = img + (bits[band].to(torch.float32) * 2.0 - 1.0)[:, None]
         return img[None].expand(3, R, R).contiguous(), label
+
+
+# ---- the image half on the device (csrc/augment.hip: ecamp_resample_boxes_u8; csrc/vision.hip: ecamp_im2col_u8) -------------------------
+# The transforms above cost a loader worker a decode, a crop, a resample and twelve bytes per pixel through pinned memory and PCIe per
+# sample.  The path below keeps their RESULT and moves the work, as `--image_shard` does for pre-training: the images of a list file are
+# decoded once, offline, into a uint8 shard (tools/make_image_shard.py --list_dir); a worker draws the box and the flip (training: the same
+# torch-RNG calls in the same order) or works out the Resize + CenterCrop geometry in integers (evaluation) and copies bytes; the device
+# resamples the batch with Pillow's own BILINEAR fixed-point arithmetic and hands the classifier uint8 [B, R, R], which its stem
+# normalises through the table of FT_MEAN / FT_STD.  Byte for byte the host item for GRAYSCALE sources (three equal channels: each is
+# resampled alike and Grayscale returns the common value); Grayscale after the resample of a colour image is not the resample of its gray
+# plane, so colour sources (Aptos, ODIR5K, MURED) are refused when the shard is made.
+def device_train_item(image, img_size):
+    """`train_transform`'s share of a loader worker: draw the crop box, then the flip (the same calls in the same order) -> (the BOX's
+    bytes, uint8 [h, w], a view of `image`; flip; (full_w, shift_w, full_h, shift_h) = (s, 0, s, 0): the box is resized to s x s)."""
+    if not isinstance(image, np.ndarray):
+        image = np.asarray(image.convert("L"), dtype=np.uint8)
+    H, W = image.shape
+    i, j, h, w = random_resized_crop_params(W, H, scale=(0.08, 1.0))
+    flip = random_flip()
+    return image[i:i + h, j:j + w], flip, (int(img_size), 0, int(img_size), 0)   # a view: `pack_boxes` makes the one copy
+
+
+def _round_half_even_of_half(d):
+    """Python's round(d / 2.0) of an integer d >= 0, in integers: ties go to the even neighbour."""
+    q, r = divmod(d, 2)
+    return q + (r & q & 1)
+
+
+def eval_geometry(w, h, img_size, ratio=1.0):
+    """`eval_transform` as numbers: Resize(S = int(img_size / ratio)) makes the image (nw, nh) (`resize_short_side`: untouched when the short
+    side is S already); CenterCrop pads with zeros where that is smaller than the crop and cuts at round((n' - size) / 2) of the padded
+    canvas.  Per axis: `full` = n, and the crop's pixel x is pixel x + shift of the resized axis (outside [0, full): zero), with
+    shift = round((max(n, size) - size) / 2) - pad, pad = (size - n) // 2 if size > n else 0.  -> (full_w, shift_w, full_h, shift_h)."""
+    size, S = int(img_size), int(img_size / ratio)
+    short, long_ = (w, h) if w <= h else (h, w)
+    if short == S:
+        nw, nh = w, h
+    else:
+        new_long = (S * long_) // short            # int(S * long / short): exact in integers
+        nw, nh = (S, new_long) if w <= h else (new_long, S)
+    out = []
+    for n in (nw, nh):
+        pad = (size - n) // 2 if size > n else 0
+        out += [n, _round_half_even_of_half(max(n, size) - size) - pad]
+    return tuple(out)
+
+
+def device_eval_item(image, img_size, ratio=1.0):
+    """`eval_transform`'s share of a loader worker -> (the WHOLE image's bytes, uint8 [H, W]; flip = False; `eval_geometry`)."""
+    if not isinstance(image, np.ndarray):
+        image = np.asarray(image.convert("L"), dtype=np.uint8)
+    H, W = image.shape
+    return np.ascontiguousarray(image), False, eval_geometry(W, H, img_size, ratio)
+
+
+def bilinear_taps(in_size, full):
+    """Pillow's ksize of a BILINEAR resize of an axis from `in_size` to `full`: 2 * ceil(max(1, in / full)) + 1, in integers."""
+    return 2 * max(1, -(-int(in_size) // int(full))) + 1
+
+
+def pack_boxes(items, pin=False):
+    """Batch of `device_train_item` / `device_eval_item` results -> (flat uint8 tensor of all boxes back to back, int64 table [B, 10] for
+    ecamp_resample_boxes_u8: byte offset, h, w, flip, first intermediate row, full_w, shift_w, full_h, shift_h, 0; meta = (tap count of the
+    batch's largest scale factor, sum of h, largest h) as Python ints, made here so that the step never reads the table back)."""
+    total = sum(c.shape[0] * c.shape[1] for c, _, _ in items)
+    if torch.utils.data.get_worker_info() is not None:
+        # in a loader worker: straight into shared memory, as torch's default_collate does -- the bytes are then copied once here (from
+        # the shard's pages) and once more by the pinning thread, instead of a third time when the batch is handed to the main process
+        flat = torch.empty(0, dtype=torch.uint8)
+        flat = flat.new(flat._typed_storage()._new_shared(total)).resize_(total)
+    else:
+        flat = torch.empty((total,), dtype=torch.uint8, pin_memory=pin)
+    table = torch.zeros((len(items), 10), dtype=torch.int64, pin_memory=pin)
+    fa, ta = flat.numpy(), table.numpy()
+    off = row = max_h = 0
+    kmax = 3
+    for n, (c, flip, (fw, sw, fh, sh)) in enumerate(items):
+        h, w = c.shape
+        fa[off:off + h * w].reshape(h, w)[...] = c
+        ta[n, :9] = (off, h, w, int(flip), row, fw, sw, fh, sh)
+        kmax = max(kmax, bilinear_taps(w, fw), bilinear_taps(h, fh))
+        off += h * w
+        row += h
+        max_h = max(max_h, h)
+    return flat, table, (kmax, row, max_h)
+
+
+def collate_boxes(batch):
+    """collate_fn of `ShardListDataset`: [(item, labels)] -> (flat bytes, table, meta, labels [B, k])."""
+    flat, table, meta = pack_boxes([item for item, _ in batch])
+    return flat, table, meta, torch.stack([y for _, y in batch])
+
+
+class ShardListDataset(Dataset):
+    """The labels of `<list_dir>/<list of the split>` over the shard that holds the list's images in list order
+    (`<shard_dir>/<list file name>.u8`, tools/make_image_shard.py --list_dir): (`device_train_item` or `device_eval_item`, labels)."""
+
+    def __init__(self, shard_dir, list_dir, split, data_volume=None, img_size=224, ratio=1.0):
+        from .pretrain_datasets import U8ShardReader
+        self.split, self.img_size, self.ratio = split, int(img_size), ratio
+        self.list_path = os.path.join(list_dir, list_file(split, data_volume))
+        self.shard_path = shard_path(shard_dir, split, data_volume)
+        check_shard(self.shard_path, self.list_path)
+        _, self.labels = read_list(self.list_path)
+        self.shard = U8ShardReader(self.shard_path)
+
+    def __len__(self):
+        return len(self.labels)
+
+    def __getitem__(self, index):
+        img = self.shard[index]
+        item = device_train_item(img, self.img_size) if self.split == "train" else device_eval_item(img, self.img_size, self.ratio)
+        return item, torch.FloatTensor(self.labels[index])
+
+
+def shard_path(shard_dir, split, data_volume=None):
+    return os.path.join(shard_dir, list_file(split, data_volume) + ".u8")
+
+
+def check_shard(path, list_path):
+    """Raise unless the shard `path` (+ its index) exists and holds as many images as `list_path` has lines.  Reads two small files."""
+    if not os.path.exists(list_path):
+        raise FileNotFoundError("%s not found: check --list_dir (the directory with train_list*.txt, val_list.txt, test_list.txt)" % list_path)
+    if not (os.path.exists(path) and os.path.exists(path + ".idx.npy")):
+        raise FileNotFoundError("image shard %s (+ .idx.npy) not found: make it with tools/make_image_shard.py --list_dir ... --dataset_path ... "
+                                "--out_dir %s" % (path, os.path.dirname(path)))
+    n, want = len(np.load(path + ".idx.npy")), len(read_list(list_path)[0])
+    if n != want:
+        raise ValueError("image shard %s holds %d images, %s lists %d: the shard was made from another list" % (path, n, list_path, want))
+
+
+class DeviceBoxResampler:
+    """boxes (flat uint8 + table [B, 10] + meta, host or device) -> uint8 [B, size, size] on the device: the classification transforms'
+    resample (+ flip), Pillow-exact (ecamp_resample_boxes_u8, BILINEAR).  The workspace grows to the largest batch seen and is reused."""
+
+    def __init__(self, device, size):
+        self.device, self.size = torch.device(device), int(size)
+        self.ws = None
+        self.err = torch.zeros((1,), dtype=torch.int32, device=self.device)
+
+    def __call__(self, flat, table, meta, check=False):
+        from .. import hip_ops as ops
+        B = table.shape[0]
+        kmax, rows, max_h = (int(v) for v in meta)
+        need = ops.resample_boxes_workspace_bytes(B, self.size, kmax, rows)
+        if self.ws is None or self.ws.numel() < need:
+            self.ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        out = torch.empty((B, self.size, self.size), dtype=torch.uint8, device=self.device)
+        ops.resample_boxes_u8(flat.to(self.device, non_blocking=True), table.to(self.device, non_blocking=True), out, self.size, kmax, rows, max_h,
+                              self.ws, self.err, filter=ops.BILINEAR)
+        if check and int(self.err.item()) != 0:
+            raise RuntimeError("ecamp_resample_boxes_u8: a box needed more taps than the table was sized for")
+        return out
+
+
+class DeviceImageLoader:
+    """A DataLoader over a `ShardListDataset` (collate_fn=collate_boxes) -> (uint8 [B, R, R] on the device, labels): what
+    engine_linprobe's loops iterate, the image being the bytes `ECAMPClassifier` normalises in its stem."""
+
+    def __init__(self, loader, device, img_size):
+        self.loader, self.dataset = loader, loader.dataset
+        self.resample = DeviceBoxResampler(device, img_size)
+
+    def __len__(self):
+        return len(self.loader)
+
+    def __iter__(self):
+        for flat, table, meta, y in self.loader:
+            yield self.resample(flat, table, meta), y

@@ -29,7 +29,8 @@ typedef struct ihipStream_t* ecampStream_t; /* == hipStream_t */
  * ecamp_layernorm_fwd_x32, ecamp_layernorm_bwd_z32, ecamp_assemble_tokens_x32, ecamp_unshuffle_fwd_x32).  ecamp_abi_version()
  * returns the value the library was BUILT with; a consumer compares it with the header it was compiled against -- the Python binding
  * (ecamp_amd/_lib.py) refuses a library of another version, which is what protects an A/B of two builds (ECAMP_LIB, tools/ab_lib.sh)
- * from calling an older build with a newer argument list.  ecamp_ce_eval -- and later ecamp_drop_path_fwd / ecamp_drop_path_bwd and ecamp_pos_embed_grad -- were
+ * from calling an older build with a newer argument list.  ecamp_ce_eval -- and later ecamp_drop_path_fwd / ecamp_drop_path_bwd, ecamp_pos_embed_grad,
+ * ecamp_resample_boxes_u8 (+ its workspace function) and ecamp_im2col_u8 -- were
  * ADDED at version 5 without touching an existing signature: a build that lacks them is refused by the binding all the same, which
  * resolves every declared symbol when it loads. */
 #define ECAMP_ABI_VERSION 5
@@ -250,6 +251,21 @@ int ecamp_assemble_tokens_x32(const void* x, float* out, const float* cls, const
 int64_t ecamp_resample_crops_workspace_bytes(int64_t B, int32_t out, int32_t kmax, int64_t tmp_rows);
 int ecamp_resample_crops_u8(const uint8_t* src, const int64_t* table, uint8_t* dst, int64_t B, int32_t out, int32_t kmax, int64_t tmp_rows,
                             int32_t max_h, void* ws, int64_t ws_bytes, int32_t* err_flag, ecampStream_t stream);
+/* The classification transforms on the device (Fine-tuning/Classification/utils/data_utils.py:20-34: RandomResizedCrop((s, s)) + flip,
+ * and Resize(int) + CenterCrop((s, s)), Pillow BILINEAR): the same two-pass resample with a filter argument (0: BILINEAR, 1: BICUBIC) and,
+ * per axis, `full` -- the size the axis is resized to -- and `shift` -- where the `out` output pixels start in the resized axis; an output
+ * pixel outside [0, full) is 0 (CenterCrop's zero padding).  table int64 [B, 10] on the device = {byte offset in src, h, w, flip (0/1), first
+ * intermediate row, full_w, shift_w, full_h, shift_h, 0}; a training crop is full = out, shift = 0.  kmax >= 2 * ceil(support *
+ * max(1, size / full)) + 1 of every sample and axis (support 1 bilinear, 2 bicubic); the other arguments as ecamp_resample_crops_u8, ws
+ * from ecamp_resample_boxes_workspace_bytes.  Filter 1 with full = out, shift = 0 gives the bytes of ecamp_resample_crops_u8. */
+int64_t ecamp_resample_boxes_workspace_bytes(int64_t B, int32_t out, int32_t kmax, int64_t tmp_rows);
+int ecamp_resample_boxes_u8(const uint8_t* src, const int64_t* table, uint8_t* dst, int64_t B, int32_t out, int32_t kmax, int64_t tmp_rows,
+                            int32_t max_h, int32_t filter, void* ws, int64_t ws_bytes, int32_t* err_flag, ecampStream_t stream);
+/* ecamp_im2col_gather straight from a uint8 grayscale image [B, R, R] at the model's own size: out [B * (Lk + 1), 3 * p * p] (f32 or the
+ * build's 16-bit format), the cls row zero, the three channel slabs the same values lut[byte] -- bit for bit ecamp_im2col_gather on
+ * lut[img] expanded to three planes (lut as in ecamp_bicubic_resize_u8, built from the caller's mean / std). */
+int ecamp_im2col_u8(const uint8_t* img, const float* lut, const int32_t* ids_keep, void* out, int64_t B, int32_t Lk, int32_t R, int32_t p,
+                    int32_t dtype, ecampStream_t stream);
 int ecamp_unshuffle_fwd(const void* y, const int32_t* ids_restore, const float* mask_token, const float* dpos, void* xd, int64_t B,
                         int32_t L, int32_t Lk, int32_t D, int32_t dtype, ecampStream_t stream); /* model_ecamp.py:245-251 */
 /* ecamp_unshuffle_fwd with an f32 xd from the 16-bit (dtype 1) y: the decoder's f32 residual stream (autocast promotes the cat of the half

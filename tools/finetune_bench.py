@@ -37,6 +37,16 @@
   11 `ecamp_sgd_scale_update` alone beside an empty launch (`ecamp_dev_spin`, one workgroup, zero cycles), alternating in one loop.
   `--parity_log FILE`: the "[fp16-finetune]" lines that tests/test_sgd_scale_kernel_gpu.py and tests/test_fp16_finetune_model_gpu.py print under
   `pytest -s` are copied behind the timings.
+
+`--image_pipeline` runs another leg INSTEAD and writes profiles/finetune_image_pipeline.txt (`--image_pipeline_out`):
+
+  13 `ecamp_resample_boxes_u8` (BILINEAR, R = 224) on B training crops of 1024 x 1024 sources (boxes drawn by `device_train_item`), and
+     `ecamp_im2col_u8` on the resulting uint8 [B, 224, 224] beside `ecamp_im2col_gather` on the f32 [B, 3, 224, 224] image, per call.
+  14 the whole fine-tune step of leg 1 on a resident f32 batch -- the code of the commit before the uint8 path existed, launch for launch --
+     against the same step on the resident uint8 batch of the same pixels, ONE model and optimizer, blocks alternating three times.
+  15 images/s of the host loader (ListDataset + train_transform: PIL decode, crop, resample, f32 planes) and of the device loader
+     (ShardListDataset + DeviceImageLoader) with the same worker count over the same generated PNG set (`--loader_images` files of
+     1024 x 1024), each over one full pass after a first pass that starts the workers.
 """
 import argparse
 import os
@@ -331,6 +341,136 @@ def fp16_leg(args, say):
                 say("   " + line[line.index("[fp16-finetune]"):].strip())
 
 
+def image_pipeline_leg(args, say):
+    """Legs 13 to 15 (see the module docstring)."""
+    import shutil
+    import tempfile
+
+    import numpy as np
+    from torch.utils.data import DataLoader
+
+    from ecamp_amd import engine_finetune
+    from ecamp_amd import hip_ops as ops
+    from ecamp_amd.module import finetune_datasets as fd
+    from ecamp_amd.module.classifier import build_classifier
+    from ecamp_amd.module.pretrain_datasets import U8ShardWriter
+    dev = torch.device("cuda")
+    C, R, S = args.classes, 224, 1024
+    batches = [int(b) for b in args.batches.split(",")]
+    say("the classification image pipeline on the device, on %s: R = %d, sources %d x %d, training crop scales 0.08 to 1" % (torch.cuda.get_device_name(0), R, S, S))
+    rng = np.random.default_rng(0)
+    base = [np.clip(127 + 80 * np.sin(np.add.outer(np.arange(S) / (5.0 + k), np.arange(S) / (9.0 - k))) + rng.integers(-30, 31, (S, S)), 0, 255).astype(np.uint8)
+            for k in range(4)]
+    lut = ops.image_lut(dev, fd.FT_MEAN, fd.FT_STD)
+    say("13 kernels alone, per call, from event pairs around 10 back-to-back calls, alternating in one loop (%d groups after %d warm-up groups)" % (args.iters, args.warmup))
+    resident = {}
+    for B in batches:
+        torch.manual_seed(B)
+        flat, table, meta = fd.pack_boxes([fd.device_train_item(base[b % 4], R) for b in range(B)])
+        flat_d, table_d = flat.to(dev), table.to(dev)
+        rs = fd.DeviceBoxResampler(dev, R)
+        u8 = rs(flat_d, table_d, meta, check=True)
+        ids = torch.arange(196, dtype=torch.int32, device=dev).expand(B, 196).contiguous()
+        f32 = lut[u8.long()][:, None].expand(B, 3, R, R).contiguous()
+        assert torch.equal(ops.im2col_u8(u8, lut, ids, 16, torch.bfloat16).view(torch.int16), ops.im2col_gather(f32, ids, 16, torch.bfloat16).view(torch.int16))
+        us = event_groups([("ecamp_resample_boxes_u8", lambda: rs(flat_d, table_d, meta)),
+                           ("ecamp_im2col_u8 (bf16 cols)", lambda: ops.im2col_u8(u8, lut, ids, 16, torch.bfloat16)),
+                           ("ecamp_im2col_gather on f32 (bf16 cols)", lambda: ops.im2col_gather(f32, ids, 16, torch.bfloat16))], args.iters, args.warmup, 10)
+        say("   B = %3d: %.1f MB of box bytes, %d taps, tallest box %d rows" % (B, flat.numel() / 1e6, meta[0], meta[2]))
+        for name, xs in us.items():
+            med, lo, hi = stats(xs)
+            say("      %-40s median %8.1f us (min %.1f, max %.1f)" % (name, med, lo, hi))
+        resident[B] = (f32, u8)
+        del flat_d, table_d, rs
+    torch.manual_seed(0)
+    clf = build_classifier("vit_base_patch16", C, True, img_size=R, compute_dtype=torch.bfloat16, train_encoder=True).to(dev)
+    step_args = argparse.Namespace(learning_rate=3e-2, weight_decay=1e-4, decay_type="cosine", warmup_steps=50, num_steps=3000, max_grad_norm=1.0)
+    opt = engine_finetune.make_optimizer(clf, step_args)
+    say("14 the whole fine-tune step (ViT-B/16, bf16, forward + backward + clip + SGD) on a resident f32 [B, 3, %d, %d] batch -- the parent commit's step: "
+        "that path runs the parent's kernels launch for launch -- against the resident uint8 [B, %d, %d] batch of the same pixels; one model and optimizer, "
+        "blocks of %d steps alternating parent / new three times, host clock around a block that ends in a device synchronise, after %d warm-up steps each"
+        % (R, R, R, R, args.iters, args.warmup))
+    n = [0]
+    step_rate = {}
+    for B in batches:
+        f32, u8 = resident[B]
+        y = (torch.rand(B, C, device=dev) < 0.3).float()
+
+        def block(x, steps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                engine_finetune.train_step(clf, opt, x, y, n[0], step_args)
+                n[0] += 1
+            torch.cuda.synchronize()
+            return 1e3 * (time.perf_counter() - t0) / steps
+
+        block(f32, args.warmup)
+        block(u8, args.warmup)
+        old, new = [], []
+        for _ in range(3):
+            old.append(block(f32, args.iters))
+            new.append(block(u8, args.iters))
+        mo, mn, spread = statistics.median(old), statistics.median(new), max(old) - min(old)
+        step_rate[B] = B / (mn * 1e-3)
+        say("   B = %3d  parent (f32): %s ms = %.0f images/s;  new (uint8): %s ms = %.0f images/s;  new - parent = %+.3f ms (medians); the parent's own spread "
+            "across its three runs: %.3f ms -> %s" % (B, " ".join("%.2f" % v for v in old), B / (mo * 1e-3), " ".join("%.2f" % v for v in new), B / (mn * 1e-3),
+                                                   mn - mo, spread, "not slower" if mn - mo <= spread else "SLOWER than the parent by more than its spread"))
+    del clf, opt, resident
+    # leg 15: the loaders, over files written here
+    from PIL import Image
+    root = tempfile.mkdtemp(prefix="ecamp_image_pipeline_")
+    try:
+        N, W = args.loader_images, args.loader_workers
+        os.makedirs(os.path.join(root, "img"))
+        lines = []
+        for k in range(N):
+            a = np.roll(base[k % 4], 37 * k, axis=1)
+            Image.fromarray(a, "L").save(os.path.join(root, "img", "i%d.png" % k), compress_level=1)
+            lines.append("img/i%d.png %s" % (k, " ".join(str((k >> c) & 1) for c in range(C))))
+        rep = args.loader_repeat          # the list names every file `rep` times: passes long enough to time, without writing more files
+        open(os.path.join(root, "train_list.txt"), "w").write("\n".join(lines * rep) + "\n")
+        with U8ShardWriter(os.path.join(root, "train_list.txt.u8")) as w:
+            for _ in range(rep):
+                for k in range(N):
+                    w.add(np.roll(base[k % 4], 37 * k, axis=1))
+        say("15 loaders: one pass over a list of %d samples (%d PNG files of %d x %d, lossless, each listed %d times; the shard holds the same pixels in list "
+            "order), batch 96, %d workers each, pinned memory; the pass is timed after a first pass (worker start-up, file cache); host: ListDataset + "
+            "train_transform -> f32 [96, 3, %d, %d]; device: ShardListDataset + DeviceImageLoader -> uint8 [96, %d, %d] in HBM (the resample included; the "
+            "timed pass ends in a device synchronise)" % (N * rep, N, S, S, rep, W, R, R, R, R))
+        host = DataLoader(fd.ListDataset(root, root, "train", data_volume="100", transform=fd.train_transform(R)), shuffle=True, batch_size=96, num_workers=W,
+                          pin_memory=True, persistent_workers=W > 0)
+        def device_loader(workers):
+            return fd.DeviceImageLoader(DataLoader(fd.ShardListDataset(root, root, "train", data_volume="100", img_size=R), shuffle=True, batch_size=96,
+                                                   num_workers=workers, pin_memory=True, collate_fn=fd.collate_boxes, persistent_workers=workers > 0), dev, R)
+
+        rates, slowest = {}, {}
+        for name, loader in (("host loader", host), ("device loader", device_loader(W)), ("device loader, %d workers" % (2 * W), device_loader(2 * W))):
+            per = []
+            for rep in range(3):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                seen = 0
+                for x, _ in loader:
+                    x = x.to(dev, non_blocking=True)
+                    seen += x.shape[0]
+                torch.cuda.synchronize()
+                per.append(seen / (time.perf_counter() - t0))
+            rates[name], slowest[name] = statistics.median(per[1:]), min(per[1:])
+            say("   %-26s %8.0f images/s (passes after the first: %s)" % (name, rates[name], " ".join("%.0f" % v for v in per[1:])))
+            del loader
+        say("   device / host = %.1f x with the same %d workers" % (rates["device loader"] / rates["host loader"], W))
+        say("   the rates these must feed: the fine-tune step of leg 14 on the uint8 batch (%s images/s), and profiles/finetune.txt / profiles/linprobe.txt: about "
+            "6 600 images/s for a fine-tune step at B = 96, 19 700 images/s for a probe step.  A loader FEEDS a step when its SLOWEST timed pass is at least the "
+            "step's rate:" % ", ".join("B = %d: %.0f" % (B, r) for B, r in step_rate.items()))
+        for name in rates:
+            verdict = ["fine-tune step at B = %d: %s" % (B, "FEEDS it" if slowest[name] >= r else "does NOT feed it") for B, r in step_rate.items()]
+            verdict.append("probe step (19 700): %s" % ("FEEDS it" if slowest[name] >= 19700 else "does NOT feed it"))
+            say("   %-26s slowest pass %6.0f images/s -> %s" % (name, slowest[name], "; ".join(verdict)))
+    finally:
+        shutil.rmtree(root, ignore_errors=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
@@ -345,9 +485,26 @@ def main():
     ap.add_argument("--pos_embed_out", type=str, default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "finetune_pos_embed.txt"))
     ap.add_argument("--fp16", action="store_true", help="run the IEEE-half / loss-scaler leg instead (profiles/finetune_fp16.txt)")
     ap.add_argument("--fp16_out", type=str, default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "finetune_fp16.txt"))
+    ap.add_argument("--image_pipeline", action="store_true", help="run the device-image-pipeline leg instead (profiles/finetune_image_pipeline.txt)")
+    ap.add_argument("--image_pipeline_out", type=str, default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "finetune_image_pipeline.txt"))
+    ap.add_argument("--loader_images", type=int, default=384, help="--image_pipeline: PNG files of the loader comparison")
+    ap.add_argument("--loader_repeat", type=int, default=8, help="--image_pipeline: times the list names each file")
+    ap.add_argument("--loader_workers", type=int, default=8, help="--image_pipeline: workers of both loaders (the drivers' default)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("finetune_bench needs an MI355X: nothing here can be measured on a CPU")
+    if args.image_pipeline:
+        lines = []
+
+        def say_ip(msg):
+            print(msg, flush=True)
+            lines.append(msg)
+
+        image_pipeline_leg(args, say_ip)
+        os.makedirs(os.path.dirname(os.path.abspath(args.image_pipeline_out)), exist_ok=True)
+        with open(args.image_pipeline_out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     if args.fp16:
         lines = []
 

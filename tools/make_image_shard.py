@@ -1,11 +1,23 @@
 #!/usr/bin/env python3
-"""Decode the radiographs of <data_path>/mimic-cxr-2.0.0-entity-llm.csv ONCE into a uint8 shard for `main_pretrain.py --image_shard`
-(module/pretrain_datasets.py: U8ShardWriter).
+"""Decode images ONCE into uint8 shards for the device image pipelines (module/pretrain_datasets.py: U8ShardWriter).
+
+Pre-training -- the radiographs of <data_path>/mimic-cxr-2.0.0-entity-llm.csv, for `main_pretrain.py --image_shard`:
 
     python tools/make_image_shard.py --data_path <dir> --out <dir>/images.u8 [--max_side 1024] [--workers 16]
 
 Without --max_side the shard holds the JPEGs' own pixels (7.8 MB per 2544 x 3056 radiograph: the crops are then exactly the reference's);
---max_side shrinks the longer side first (Pillow bicubic) -- smaller files and host -> HBM copies, crops from the shrunk image."""
+--max_side shrinks the longer side first (Pillow bicubic) -- smaller files and host -> HBM copies, crops from the shrunk image.
+
+Classification -- one shard per list file of a task, for `main_linprobe.py / main_finetune.py --image_shard_dir`:
+
+    python tools/make_image_shard.py --list_dir <lists> --dataset_path <images> --out_dir <dir> [--splits train_list.txt val_list.txt ...]
+
+writes <out_dir>/<list file name>.u8 (+ .idx.npy) with the list's images in list order, opened through `pil_loader` as the dataset opens
+them.  --splits: list file names (default: every one of train_list.txt, train_list_1.txt, train_list_10.txt, val_list.txt, test_list.txt
+that exists).  The device pipeline equals the host transforms byte for byte for GRAYSCALE sources only -- an image whose three channels
+are equal keeps that property through the resample, and Grayscale returns the common value; Grayscale after the resample of a colour
+image is NOT the resample of its gray plane.  An image whose channels differ therefore ends the run, naming the file: Aptos, ODIR5K and
+MURED are colour fundus photographs and stay on the host transforms."""
 import argparse
 import os
 import sys
@@ -15,6 +27,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+LIST_FILES = ("train_list.txt", "train_list_1.txt", "train_list_10.txt", "val_list.txt", "test_list.txt")
 
 
 def decode(args):
@@ -27,13 +41,63 @@ def decode(args):
     return np.asarray(img, dtype=np.uint8)
 
 
+def decode_gray(path):
+    """The dataset's `pil_loader` image as one uint8 plane, or None if its three channels differ (a colour source)."""
+    from ecamp_amd.module.pretrain_datasets import pil_loader
+    a = np.asarray(pil_loader(path), dtype=np.uint8)
+    if not (np.array_equal(a[..., 0], a[..., 1]) and np.array_equal(a[..., 0], a[..., 2])):
+        return None
+    return np.ascontiguousarray(a[..., 0])
+
+
+def shard_lists(list_dir, dataset_path, out_dir, splits, workers):
+    from ecamp_amd.module.finetune_datasets import read_list
+    from ecamp_amd.module.pretrain_datasets import U8ShardWriter
+    names = list(splits) if splits else [n for n in LIST_FILES if os.path.exists(os.path.join(list_dir, n))]
+    if not names:
+        raise SystemExit("no list file (%s) in %s" % (", ".join(LIST_FILES), list_dir))
+    os.makedirs(out_dir, exist_ok=True)
+    for name in names:
+        lp = os.path.join(list_dir, name)
+        if not os.path.exists(lp):
+            raise SystemExit("%s not found" % lp)
+        paths = [os.path.join(dataset_path, r) for r in read_list(lp)[0]]
+        out = os.path.join(out_dir, name + ".u8")
+        colour = None
+        with U8ShardWriter(out) as w, ProcessPoolExecutor(workers) as ex:
+            for n, arr in enumerate(ex.map(decode_gray, paths, chunksize=8)):
+                if arr is None:
+                    colour = paths[n]
+                    break
+                w.add(arr)
+                if n % 1000 == 0:
+                    print("%s: %d / %d" % (name, n, len(paths)), flush=True)
+        if colour is not None:   # no partial shard is left behind
+            os.remove(out)
+            os.remove(out + ".idx.npy")
+            raise SystemExit("%s is a COLOUR image (its three channels differ): the device image pipeline equals the host transforms "
+                             "for grayscale sources only (Grayscale after the resample is not the resample of the gray plane) -- "
+                             "keep this dataset on the host transforms (no --image_shard_dir)" % colour)
+        print("wrote %s (%d images, %.3f GB) + .idx.npy" % (out, len(paths), os.path.getsize(out) / 1e9))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--data_path", required=True)
-    ap.add_argument("--out", required=True)
+    ap.add_argument("--data_path", help="pre-training: the directory of mimic-cxr-2.0.0-entity-llm.csv")
+    ap.add_argument("--out", help="pre-training: the shard file to write")
     ap.add_argument("--max_side", type=int, default=0)
     ap.add_argument("--workers", type=int, default=os.cpu_count() or 1)
+    ap.add_argument("--list_dir", help="classification: the directory of train_list*.txt / val_list.txt / test_list.txt")
+    ap.add_argument("--dataset_path", help="classification: the root the lists' relative paths start from")
+    ap.add_argument("--out_dir", help="classification: where <list file name>.u8 go (default: --list_dir)")
+    ap.add_argument("--splits", nargs="*", default=None, help="classification: list file names (default: every known one that exists)")
     a = ap.parse_args()
+    if a.list_dir:
+        if a.dataset_path is None or a.data_path or a.out or a.max_side:
+            ap.error("--list_dir goes with --dataset_path [--out_dir] [--splits]; --data_path / --out / --max_side belong to the pre-training mode")
+        return shard_lists(a.list_dir, a.dataset_path, a.out_dir or a.list_dir, a.splits, a.workers)
+    if not (a.data_path and a.out):
+        ap.error("--data_path and --out are required (or --list_dir and --dataset_path)")
     import pandas as pd
     from ecamp_amd.module.pretrain_datasets import U8ShardWriter
     paths = list(pd.read_csv(os.path.join(a.data_path, "mimic-cxr-2.0.0-entity-llm.csv"))["img_path"])
