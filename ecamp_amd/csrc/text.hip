@@ -460,7 +460,11 @@ __global__ __launch_bounds__(NT) void ce_fwd_bwd_row_kernel(bf16_t* __restrict__
 }
 extern "C" int ecamp_ce_fwd_bwd(void* logits, const int64_t* labels, const float* weights, float* loss_sum, int64_t M, int32_t V,
                                 int64_t ld, float inv_count, int32_t dtype, hipStream_t stream) {
-    ECAMP_CHECK_ARG(logits && labels && weights && loss_sum && V % 4 == 0 && ld % 4 == 0, "ce_fwd_bwd: bad args");
+    ECAMP_CHECK_ARG(logits && labels && weights && loss_sum, "ce_fwd_bwd: null pointer");
+    ECAMP_CHECK_ARG(V > 0 && V % 4 == 0 && ld % 4 == 0 && ld >= V, "ce_fwd_bwd: V=%d and ld=%ld must be multiples of 4 (ld >= V > 0)", V, (long)ld);
+    ECAMP_CHECK_ARG(M >= 0 && M <= 0x7fffffffLL, "ce_fwd_bwd: M=%ld rows do not fit one launch", (long)M);
+    ECAMP_CHECK_ARG(dtype == ECAMP_F32 || dtype == ECAMP_BF16, "ce_fwd_bwd: dtype %d", dtype);
+    if (M == 0) return 0;
     dim3 grid((unsigned)M), block(256);
     if (dtype == ECAMP_BF16 && V % 8 == 0 && ld % 8 == 0 && V <= 32768 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0) {
         const int ce_variant = ecamp_opt(OPT_CE_KERNEL);   // development A/B: 0 = the two-exp kernel of round 2

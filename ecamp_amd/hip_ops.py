@@ -618,6 +618,9 @@ def ce_fwd_bwd_(logits, labels, weights, loss_sum, gain=1.0):
     the loss scale is known, and w (p - onehot) / M is 1e-9 for M = 32768 rows -- zero in IEEE half."""
     _chk(logits, labels, weights)
     M, V = logits.shape
+    assert logits.stride(1) == 1 and labels.numel() == M and weights.numel() == M
+    if M == 0:      # no rows (an empty tensor has no address to hand over)
+        return logits
     call("ecamp_ce_fwd_bwd", ptr(logits), ptr(labels), ptr(weights), ptr(loss_sum), M, V, logits.stride(0), float(gain) / M,
          code(logits.dtype), stream())
     return logits

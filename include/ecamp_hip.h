@@ -303,8 +303,14 @@ int ecamp_bert_embed_bwd(const void* de, const void* z, const float* mean, const
                          const int64_t* type_ids, float* gword, float* gpos, float* gtype, float* dgamma, float* dbeta, int64_t B,
                          int32_t S, int32_t cols, int32_t pad_id, int32_t hot0, int32_t hot1, float drop_p, uint64_t seed,
                          uint64_t offset, int32_t dtype, ecampStream_t stream);
+/* Weighted cross-entropy of the MLM head with its gradient written over the logits (bert_modeling.py:213-217).  `logits` [M, V], row
+ * stride ld, f32 or the build's 16-bit format; ld >= V > 0, V and ld multiples of 4, 0 <= M <= 2^31 - 1 (anything else, a null pointer
+ * or another dtype code is refused before any launch; M == 0 returns 0 without one).  Per row, with w = weights[i] and a label in
+ * [0, V):  loss_sum += w * (logsumexp(row) - logit[label])  and  logits[i, j] = inv_count * w * (softmax_ij - [j == label]);  a row
+ * whose label lies outside [0, V) (ignore_index -100) adds nothing and gets a row of zeros.  Columns [V, ld) are never written.
+ * inv_count = gain / M: the caller divides loss_sum by M and the gain out of the upstream gradient.  Logits must be finite. */
 int ecamp_ce_fwd_bwd(void* logits, const int64_t* labels, const float* weights, float* loss_sum, int64_t M, int32_t V, int64_t ld,
-                     float inv_count, int32_t dtype, ecampStream_t stream); /* bert_modeling.py:213-217 */
+                     float inv_count, int32_t dtype, ecampStream_t stream);
 /* Held-out evaluation of the same head (no reference counterpart: the reference has no validation loop).  Read-only on `logits`
  * [M, V] (row stride ld; V and ld multiples of 4).  A row whose label lies outside [0, V) (ignore_index -100) is skipped without a
  * read of its logits; for every other row, with xl = logit[label] and rank = #{ j : logit[j] > xl } (strictly greater: a label tied
