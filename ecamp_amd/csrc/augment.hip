@@ -10,6 +10,9 @@
 // MIMIC-CXR-JPG radiographs are grayscale: the reference's RGB crop has three equal channels, each resampled by the same integer
 // arithmetic, and Grayscale's L = (19595 R + 38470 G + 7471 B + 2^15) >> 16 returns that common value -- so one uint8 plane is the
 // whole item before ToTensor / Normalize (the `image_u8` schema the model's kernels already read).
+// COLOUR sources (the fundus tasks of the classification transforms, at the end of this file): Pillow resamples an RGB image band by
+// band with these coefficients and this uint8 intermediate, and Grayscale follows the resize -- so a colour sample keeps three planes
+// through both passes and ecamp_resample_boxes_rgb_u8 folds them with the formula above behind the vertical pass: the host's byte again.
 //
 // Host -> device: per sample only the bytes of the drawn crop box (contiguous h x w uint8) and a table row; the host draws the boxes
 // and flips from the torch RNG in torchvision's order (ecamp_amd/module/pretrain_datasets.py: crop_params).
@@ -20,7 +23,7 @@
 
 #define RS_PRECISION_BITS 22
 
-struct RsTab { long off, h, w, flip, row0, pad; };
+struct RsTab { long off, h, w, flip, row0, pad; };   // pad: column 9 of a stride-10 row -- 3: three planes (ecamp_resample_boxes_rgb_u8 alone reads it)
 
 __device__ __forceinline__ double rs_bicubic(double x) {
 #pragma clang fp contract(off)
@@ -56,7 +59,8 @@ template <> struct RsFilter<RS_BICUBIC> {
 // `tab`: rows of `stride` int64.  stride 6 (ecamp_resample_crops_u8): the RsTab row, every axis resized from its size to `out`.  stride 10
 // (ecamp_resample_boxes_u8): {off, h, w, flip, row0, full_w, shift_w, full_h, shift_h, 0} -- output index x of an axis is index
 // u = x + shift of a resize of that axis from its size to `full`; u outside [0, full) has no tap (the passes then write (2^21) >> 22 = 0:
-// CenterCrop's zero padding).  The RsTab share of such a row is copied to `tab_out` for the two passes.
+// CenterCrop's zero padding).  The RsTab share of such a row, and its last column (the plane count of the colour entry point: the taps
+// depend on h, w and the geometry only), are copied to `tab_out` for the two passes.
 template <int F>
 __global__ __launch_bounds__(256) void resample_coef_kernel(const long* __restrict__ tab, int stride, RsTab* __restrict__ tab_out, int2* __restrict__ bounds,
                                                             int* __restrict__ coef, long B, int out, int kmax, int* __restrict__ err) {
@@ -71,7 +75,7 @@ __global__ __launch_bounds__(256) void resample_coef_kernel(const long* __restri
     if (stride == 10) {
         full = (int)t[5 + 2 * axis];
         u = xx + (int)t[6 + 2 * axis];
-        if (xx == 0 && axis == 0) tab_out[b] = RsTab{t[0], t[1], t[2], t[3], t[4], 0};
+        if (xx == 0 && axis == 0) tab_out[b] = RsTab{t[0], t[1], t[2], t[3], t[4], t[9]};
     }
     int* k = coef + id * kmax;
     if (full <= 0 || inSize <= 0) {
@@ -119,15 +123,18 @@ __device__ __forceinline__ unsigned char rs_clip8(int v) {
     return (unsigned char)(v < 0 ? 0 : v > 255 ? 255 : v);
 }
 
-// horizontal pass: block = (sample, chunk of ROWS rows); thread xx owns output column xx, its taps live in LDS as [tap][column]
+// horizontal pass: block = (sample, chunk of ROWS rows); thread xx owns output column xx, its taps live in LDS as [tap][column].
+// PLANES (the colour entry point): a sample of three planes h x w back to back is 3 h rows of w bytes, resampled row by row alike.
 #define RS_ROWS 32
+template <bool PLANES>
 __global__ __launch_bounds__(512) void resample_h_kernel(const unsigned char* __restrict__ src, const RsTab* __restrict__ tab, const int2* __restrict__ bounds,
                                                          const int* __restrict__ coef, unsigned char* __restrict__ tmp, int out, int kmax) {
     extern __shared__ int kl[];   // [kmax][out]
     const long b = blockIdx.y;
     const RsTab t = tab[b];
     const int r0 = blockIdx.x * RS_ROWS;
-    if (r0 >= t.h) return;
+    const int rows = PLANES && t.pad == 3 ? 3 * (int)t.h : (int)t.h;
+    if (r0 >= rows) return;
     const long cid = (b * 2 + 0) * out;
     for (int i = threadIdx.x; i < out * kmax; i += blockDim.x) {
         const int xx = i / kmax, tp = i - xx * kmax;
@@ -137,7 +144,7 @@ __global__ __launch_bounds__(512) void resample_h_kernel(const unsigned char* __
     const int xx = threadIdx.x;
     if (xx >= out) return;
     const int2 bd = bounds[cid + xx];
-    const int r1 = min(r0 + RS_ROWS, (int)t.h);
+    const int r1 = min(r0 + RS_ROWS, rows);
     for (int r = r0; r < r1; ++r) {
         const unsigned char* p = src + t.off + (long)r * t.w + bd.x;
         int ss = 1 << (RS_PRECISION_BITS - 1);
@@ -162,9 +169,51 @@ __global__ __launch_bounds__(512) void resample_v_kernel(const unsigned char* __
     dst[(b * out + yy) * out + (t.flip ? out - 1 - xx : xx)] = rs_clip8(ss);
 }
 
+// vertical pass of the colour entry point (+ luma fold + flip).  A three-plane sample owns 3 h rows of the intermediate, plane p from
+// row0 + p h: the three clipped bytes of an output pixel come from the same taps, and Pillow's convert("L") folds them,
+// L = (19595 R + 38470 G + 7471 B + 2^15) >> 16 (at most 65536 * 255 + 2^15: int32).  No tap: three zeros, and 2^15 >> 16 = 0.  A one-plane
+// sample stores resample_v_kernel's byte.  One thread per output pixel, RS_VC_THREADS consecutive pixels of a sample per block: no lane
+// is idle but in a sample's last block, at any `out` (a block per output row keeps 224 of 256 lanes at out = 224, 16 of 64 at out = 16).
+#define RS_VC_THREADS 256
+__global__ __launch_bounds__(RS_VC_THREADS) void resample_v_rgb_kernel(const unsigned char* __restrict__ tmp, const RsTab* __restrict__ tab,
+                                                                       const int2* __restrict__ bounds, const int* __restrict__ coef,
+                                                                       unsigned char* __restrict__ dst, int out, int kmax) {
+    const long b = blockIdx.y;
+    const int px = blockIdx.x * RS_VC_THREADS + threadIdx.x;
+    if (px >= out * out) return;
+    const int yy = px / out, xx = px - yy * out;
+    const RsTab t = tab[b];
+    const long cid = (b * 2 + 1) * out + yy;
+    const int2 bd = bounds[cid];
+    const int* k = coef + cid * kmax;
+    const unsigned char* p = tmp + (t.row0 + bd.x) * out + xx;
+    int v;
+    if (t.pad == 3) {
+        const long plane = t.h * out;
+        int sr = 1 << (RS_PRECISION_BITS - 1), sg = sr, sb = sr;
+        for (int tp = 0; tp < bd.y; ++tp) {
+            const int kv = k[tp];
+            const unsigned char* q = p + (long)tp * out;
+            sr += (int)q[0] * kv;
+            sg += (int)q[plane] * kv;
+            sb += (int)q[2 * plane] * kv;
+        }
+        v = (19595 * (int)rs_clip8(sr) + 38470 * (int)rs_clip8(sg) + 7471 * (int)rs_clip8(sb) + 0x8000) >> 16;
+    } else {
+        int ss = 1 << (RS_PRECISION_BITS - 1);
+        for (int tp = 0; tp < bd.y; ++tp) ss += (int)p[(long)tp * out] * k[tp];
+        v = rs_clip8(ss);
+    }
+    dst[(b * out + yy) * out + (t.flip ? out - 1 - xx : xx)] = (unsigned char)v;
+}
+
 static void rs_lds_optin() {
     static bool optin = false;
-    if (!optin) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(resample_h_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); optin = true; }
+    if (!optin) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(resample_h_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(resample_h_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        optin = true;
+    }
 }
 
 // workspace: bounds int2 [B][2][out] | coef int32 [B][2][out][kmax] | err int32 (16 B) | intermediate uint8 [tmp_rows][out]
@@ -195,7 +244,7 @@ extern "C" int ecamp_resample_crops_u8(const uint8_t* src, const int64_t* table,
     const size_t shm = (size_t)kmax * out * sizeof(int);
     rs_lds_optin();
     const unsigned chunks = (unsigned)((max_h + RS_ROWS - 1) / RS_ROWS);
-    hipLaunchKernelGGL(resample_h_kernel, dim3(chunks, (unsigned)B), dim3(512), shm, stream, src, tab, bounds, coef, tmp, (int)out, (int)kmax);
+    hipLaunchKernelGGL(resample_h_kernel<false>, dim3(chunks, (unsigned)B), dim3(512), shm, stream, src, tab, bounds, coef, tmp, (int)out, (int)kmax);
     hipLaunchKernelGGL(resample_v_kernel, dim3((unsigned)out, (unsigned)B), dim3(512), 0, stream, tmp, tab, bounds, coef, dst, (int)out, (int)kmax);
     ECAMP_LAUNCH_CHECK();
     return 0;
@@ -237,8 +286,46 @@ extern "C" int ecamp_resample_boxes_u8(const uint8_t* src, const int64_t* table,
     const size_t shm = (size_t)kmax * out * sizeof(int);
     rs_lds_optin();
     const unsigned chunks = (unsigned)((max_h + RS_ROWS - 1) / RS_ROWS);
-    hipLaunchKernelGGL(resample_h_kernel, dim3(chunks, (unsigned)B), dim3(512), shm, stream, src, tab, bounds, coef, tmp, (int)out, (int)kmax);
+    hipLaunchKernelGGL(resample_h_kernel<false>, dim3(chunks, (unsigned)B), dim3(512), shm, stream, src, tab, bounds, coef, tmp, (int)out, (int)kmax);
     hipLaunchKernelGGL(resample_v_kernel, dim3((unsigned)out, (unsigned)B), dim3(512), 0, stream, tmp, tab, bounds, coef, dst, (int)out, (int)kmax);
+    ECAMP_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- the same transforms on COLOUR sources: three planes through the same taps, Grayscale behind the resample -----------------------
+// Pillow resamples an RGB image band by band with the coefficients and the uint8 intermediate of an L image, and Grayscale (convert("L"))
+// comes after the resize in data_utils.py:20-34 -- so the fold sits behind the vertical pass (resampling the gray plane instead differs
+// by 1 in about 30 % of the bytes).  Column 9 of a table row is the sample's plane count: 3 = planar R, G, B (3 x h x w bytes at `off`,
+// 3 h rows of the intermediate from row0), anything else one plane, the row of ecamp_resample_boxes_u8.  tmp_rows / max_h count c * h; workspace as above.
+extern "C" int ecamp_resample_boxes_rgb_u8(const uint8_t* src, const int64_t* table, uint8_t* dst, int64_t B, int32_t out, int32_t kmax, int64_t tmp_rows,
+                                           int32_t max_h, int32_t filter, void* ws, int64_t ws_bytes, int32_t* err_flag, hipStream_t stream) {
+    ECAMP_CHECK_ARG(src && table && dst && ws && err_flag, "resample_boxes_rgb_u8: null argument");
+    ECAMP_CHECK_ARG(filter == RS_BILINEAR || filter == RS_BICUBIC, "resample_boxes_rgb_u8: filter %d (0: bilinear, 1: bicubic)", filter);
+    ECAMP_CHECK_ARG(B > 0 && B <= 65535 && out > 0 && out <= 512 && kmax >= (filter == RS_BICUBIC ? 5 : 3) && (size_t)kmax * out * sizeof(int) <= 160 * 1024 && tmp_rows > 0 &&
+                        max_h > 0 && max_h <= tmp_rows,
+                    "resample_boxes_rgb_u8: B=%ld (<= 65535) out=%d (<= 512) kmax=%d (taps x out x 4 B must fit the 160 KB LDS) tmp_rows=%ld max_h=%d", (long)B, out, kmax,
+                    (long)tmp_rows, max_h);
+    ECAMP_CHECK_ARG(ws_bytes >= ecamp_resample_boxes_workspace_bytes(B, out, kmax, tmp_rows), "resample_boxes_rgb_u8: workspace of %ld bytes is too small", (long)ws_bytes);
+    unsigned char* w = reinterpret_cast<unsigned char*>(ws);
+    int2* bounds = reinterpret_cast<int2*>(w);
+    w += rs_align((size_t)B * 2 * out * sizeof(int2));
+    int* coef = reinterpret_cast<int*>(w);
+    w += rs_align((size_t)B * 2 * out * kmax * sizeof(int));
+    unsigned char* tmp = w + 256;
+    RsTab* tab = reinterpret_cast<RsTab*>(tmp + rs_align((size_t)tmp_rows * out));
+    const long n = B * 2 * out;
+    const dim3 cg((unsigned)((n + 255) / 256));
+    const long* t10 = reinterpret_cast<const long*>(table);
+    if (filter == RS_BILINEAR)
+        hipLaunchKernelGGL(resample_coef_kernel<RS_BILINEAR>, cg, dim3(256), 0, stream, t10, 10, tab, bounds, coef, (long)B, (int)out, (int)kmax, (int*)err_flag);
+    else
+        hipLaunchKernelGGL(resample_coef_kernel<RS_BICUBIC>, cg, dim3(256), 0, stream, t10, 10, tab, bounds, coef, (long)B, (int)out, (int)kmax, (int*)err_flag);
+    const size_t shm = (size_t)kmax * out * sizeof(int);
+    rs_lds_optin();
+    const unsigned chunks = (unsigned)((max_h + RS_ROWS - 1) / RS_ROWS);   // max_h: the largest c * h
+    hipLaunchKernelGGL(resample_h_kernel<true>, dim3(chunks, (unsigned)B), dim3(512), shm, stream, src, tab, bounds, coef, tmp, (int)out, (int)kmax);
+    const unsigned vblocks = (unsigned)(((long)out * out + RS_VC_THREADS - 1) / RS_VC_THREADS);
+    hipLaunchKernelGGL(resample_v_rgb_kernel, dim3(vblocks, (unsigned)B), dim3(RS_VC_THREADS), 0, stream, tmp, tab, bounds, coef, dst, (int)out, (int)kmax);
     ECAMP_LAUNCH_CHECK();
     return 0;
 }

@@ -911,3 +911,15 @@ def resample_boxes_u8(flat, table, out_t, out, kmax, tmp_rows, max_h, ws, err, f
     call("ecamp_resample_boxes_u8", ptr(flat), ptr(table), ptr(out_t), table.shape[0], int(out), int(kmax), int(tmp_rows), int(max_h), int(filter), ptr(ws),
          ws.numel(), ptr(err), stream())
     return out_t
+
+
+def resample_boxes_rgb_u8(flat, table, out_t, out, kmax, tmp_rows, max_h, ws, err, filter=BILINEAR):
+    """`resample_boxes_u8` for batches with colour samples: table column 9 is the plane count c (3: planar R, G, B, 3 x h x w bytes at off and
+    3 h intermediate rows from row0; else one plane), tmp_rows / max_h count c * h.  Three planes through the same taps, then Pillow's
+    convert("L") -- byte for byte Grayscale after the resize of the RGB image; a one-plane sample gets `resample_boxes_u8`'s byte."""
+    _chk(flat, table, out_t, ws, err)
+    assert flat.dtype == torch.uint8 and table.dtype == torch.int64 and table.is_contiguous() and table.shape[1] == 10
+    assert out_t.dtype == torch.uint8 and out_t.is_contiguous() and tuple(out_t.shape) == (table.shape[0], out, out)
+    call("ecamp_resample_boxes_rgb_u8", ptr(flat), ptr(table), ptr(out_t), table.shape[0], int(out), int(kmax), int(tmp_rows), int(max_h), int(filter), ptr(ws),
+         ws.numel(), ptr(err), stream())
+    return out_t

@@ -27,7 +27,8 @@ import torch
 TASKS = ["ChestX-ray14", "CheXpert", "RSNA", "SIIM", "COVIDx", "Aptos", "SpineXR", "ODIR5K", "MURED"]
 SINGLE_LABEL_TASKS = ("COVIDx", "Aptos")   # train.py:118-121: everything else is multilabel
 IMAGE_PIPELINE_LINE = ("NOTE: the image pipeline runs on the device (--image_shard_dir %s): crop, BILINEAR resample, flip and normalisation of the "
-                       "pre-decoded uint8 shards; the bytes of the host transforms for grayscale sources")
+                       "pre-decoded uint8 shards; the bytes of the host transforms -- a colour image of a colour shard (make_image_shard.py --colour) is "
+                       "resampled as three planes and folded to luma behind the resample, as Pillow's Grayscale after the resize")
 
 
 def get_args_parser():
@@ -83,7 +84,9 @@ def get_args_parser():
                    help="run the image pipeline on the device: DIR holds one uint8 shard per list file (<list file name>.u8 + .idx.npy, made by "
                         "tools/make_image_shard.py --list_dir ... --dataset_path ... --out_dir DIR); loader workers send the bytes of the crop box, "
                         "the device resamples them with Pillow's BILINEAR arithmetic and the model reads uint8 images.  The same bytes as the "
-                        "host transforms for grayscale sources; colour sources are refused when the shard is made")
+                        "host transforms.  Colour sources (Aptos, ODIR5K, MURED): make the shards with --colour; a colour shard is recognised from "
+                        "its index, its colour images travel as three planes and the device folds them to luma behind the resample, as "
+                        "Grayscale after the resize does (without --colour the tool ends at the first colour image)")
     return p
 
 

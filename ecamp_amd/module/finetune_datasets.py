@@ -157,18 +157,30 @@ class SyntheticClassificationDataset(Dataset):
 # decoded once, offline, into a uint8 shard (tools/make_image_shard.py --list_dir); a worker draws the box and the flip (training: the same
 # torch-RNG calls in the same order) or works out the Resize + CenterCrop geometry in integers (evaluation) and copies bytes; the device
 # resamples the batch with Pillow's own BILINEAR fixed-point arithmetic and hands the classifier uint8 [B, R, R], which its stem
-# normalises through the table of FT_MEAN / FT_STD.  Byte for byte the host item for GRAYSCALE sources (three equal channels: each is
-# resampled alike and Grayscale returns the common value); Grayscale after the resample of a colour image is not the resample of its gray
-# plane, so colour sources (Aptos, ODIR5K, MURED) are refused when the shard is made.
+# normalises through the table of FT_MEAN / FT_STD.  Byte for byte the host item: a GRAYSCALE source (three equal channels: each is
+# resampled alike and Grayscale returns the common value) is one plane; Grayscale after the resample of a colour image is not the resample
+# of its gray plane, so a COLOUR source (Aptos, ODIR5K, MURED; `make_image_shard.py --colour`) keeps its three planes [3, H, W] through the
+# shard and the box, the device resamples each with the same taps -- Pillow resamples an RGB image band by band -- and folds them with
+# Pillow's convert("L") behind the vertical pass (ecamp_resample_boxes_rgb_u8).  A batch without a colour sample takes the one-plane call.
+def _as_planes(image):
+    """uint8 [H, W] or [3, H, W] as it is; a PIL image -> its common channel [H, W] if the three are equal, else [3, H, W]."""
+    if isinstance(image, np.ndarray):
+        return image
+    a = np.asarray(image.convert("RGB"), dtype=np.uint8)
+    if np.array_equal(a[..., 0], a[..., 1]) and np.array_equal(a[..., 0], a[..., 2]):
+        return np.ascontiguousarray(a[..., 0])
+    return np.ascontiguousarray(a.transpose(2, 0, 1))
+
+
 def device_train_item(image, img_size):
-    """`train_transform`'s share of a loader worker: draw the crop box, then the flip (the same calls in the same order) -> (the BOX's
-    bytes, uint8 [h, w], a view of `image`; flip; (full_w, shift_w, full_h, shift_h) = (s, 0, s, 0): the box is resized to s x s)."""
-    if not isinstance(image, np.ndarray):
-        image = np.asarray(image.convert("L"), dtype=np.uint8)
-    H, W = image.shape
+    """`train_transform`'s share of a loader worker: draw the crop box, then the flip (the same calls in the same order, whatever the
+    number of planes) -> (the BOX's bytes, uint8 [h, w] or [3, h, w], a view of `image`; flip; (full_w, shift_w, full_h, shift_h) =
+    (s, 0, s, 0): the box is resized to s x s)."""
+    image = _as_planes(image)
+    H, W = image.shape[-2:]
     i, j, h, w = random_resized_crop_params(W, H, scale=(0.08, 1.0))
     flip = random_flip()
-    return image[i:i + h, j:j + w], flip, (int(img_size), 0, int(img_size), 0)   # a view: `pack_boxes` makes the one copy
+    return image[..., i:i + h, j:j + w], flip, (int(img_size), 0, int(img_size), 0)   # a view: `pack_boxes` makes the one copy
 
 
 def _round_half_even_of_half(d):
@@ -197,10 +209,9 @@ def eval_geometry(w, h, img_size, ratio=1.0):
 
 
 def device_eval_item(image, img_size, ratio=1.0):
-    """`eval_transform`'s share of a loader worker -> (the WHOLE image's bytes, uint8 [H, W]; flip = False; `eval_geometry`)."""
-    if not isinstance(image, np.ndarray):
-        image = np.asarray(image.convert("L"), dtype=np.uint8)
-    H, W = image.shape
+    """`eval_transform`'s share of a loader worker -> (the WHOLE image's bytes, uint8 [H, W] or [3, H, W]; flip = False; `eval_geometry`)."""
+    image = _as_planes(image)
+    H, W = image.shape[-2:]
     return np.ascontiguousarray(image), False, eval_geometry(W, H, img_size, ratio)
 
 
@@ -212,8 +223,10 @@ def bilinear_taps(in_size, full):
 def pack_boxes(items, pin=False):
     """Batch of `device_train_item` / `device_eval_item` results -> (flat uint8 tensor of all boxes back to back, int64 table [B, 10] for
     ecamp_resample_boxes_u8: byte offset, h, w, flip, first intermediate row, full_w, shift_w, full_h, shift_h, 0; meta = (tap count of the
-    batch's largest scale factor, sum of h, largest h) as Python ints, made here so that the step never reads the table back)."""
-    total = sum(c.shape[0] * c.shape[1] for c, _, _ in items)
+    batch's largest scale factor, sum of h, largest h) as Python ints, made here so that the step never reads the table back).
+    A colour box [3, h, w] is copied as three contiguous planes, has 3 in the last column and 3 h intermediate rows (the table of
+    ecamp_resample_boxes_rgb_u8; the sums and the maximum then count 3 h), and gives meta a fourth field, True: a colour sample is present."""
+    total = sum(c.size for c, _, _ in items)
     if torch.utils.data.get_worker_info() is not None:
         # in a loader worker: straight into shared memory, as torch's default_collate does -- the bytes are then copied once here (from
         # the shard's pages) and once more by the pinning thread, instead of a third time when the batch is handed to the main process
@@ -225,15 +238,22 @@ def pack_boxes(items, pin=False):
     fa, ta = flat.numpy(), table.numpy()
     off = row = max_h = 0
     kmax = 3
+    colour = False
     for n, (c, flip, (fw, sw, fh, sh)) in enumerate(items):
-        h, w = c.shape
-        fa[off:off + h * w].reshape(h, w)[...] = c
+        h, w = c.shape[-2:]
+        planes = 1
+        if c.ndim == 3:
+            if c.shape[0] != 3:
+                raise ValueError("pack_boxes: a box is uint8 [h, w] or [3, h, w], got %s" % (c.shape,))
+            planes, colour = 3, True
+            ta[n, 9] = 3
+        fa[off:off + c.size].reshape(c.shape)[...] = c
         ta[n, :9] = (off, h, w, int(flip), row, fw, sw, fh, sh)
         kmax = max(kmax, bilinear_taps(w, fw), bilinear_taps(h, fh))
-        off += h * w
-        row += h
-        max_h = max(max_h, h)
-    return flat, table, (kmax, row, max_h)
+        off += c.size
+        row += planes * h
+        max_h = max(max_h, planes * h)
+    return flat, table, ((kmax, row, max_h, True) if colour else (kmax, row, max_h))
 
 
 def collate_boxes(batch):
@@ -282,7 +302,8 @@ def check_shard(path, list_path):
 
 class DeviceBoxResampler:
     """boxes (flat uint8 + table [B, 10] + meta, host or device) -> uint8 [B, size, size] on the device: the classification transforms'
-    resample (+ flip), Pillow-exact (ecamp_resample_boxes_u8, BILINEAR).  The workspace grows to the largest batch seen and is reused."""
+    resample (+ flip), Pillow-exact (ecamp_resample_boxes_u8, BILINEAR; ecamp_resample_boxes_rgb_u8 -- three planes, then Grayscale -- when
+    meta's fourth field says the batch holds a colour sample).  The workspace grows to the largest batch seen and is reused."""
 
     def __init__(self, device, size):
         self.device, self.size = torch.device(device), int(size)
@@ -292,15 +313,16 @@ class DeviceBoxResampler:
     def __call__(self, flat, table, meta, check=False):
         from .. import hip_ops as ops
         B = table.shape[0]
-        kmax, rows, max_h = (int(v) for v in meta)
+        kmax, rows, max_h = (int(v) for v in meta[:3])
+        call = ops.resample_boxes_rgb_u8 if len(meta) > 3 and meta[3] else ops.resample_boxes_u8
         need = ops.resample_boxes_workspace_bytes(B, self.size, kmax, rows)
         if self.ws is None or self.ws.numel() < need:
             self.ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
         out = torch.empty((B, self.size, self.size), dtype=torch.uint8, device=self.device)
-        ops.resample_boxes_u8(flat.to(self.device, non_blocking=True), table.to(self.device, non_blocking=True), out, self.size, kmax, rows, max_h,
-                              self.ws, self.err, filter=ops.BILINEAR)
+        call(flat.to(self.device, non_blocking=True), table.to(self.device, non_blocking=True), out, self.size, kmax, rows, max_h, self.ws, self.err,
+             filter=ops.BILINEAR)
         if check and int(self.err.item()) != 0:
-            raise RuntimeError("ecamp_resample_boxes_u8: a box needed more taps than the table was sized for")
+            raise RuntimeError("ecamp_" + call.__name__ + ": a box needed more taps than the table was sized for")
         return out
 
 

@@ -232,15 +232,23 @@ class U8ShardWriter:
     `add` takes a PIL image or a uint8 [H, W] array; colour inputs go through PIL's convert('L') -- for MIMIC-CXR-JPG (grayscale JPEGs
     the reference opens as RGB, pretrain_datasets.py:28-31) that is the identity on the common channel.  `max_side`: optionally
     shrink the stored image so that its longer side is at most that many pixels (Pillow bicubic) -- a LOSSY choice of the user
-    (the reference crops from the full-size image); without it the crops are the reference's pixels."""
+    (the reference crops from the full-size image); without it the crops are the reference's pixels.
 
-    def __init__(self, path, max_side=None):
-        self.path, self.max_side = path, max_side
+    `colour=True` (the classification pipeline's colour sources, module/finetune_datasets.py; not with `max_side`): `add` takes an RGB PIL
+    image or a uint8 [H, W, 3] array and keeps the channels -- one plane [H, W] if they are equal, else three planes [3, H, W] (R, G, B);
+    the index is then [N, 4] = (byte offset, H, W, C)."""
+
+    def __init__(self, path, max_side=None, colour=False):
+        if colour and max_side:
+            raise ValueError("U8ShardWriter: max_side is not supported with colour=True")
+        self.path, self.max_side, self.colour = path, max_side, bool(colour)
         self.f = open(path, "wb")
         self.index = []
 
     def add(self, img):
         from PIL import Image
+        if self.colour:
+            return self._add_colour(img)
         if not isinstance(img, Image.Image):
             img = Image.fromarray(np.ascontiguousarray(img, dtype=np.uint8), "L")
         img = img.convert("L")
@@ -252,9 +260,22 @@ class U8ShardWriter:
         self.f.write(a.tobytes())
         return len(self.index) - 1
 
+    def _add_colour(self, img):
+        from PIL import Image
+        a = np.asarray(img.convert("RGB") if isinstance(img, Image.Image) else img, dtype=np.uint8)
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError("U8ShardWriter(colour=True).add takes an RGB image or a uint8 [H, W, 3] array, got shape %s" % (a.shape,))
+        if np.array_equal(a[..., 0], a[..., 1]) and np.array_equal(a[..., 0], a[..., 2]):
+            planes, c = a[..., 0], 1
+        else:
+            planes, c = a.transpose(2, 0, 1), 3
+        self.index.append((self.f.tell(), a.shape[0], a.shape[1], c))
+        self.f.write(np.ascontiguousarray(planes).tobytes())
+        return len(self.index) - 1
+
     def close(self):
         self.f.close()
-        np.save(self.path + ".idx.npy", np.asarray(self.index, dtype=np.int64).reshape(-1, 3))
+        np.save(self.path + ".idx.npy", np.asarray(self.index, dtype=np.int64).reshape(-1, 4 if self.colour else 3))
 
     def __enter__(self):
         return self
@@ -264,7 +285,8 @@ class U8ShardWriter:
 
 
 class U8ShardReader:
-    """Memory-mapped view of a `U8ShardWriter` file: `reader[i]` -> uint8 [H, W] (no copy, no decode)."""
+    """Memory-mapped view of a `U8ShardWriter` file: `reader[i]` -> uint8 [H, W] (no copy, no decode); from a colour shard (index
+    [N, 4]) [H, W] for a one-plane image and [3, H, W] for a three-plane one.  `planes(i)` -> C."""
 
     def __init__(self, path):
         self.index = np.load(path + ".idx.npy")
@@ -273,8 +295,13 @@ class U8ShardReader:
     def __len__(self):
         return len(self.index)
 
+    def planes(self, i):
+        return int(self.index[i][3]) if self.index.shape[1] > 3 else 1
+
     def __getitem__(self, i):
-        off, h, w = (int(v) for v in self.index[i])
+        off, h, w = (int(v) for v in self.index[i][:3])
+        if self.planes(i) == 3:
+            return self.data[off:off + 3 * h * w].reshape(3, h, w)
         return self.data[off:off + h * w].reshape(h, w)
 
 

@@ -30,7 +30,7 @@ typedef struct ihipStream_t* ecampStream_t; /* == hipStream_t */
  * returns the value the library was BUILT with; a consumer compares it with the header it was compiled against -- the Python binding
  * (ecamp_amd/_lib.py) refuses a library of another version, which is what protects an A/B of two builds (ECAMP_LIB, tools/ab_lib.sh)
  * from calling an older build with a newer argument list.  ecamp_ce_eval -- and later ecamp_drop_path_fwd / ecamp_drop_path_bwd, ecamp_pos_embed_grad,
- * ecamp_resample_boxes_u8 (+ its workspace function) and ecamp_im2col_u8 -- were
+ * ecamp_resample_boxes_u8 (+ its workspace function), ecamp_im2col_u8 and ecamp_resample_boxes_rgb_u8 -- were
  * ADDED at version 5 without touching an existing signature: a build that lacks them is refused by the binding all the same, which
  * resolves every declared symbol when it loads. */
 #define ECAMP_ABI_VERSION 5
@@ -261,6 +261,15 @@ int ecamp_resample_crops_u8(const uint8_t* src, const int64_t* table, uint8_t* d
 int64_t ecamp_resample_boxes_workspace_bytes(int64_t B, int32_t out, int32_t kmax, int64_t tmp_rows);
 int ecamp_resample_boxes_u8(const uint8_t* src, const int64_t* table, uint8_t* dst, int64_t B, int32_t out, int32_t kmax, int64_t tmp_rows,
                             int32_t max_h, int32_t filter, void* ws, int64_t ws_bytes, int32_t* err_flag, ecampStream_t stream);
+/* ecamp_resample_boxes_u8 for batches that may hold COLOUR sources (the same call sites, data_utils.py:20-34, on the colour-fundus tasks:
+ * Pillow resamples an RGB image band by band with an L image's coefficients and uint8 intermediate, and Grayscale -- convert("L"),
+ * L = (19595 R + 38470 G + 7471 B + 2^15) >> 16 -- follows the resize).  Same arguments; the last table column is the sample's plane
+ * count c: 3 = three planes R, G, B of h x w bytes back to back at the byte offset, which own 3 h rows of the intermediate from the
+ * sample's first row (plane p at + p h) and are folded to luma behind the vertical pass; any other value = one plane, the row's meaning
+ * in ecamp_resample_boxes_u8, and that function's byte.  tmp_rows = sum of c * h, max_h = largest c * h; ws from
+ * ecamp_resample_boxes_workspace_bytes; both filters; the same argument checks and err_flag. */
+int ecamp_resample_boxes_rgb_u8(const uint8_t* src, const int64_t* table, uint8_t* dst, int64_t B, int32_t out, int32_t kmax, int64_t tmp_rows,
+                                int32_t max_h, int32_t filter, void* ws, int64_t ws_bytes, int32_t* err_flag, ecampStream_t stream);
 /* ecamp_im2col_gather straight from a uint8 grayscale image [B, R, R] at the model's own size: out [B * (Lk + 1), 3 * p * p] (f32 or the
  * build's 16-bit format), the cls row zero, the three channel slabs the same values lut[byte] -- bit for bit ecamp_im2col_gather on
  * lut[img] expanded to three planes (lut as in ecamp_bicubic_resize_u8, built from the caller's mean / std). */

@@ -47,6 +47,13 @@
   15 images/s of the host loader (ListDataset + train_transform: PIL decode, crop, resample, f32 planes) and of the device loader
      (ShardListDataset + DeviceImageLoader) with the same worker count over the same generated PNG set (`--loader_images` files of
      1024 x 1024), each over one full pass after a first pass that starts the workers.
+
+`--image_pipeline --colour` runs the resample and loader comparison of that leg on COLOUR sources instead and writes
+profiles/finetune_image_pipeline_colour.txt (`--image_pipeline_colour_out`):
+
+  16 `ecamp_resample_boxes_rgb_u8` on B three-plane training crops of 1024 x 1024 sources with three different planes, beside
+     `ecamp_resample_boxes_u8` on the first planes of the same boxes (the boxes of leg 13: the same seed draws them), alternating in one loop.
+  17 leg 15 over colour PNG files and a colour shard (`U8ShardWriter(colour=True)`); `--loader_images 0` skips it.
 """
 import argparse
 import os
@@ -471,6 +478,115 @@ def image_pipeline_leg(args, say):
         shutil.rmtree(root, ignore_errors=True)
 
 
+def image_pipeline_colour_leg(args, say):
+    """Legs 16 and 17 (see the module docstring)."""
+    import shutil
+    import tempfile
+
+    import numpy as np
+    from torch.utils.data import DataLoader
+
+    from ecamp_amd.module import finetune_datasets as fd
+    from ecamp_amd.module.pretrain_datasets import U8ShardWriter
+    dev = torch.device("cuda")
+    C, R, S = args.classes, 224, 1024
+    batches = [int(b) for b in args.batches.split(",")]
+    say("colour sources in the classification image pipeline on the device, on %s: R = %d, sources 3 x %d x %d (three different planes), training crop "
+        "scales 0.08 to 1" % (torch.cuda.get_device_name(0), R, S, S))
+    rng = np.random.default_rng(0)
+    base = [np.clip(127 + 80 * np.sin(np.add.outer(np.arange(S) / (5.0 + k), np.arange(S) / (9.0 - k))) + rng.integers(-30, 31, (S, S)), 0, 255).astype(np.uint8)
+            for k in range(4)]
+    colour = [np.stack([base[k], base[(k + 1) % 4], base[(k + 2) % 4]]) for k in range(4)]
+    say("16 kernels alone, per call (coefficients + horizontal + vertical pass), from event pairs around 10 back-to-back calls, alternating in one loop "
+        "(%d groups after %d warm-up groups); the gray entry point runs on the FIRST PLANES of the same boxes" % (args.iters, args.warmup))
+    PARENT_US = {96: 175.0, 256: 399.0}      # profiles/finetune_image_pipeline.txt, leg 13: the gray entry point at the parent commit
+    for B in batches:
+        torch.manual_seed(B)                  # leg 13's seed: the same boxes
+        items = [fd.device_train_item(colour[b % 4], R) for b in range(B)]
+        cf, ct, cm = fd.pack_boxes(items)
+        gf, gt, gm = fd.pack_boxes([(box[0], flip, geom) for box, flip, geom in items])
+        assert len(cm) == 4 and cm[3] and len(gm) == 3 and cm[0] == gm[0] and cm[1] == 3 * gm[1]
+        cf, ct, gf, gt = cf.to(dev), ct.to(dev), gf.to(dev), gt.to(dev)
+        rs_c, rs_g = fd.DeviceBoxResampler(dev, R), fd.DeviceBoxResampler(dev, R)
+        got = rs_c(cf, ct, cm, check=True)
+        from PIL import Image
+        box, flip, _ = items[0]                # one sample against Pillow itself, before anything is timed
+        want = Image.fromarray(np.ascontiguousarray(box.transpose(1, 2, 0)), "RGB").resize((R, R), Image.BILINEAR)
+        want = np.asarray((want.transpose(Image.FLIP_LEFT_RIGHT) if flip else want).convert("L"))
+        assert np.array_equal(got[0].cpu().numpy(), want)
+        us = event_groups([("ecamp_resample_boxes_rgb_u8 (three planes)", lambda: rs_c(cf, ct, cm)),
+                           ("ecamp_resample_boxes_u8 (first planes)", lambda: rs_g(gf, gt, gm))], args.iters, args.warmup, 10)
+        say("   B = %3d: %.1f MB of colour box bytes (%.1f MB of first planes), %d taps, tallest colour sample %d intermediate rows" % (B, cf.numel() / 1e6, gf.numel() / 1e6, cm[0], cm[2]))
+        med = {}
+        for name, xs in us.items():
+            med[name], lo, hi = stats(xs)
+            say("      %-44s median %8.1f us (min %.1f, max %.1f)" % (name, med[name], lo, hi))
+        c, g = med["ecamp_resample_boxes_rgb_u8 (three planes)"], med["ecamp_resample_boxes_u8 (first planes)"]
+        say("      colour / gray = %.2f x (three times the source bytes and taps, one coefficient pass and one output byte: about 3 x is the expectation)" % (c / g))
+        if B in PARENT_US:
+            say("      the gray entry point at the parent commit (profiles/finetune_image_pipeline.txt): %.0f us; here %.1f us (this run's own spread: %.1f us)"
+                % (PARENT_US[B], g, max(us["ecamp_resample_boxes_u8 (first planes)"]) - min(us["ecamp_resample_boxes_u8 (first planes)"])))
+        del cf, ct, gf, gt, rs_c, rs_g
+    if args.loader_images <= 0:
+        return
+    from PIL import Image
+    root = tempfile.mkdtemp(prefix="ecamp_image_pipeline_colour_")
+    try:
+        N, W, rep = args.loader_images, args.loader_workers, args.loader_repeat
+
+        def source(k):
+            return np.roll(colour[k % 4], 37 * k, axis=2)
+
+        os.makedirs(os.path.join(root, "img"))
+        lines = []
+        for k in range(N):
+            Image.fromarray(np.ascontiguousarray(source(k).transpose(1, 2, 0)), "RGB").save(os.path.join(root, "img", "i%d.png" % k), compress_level=1)
+            lines.append("img/i%d.png %s" % (k, " ".join(str((k >> c) & 1) for c in range(C))))
+        open(os.path.join(root, "train_list.txt"), "w").write("\n".join(lines * rep) + "\n")
+        with U8ShardWriter(os.path.join(root, "train_list.txt.u8"), colour=True) as w:
+            for _ in range(rep):
+                for k in range(N):
+                    w.add(np.ascontiguousarray(source(k).transpose(1, 2, 0)))
+        say("17 loaders: one pass over a list of %d samples (%d colour PNG files of %d x %d, lossless, each listed %d times; the colour shard holds the same "
+            "pixels as three planes per image, %.1f GB, in list order), batch 96, %d workers each, pinned memory; the pass is timed after a first pass; host: "
+            "ListDataset + train_transform -> f32 [96, 3, %d, %d]; device: ShardListDataset + DeviceImageLoader -> uint8 [96, %d, %d] in HBM (three-plane boxes "
+            "over PCIe, the resample and the fold included; the timed pass ends in a device synchronise)"
+            % (N * rep, N, S, S, rep, os.path.getsize(os.path.join(root, "train_list.txt.u8")) / 1e9, W, R, R, R, R))
+        host = DataLoader(fd.ListDataset(root, root, "train", data_volume="100", transform=fd.train_transform(R)), shuffle=True, batch_size=96, num_workers=W,
+                          pin_memory=True, persistent_workers=W > 0)
+
+        def device_loader(workers):
+            return fd.DeviceImageLoader(DataLoader(fd.ShardListDataset(root, root, "train", data_volume="100", img_size=R), shuffle=True, batch_size=96,
+                                                   num_workers=workers, pin_memory=True, collate_fn=fd.collate_boxes, persistent_workers=workers > 0), dev, R)
+
+        rates, slowest = {}, {}
+        for name, loader in (("host loader", host), ("device loader", device_loader(W)), ("device loader, %d workers" % (2 * W), device_loader(2 * W))):
+            per = []
+            for _ in range(3):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                seen = 0
+                for x, _ in loader:
+                    x = x.to(dev, non_blocking=True)
+                    seen += x.shape[0]
+                torch.cuda.synchronize()
+                per.append(seen / (time.perf_counter() - t0))
+            rates[name], slowest[name] = statistics.median(per[1:]), min(per[1:])
+            say("   %-26s %8.0f images/s (passes after the first: %s)" % (name, rates[name], " ".join("%.0f" % v for v in per[1:])))
+            del loader
+        say("   device / host = %.1f x with the same %d workers" % (rates["device loader"] / rates["host loader"], W))
+        say("   the rates these must feed (profiles/finetune.txt): a fine-tune step at B = 96 runs 6 600 images/s, at B = 256 7 200 images/s.  A loader FEEDS a "
+            "step when its SLOWEST timed pass is at least the step's rate:")
+        for name in rates:
+            say("   %-26s slowest pass %6.0f images/s -> %s" % (name, slowest[name], "; ".join(
+                "fine-tune step at B = %d (%d): %s" % (B, r, "FEEDS it" if slowest[name] >= r else "does NOT feed it") for B, r in ((96, 6600), (256, 7200)))))
+        say("   NOT measured: real fundus photographs are larger than %d x %d (Aptos: up to 4288 x 2848).  A training box then carries up to an order of "
+            "magnitude more bytes per sample, three planes each, from the shard's pages through pinned memory and PCIe; host-to-device bytes per batch and "
+            "the worker-side copy grow with them, and the rates above do not speak for that." % (S, S))
+    finally:
+        shutil.rmtree(root, ignore_errors=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
@@ -487,10 +603,16 @@ def main():
     ap.add_argument("--fp16_out", type=str, default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "finetune_fp16.txt"))
     ap.add_argument("--image_pipeline", action="store_true", help="run the device-image-pipeline leg instead (profiles/finetune_image_pipeline.txt)")
     ap.add_argument("--image_pipeline_out", type=str, default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "finetune_image_pipeline.txt"))
+    ap.add_argument("--colour", action="store_true", help="--image_pipeline: the resample and loader comparison on colour sources instead "
+                                                          "(profiles/finetune_image_pipeline_colour.txt)")
+    ap.add_argument("--image_pipeline_colour_out", type=str,
+                    default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "finetune_image_pipeline_colour.txt"))
     ap.add_argument("--loader_images", type=int, default=384, help="--image_pipeline: PNG files of the loader comparison")
     ap.add_argument("--loader_repeat", type=int, default=8, help="--image_pipeline: times the list names each file")
     ap.add_argument("--loader_workers", type=int, default=8, help="--image_pipeline: workers of both loaders (the drivers' default)")
     args = ap.parse_args()
+    if args.colour and not args.image_pipeline:
+        ap.error("--colour goes with --image_pipeline")
     if not torch.cuda.is_available():
         raise SystemExit("finetune_bench needs an MI355X: nothing here can be measured on a CPU")
     if args.image_pipeline:
@@ -500,9 +622,10 @@ def main():
             print(msg, flush=True)
             lines.append(msg)
 
-        image_pipeline_leg(args, say_ip)
-        os.makedirs(os.path.dirname(os.path.abspath(args.image_pipeline_out)), exist_ok=True)
-        with open(args.image_pipeline_out, "w") as f:
+        out = args.image_pipeline_colour_out if args.colour else args.image_pipeline_out
+        (image_pipeline_colour_leg if args.colour else image_pipeline_leg)(args, say_ip)
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
             f.write("\n".join(lines) + "\n")
         return
     if args.fp16:
