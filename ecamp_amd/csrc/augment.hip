@@ -10,15 +10,18 @@
 // MIMIC-CXR-JPG radiographs are grayscale: the reference's RGB crop has three equal channels, each resampled by the same integer
 // arithmetic, and Grayscale's L = (19595 R + 38470 G + 7471 B + 2^15) >> 16 returns that common value -- so one uint8 plane is the
 // whole item before ToTensor / Normalize (the `image_u8` schema the model's kernels already read).
-// COLOUR sources (the fundus tasks of the classification transforms, at the end of this file): Pillow resamples an RGB image band by
-// band with these coefficients and this uint8 intermediate, and Grayscale follows the resize -- so a colour sample keeps three planes
-// through both passes and ecamp_resample_boxes_rgb_u8 folds them with the formula above behind the vertical pass: the host's byte again.
+// Colour sources (the fundus tasks of the classification transforms): Pillow resamples an RGB image band by band with these
+// coefficients and this uint8 intermediate, and Grayscale follows the resize -- so a colour sample keeps three planes through both
+// passes and the vertical pass folds them with the formula above: the host's byte again.
 //
-// Host -> device: per sample only the bytes of the drawn crop box (contiguous h x w uint8) and a table row; the host draws the boxes
-// and flips from the torch RNG in torchvision's order (ecamp_amd/module/pretrain_datasets.py: crop_params).
-//   table[b] = {byte offset of the crop in `src`, h, w, flip, first row of the sample in the intermediate, unused}
-// Three launches: coefficients (double precision, no contraction: the rounding of every operation is Pillow's), horizontal pass
-// (rows x 448 uint8 intermediate in the caller's workspace), vertical pass (+ flip) -> dst uint8 [B, out, out].
+// Host -> device: per sample only the bytes of the drawn box (contiguous uint8) and a table row; the host draws the boxes and flips
+// from the torch RNG in torchvision's order (ecamp_amd/module/pretrain_datasets.py, finetune_datasets.py).
+// ONE pipeline of three launches -- coefficients (double precision, no contraction: the rounding of every operation is Pillow's),
+// horizontal pass (rows x out uint8 intermediate in the caller's workspace), vertical pass (+ flip) -> dst uint8 [B, out, out] -- behind
+// one host launch path (rs_run) and one workspace layout (rs_carve), with THREE table forms, one entry point each:
+//   ecamp_resample_crops_u8      stride 6, BICUBIC: {byte offset of the box in `src`, h, w, flip, first row in the intermediate, unused}
+//   ecamp_resample_boxes_u8      stride 10, BILINEAR or BICUBIC: the same five + {full_w, shift_w, full_h, shift_h, 0}
+//   ecamp_resample_boxes_rgb_u8  the stride-10 row whose last column is the plane count (3: planar R, G, B), three-plane passes
 #include "common.h"
 
 #define RS_PRECISION_BITS 22
@@ -207,6 +210,7 @@ __global__ __launch_bounds__(RS_VC_THREADS) void resample_v_rgb_kernel(const uns
     dst[(b * out + yy) * out + (t.flip ? out - 1 - xx : xx)] = (unsigned char)v;
 }
 
+// ---- host side: one workspace layout and one launch path under the three entry points --------------------------------------------
 static void rs_lds_optin() {
     static bool optin = false;
     if (!optin) {
@@ -216,116 +220,82 @@ static void rs_lds_optin() {
     }
 }
 
-// workspace: bounds int2 [B][2][out] | coef int32 [B][2][out][kmax] | err int32 (16 B) | intermediate uint8 [tmp_rows][out]
+// workspace: bounds int2 [B][2][out] | coef int32 [B][2][out][kmax] | 256 spare bytes | intermediate uint8 [tmp_rows][out] | RsTab [B]
+// (the stride-10 forms only); every part starts on a multiple of 256 bytes, `bytes` is the end of the last one
+struct RsWorkspace { int2* bounds; int* coef; unsigned char* tmp; RsTab* tab; size_t bytes; };
+
 static size_t rs_align(size_t v) { return (v + 255) & ~(size_t)255; }
-extern "C" int64_t ecamp_resample_crops_workspace_bytes(int64_t B, int32_t out, int32_t kmax, int64_t tmp_rows) {
-    if (B <= 0 || out <= 0 || kmax <= 0 || tmp_rows <= 0) return 0;
-    return (int64_t)(rs_align((size_t)B * 2 * out * sizeof(int2)) + rs_align((size_t)B * 2 * out * kmax * sizeof(int)) + 256 + rs_align((size_t)tmp_rows * out));
+static RsWorkspace rs_carve(void* ws, int64_t B, int out, int kmax, int64_t tmp_rows, bool with_tab) {
+    const uintptr_t w = reinterpret_cast<uintptr_t>(ws);   // integers: the size functions carve a null workspace
+    const size_t coef = rs_align((size_t)B * 2 * out * sizeof(int2)), tmp = coef + rs_align((size_t)B * 2 * out * kmax * sizeof(int)) + 256;
+    const size_t tab = tmp + rs_align((size_t)tmp_rows * out), end = with_tab ? tab + rs_align((size_t)B * sizeof(RsTab)) : tab;
+    return {reinterpret_cast<int2*>(w), reinterpret_cast<int*>(w + coef), reinterpret_cast<unsigned char*>(w + tmp),
+            with_tab ? reinterpret_cast<RsTab*>(w + tab) : nullptr, end};
 }
 
+extern "C" int64_t ecamp_resample_crops_workspace_bytes(int64_t B, int32_t out, int32_t kmax, int64_t tmp_rows) {
+    return B <= 0 || out <= 0 || kmax <= 0 || tmp_rows <= 0 ? 0 : (int64_t)rs_carve(nullptr, B, out, kmax, tmp_rows, false).bytes;
+}
+
+extern "C" int64_t ecamp_resample_boxes_workspace_bytes(int64_t B, int32_t out, int32_t kmax, int64_t tmp_rows) {
+    return B <= 0 || out <= 0 || kmax <= 0 || tmp_rows <= 0 ? 0 : (int64_t)rs_carve(nullptr, B, out, kmax, tmp_rows, true).bytes;
+}
+
+// an entry point: its name (for messages), the stride of its table rows (6: the passes read the caller's table, no RsTab tail; 10: the
+// coefficient kernel copies the RsTab share into the workspace tail), filter, smallest tap table, and whether the passes are the three-plane ones
+struct RsPlan { const char* name; int stride, filter, min_kmax; bool colour; };
+
+static int rs_run(const RsPlan& p, const uint8_t* src, const int64_t* table, uint8_t* dst, int64_t B, int32_t out, int32_t kmax, int64_t tmp_rows, int32_t max_h,
+                  void* ws, int64_t ws_bytes, int32_t* err_flag, hipStream_t stream) {
+    ECAMP_CHECK_ARG(src && table && dst && ws && err_flag, "%s: null argument", p.name);
+    ECAMP_CHECK_ARG(p.filter == RS_BILINEAR || p.filter == RS_BICUBIC, "%s: filter %d (0: bilinear, 1: bicubic)", p.name, p.filter);
+    const bool sizes_ok = B > 0 && B <= 65535 && out > 0 && out <= 512 && tmp_rows > 0 && max_h > 0 && max_h <= tmp_rows;   // B: gridDim.y of both passes
+    ECAMP_CHECK_ARG(sizes_ok && kmax >= p.min_kmax && (size_t)kmax * out * sizeof(int) <= 160 * 1024,
+                    "%s: B=%ld (<= 65535) out=%d (<= 512) kmax=%d (taps x out x 4 B must fit the 160 KB LDS) tmp_rows=%ld max_h=%d", p.name, (long)B, out, kmax, (long)tmp_rows, max_h);
+    const bool with_tab = p.stride == 10;
+    const RsWorkspace k = rs_carve(ws, B, out, kmax, tmp_rows, with_tab);
+    ECAMP_CHECK_ARG(ws_bytes >= (int64_t)k.bytes, "%s: workspace of %ld bytes is too small", p.name, (long)ws_bytes);
+    const RsTab* tab = with_tab ? k.tab : reinterpret_cast<const RsTab*>(table);
+    const long n = B * 2 * out;
+    const auto coef_kernel = p.filter == RS_BILINEAR ? resample_coef_kernel<RS_BILINEAR> : resample_coef_kernel<RS_BICUBIC>;
+    hipLaunchKernelGGL(coef_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, reinterpret_cast<const long*>(table), p.stride, k.tab, k.bounds, k.coef, (long)B,
+                       (int)out, (int)kmax, (int*)err_flag);
+    // rows per sample are data (the table lives on the device): the grid covers the tallest sample of the batch (max_h, the host knows it)
+    const size_t shm = (size_t)kmax * out * sizeof(int);
+    rs_lds_optin();
+    const dim3 hgrid((unsigned)((max_h + RS_ROWS - 1) / RS_ROWS), (unsigned)B);
+    if (p.colour) {
+        hipLaunchKernelGGL(resample_h_kernel<true>, hgrid, dim3(512), shm, stream, src, tab, k.bounds, k.coef, k.tmp, (int)out, (int)kmax);
+        const unsigned vblocks = (unsigned)(((long)out * out + RS_VC_THREADS - 1) / RS_VC_THREADS);
+        hipLaunchKernelGGL(resample_v_rgb_kernel, dim3(vblocks, (unsigned)B), dim3(RS_VC_THREADS), 0, stream, k.tmp, tab, k.bounds, k.coef, dst, (int)out, (int)kmax);
+    } else {
+        hipLaunchKernelGGL(resample_h_kernel<false>, hgrid, dim3(512), shm, stream, src, tab, k.bounds, k.coef, k.tmp, (int)out, (int)kmax);
+        hipLaunchKernelGGL(resample_v_kernel, dim3((unsigned)out, (unsigned)B), dim3(512), 0, stream, k.tmp, tab, k.bounds, k.coef, dst, (int)out, (int)kmax);
+    }
+    const hipError_t e = hipGetLastError();   // ECAMP_LAUNCH_CHECK with the entry point's name in place of __func__
+    if (e != hipSuccess) return ecamp_set_error((int)e, "ecamp_%s: launch failed: %s", p.name, hipGetErrorString(e));
+    return 0;
+}
+
+// the pre-training crops: stride-6 rows, BICUBIC, every axis resized from its size to `out`.  B <= 65535 (gridDim.y of the passes) is an
+// argument error here as in the two entry points below: unchecked, a larger batch surfaces as a launch failure.
 extern "C" int ecamp_resample_crops_u8(const uint8_t* src, const int64_t* table, uint8_t* dst, int64_t B, int32_t out, int32_t kmax, int64_t tmp_rows,
                                        int32_t max_h, void* ws, int64_t ws_bytes, int32_t* err_flag, hipStream_t stream) {
-    ECAMP_CHECK_ARG(src && table && dst && ws && err_flag, "resample_crops_u8: null argument");
-    ECAMP_CHECK_ARG(B > 0 && out > 0 && out <= 512 && kmax >= 5 && (size_t)kmax * out * sizeof(int) <= 160 * 1024 && tmp_rows > 0 && max_h > 0 && max_h <= tmp_rows,
-                    "resample_crops_u8: B=%ld out=%d (<= 512) kmax=%d (taps x out x 4 B must fit the 160 KB LDS) tmp_rows=%ld max_h=%d", (long)B, out, kmax, (long)tmp_rows, max_h);
-    ECAMP_CHECK_ARG(ws_bytes >= ecamp_resample_crops_workspace_bytes(B, out, kmax, tmp_rows), "resample_crops_u8: workspace of %ld bytes is too small", (long)ws_bytes);
-    unsigned char* w = reinterpret_cast<unsigned char*>(ws);
-    int2* bounds = reinterpret_cast<int2*>(w);
-    w += rs_align((size_t)B * 2 * out * sizeof(int2));
-    int* coef = reinterpret_cast<int*>(w);
-    w += rs_align((size_t)B * 2 * out * kmax * sizeof(int));
-    (void)w;   // (the 256 bytes behind the tables are spare)
-    unsigned char* tmp = w + 256;
-    const RsTab* tab = reinterpret_cast<const RsTab*>(table);
-    const long n = B * 2 * out;
-    hipLaunchKernelGGL(resample_coef_kernel<RS_BICUBIC>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, reinterpret_cast<const long*>(table), 6, (RsTab*)nullptr, bounds,
-                       coef, (long)B, (int)out, (int)kmax, (int*)err_flag);
-    // rows per sample are data (the table lives on the device): the grid covers the tallest crop of the batch (max_h, the host knows it)
-    const size_t shm = (size_t)kmax * out * sizeof(int);
-    rs_lds_optin();
-    const unsigned chunks = (unsigned)((max_h + RS_ROWS - 1) / RS_ROWS);
-    hipLaunchKernelGGL(resample_h_kernel<false>, dim3(chunks, (unsigned)B), dim3(512), shm, stream, src, tab, bounds, coef, tmp, (int)out, (int)kmax);
-    hipLaunchKernelGGL(resample_v_kernel, dim3((unsigned)out, (unsigned)B), dim3(512), 0, stream, tmp, tab, bounds, coef, dst, (int)out, (int)kmax);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    return rs_run({"resample_crops_u8", 6, RS_BICUBIC, 5, false}, src, table, dst, B, out, kmax, tmp_rows, max_h, ws, ws_bytes, err_flag, stream);
 }
 
-// ---- the classification transforms (data_utils.py:20-34): RandomResizedCrop((s, s)) / flip, and Resize(int) + CenterCrop((s, s)) ----
-// One resample per axis with two more numbers: `full`, the size the axis is resized to, and `shift`, where the s output pixels start in
-// that resized axis (negative, or past `full`: CenterCrop's zero padding).  Training is full = out, shift = 0 on the crop box.  Same
-// coefficient kernel (template over the filter), same two passes; the passes read the RsTab rows the coefficient kernel copies out.
-// workspace: as above | RsTab [B]
-extern "C" int64_t ecamp_resample_boxes_workspace_bytes(int64_t B, int32_t out, int32_t kmax, int64_t tmp_rows) {
-    const int64_t base = ecamp_resample_crops_workspace_bytes(B, out, kmax, tmp_rows);
-    return base == 0 ? 0 : base + (int64_t)rs_align((size_t)B * sizeof(RsTab));
-}
-
+// the classification transforms (data_utils.py:20-34): RandomResizedCrop((s, s)) / flip, and Resize(int) + CenterCrop((s, s)).  One
+// resample per axis with two more numbers: `full`, the size the axis is resized to, and `shift`, where the s output pixels start in
+// that resized axis (negative, or past `full`: CenterCrop's zero padding).  Training is full = out, shift = 0 on the crop box.
 extern "C" int ecamp_resample_boxes_u8(const uint8_t* src, const int64_t* table, uint8_t* dst, int64_t B, int32_t out, int32_t kmax, int64_t tmp_rows,
                                        int32_t max_h, int32_t filter, void* ws, int64_t ws_bytes, int32_t* err_flag, hipStream_t stream) {
-    ECAMP_CHECK_ARG(src && table && dst && ws && err_flag, "resample_boxes_u8: null argument");
-    ECAMP_CHECK_ARG(filter == RS_BILINEAR || filter == RS_BICUBIC, "resample_boxes_u8: filter %d (0: bilinear, 1: bicubic)", filter);
-    ECAMP_CHECK_ARG(B > 0 && B <= 65535 && out > 0 && out <= 512 && kmax >= (filter == RS_BICUBIC ? 5 : 3) && (size_t)kmax * out * sizeof(int) <= 160 * 1024 && tmp_rows > 0 &&
-                        max_h > 0 && max_h <= tmp_rows,
-                    "resample_boxes_u8: B=%ld (<= 65535) out=%d (<= 512) kmax=%d (taps x out x 4 B must fit the 160 KB LDS) tmp_rows=%ld max_h=%d", (long)B, out, kmax,
-                    (long)tmp_rows, max_h);
-    ECAMP_CHECK_ARG(ws_bytes >= ecamp_resample_boxes_workspace_bytes(B, out, kmax, tmp_rows), "resample_boxes_u8: workspace of %ld bytes is too small", (long)ws_bytes);
-    unsigned char* w = reinterpret_cast<unsigned char*>(ws);
-    int2* bounds = reinterpret_cast<int2*>(w);
-    w += rs_align((size_t)B * 2 * out * sizeof(int2));
-    int* coef = reinterpret_cast<int*>(w);
-    w += rs_align((size_t)B * 2 * out * kmax * sizeof(int));
-    unsigned char* tmp = w + 256;
-    RsTab* tab = reinterpret_cast<RsTab*>(tmp + rs_align((size_t)tmp_rows * out));
-    const long n = B * 2 * out;
-    const dim3 cg((unsigned)((n + 255) / 256));
-    const long* t10 = reinterpret_cast<const long*>(table);
-    if (filter == RS_BILINEAR)
-        hipLaunchKernelGGL(resample_coef_kernel<RS_BILINEAR>, cg, dim3(256), 0, stream, t10, 10, tab, bounds, coef, (long)B, (int)out, (int)kmax, (int*)err_flag);
-    else
-        hipLaunchKernelGGL(resample_coef_kernel<RS_BICUBIC>, cg, dim3(256), 0, stream, t10, 10, tab, bounds, coef, (long)B, (int)out, (int)kmax, (int*)err_flag);
-    const size_t shm = (size_t)kmax * out * sizeof(int);
-    rs_lds_optin();
-    const unsigned chunks = (unsigned)((max_h + RS_ROWS - 1) / RS_ROWS);
-    hipLaunchKernelGGL(resample_h_kernel<false>, dim3(chunks, (unsigned)B), dim3(512), shm, stream, src, tab, bounds, coef, tmp, (int)out, (int)kmax);
-    hipLaunchKernelGGL(resample_v_kernel, dim3((unsigned)out, (unsigned)B), dim3(512), 0, stream, tmp, tab, bounds, coef, dst, (int)out, (int)kmax);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    return rs_run({"resample_boxes_u8", 10, filter, filter == RS_BICUBIC ? 5 : 3, false}, src, table, dst, B, out, kmax, tmp_rows, max_h, ws, ws_bytes, err_flag, stream);
 }
 
-// ---- the same transforms on COLOUR sources: three planes through the same taps, Grayscale behind the resample -----------------------
-// Pillow resamples an RGB image band by band with the coefficients and the uint8 intermediate of an L image, and Grayscale (convert("L"))
-// comes after the resize in data_utils.py:20-34 -- so the fold sits behind the vertical pass (resampling the gray plane instead differs
-// by 1 in about 30 % of the bytes).  Column 9 of a table row is the sample's plane count: 3 = planar R, G, B (3 x h x w bytes at `off`,
-// 3 h rows of the intermediate from row0), anything else one plane, the row of ecamp_resample_boxes_u8.  tmp_rows / max_h count c * h; workspace as above.
+// the same transforms on COLOUR sources: Grayscale (convert("L")) comes after the resize in data_utils.py:20-34, so the fold sits behind the
+// vertical pass (resampling the gray plane instead differs by 1 in about 30 % of the bytes).  Column 9 of a table row is the plane count c: 3 = planar
+// R, G, B (3 x h x w bytes at `off`, 3 h intermediate rows from row0), anything else the row of ecamp_resample_boxes_u8; tmp_rows / max_h count c * h.
 extern "C" int ecamp_resample_boxes_rgb_u8(const uint8_t* src, const int64_t* table, uint8_t* dst, int64_t B, int32_t out, int32_t kmax, int64_t tmp_rows,
                                            int32_t max_h, int32_t filter, void* ws, int64_t ws_bytes, int32_t* err_flag, hipStream_t stream) {
-    ECAMP_CHECK_ARG(src && table && dst && ws && err_flag, "resample_boxes_rgb_u8: null argument");
-    ECAMP_CHECK_ARG(filter == RS_BILINEAR || filter == RS_BICUBIC, "resample_boxes_rgb_u8: filter %d (0: bilinear, 1: bicubic)", filter);
-    ECAMP_CHECK_ARG(B > 0 && B <= 65535 && out > 0 && out <= 512 && kmax >= (filter == RS_BICUBIC ? 5 : 3) && (size_t)kmax * out * sizeof(int) <= 160 * 1024 && tmp_rows > 0 &&
-                        max_h > 0 && max_h <= tmp_rows,
-                    "resample_boxes_rgb_u8: B=%ld (<= 65535) out=%d (<= 512) kmax=%d (taps x out x 4 B must fit the 160 KB LDS) tmp_rows=%ld max_h=%d", (long)B, out, kmax,
-                    (long)tmp_rows, max_h);
-    ECAMP_CHECK_ARG(ws_bytes >= ecamp_resample_boxes_workspace_bytes(B, out, kmax, tmp_rows), "resample_boxes_rgb_u8: workspace of %ld bytes is too small", (long)ws_bytes);
-    unsigned char* w = reinterpret_cast<unsigned char*>(ws);
-    int2* bounds = reinterpret_cast<int2*>(w);
-    w += rs_align((size_t)B * 2 * out * sizeof(int2));
-    int* coef = reinterpret_cast<int*>(w);
-    w += rs_align((size_t)B * 2 * out * kmax * sizeof(int));
-    unsigned char* tmp = w + 256;
-    RsTab* tab = reinterpret_cast<RsTab*>(tmp + rs_align((size_t)tmp_rows * out));
-    const long n = B * 2 * out;
-    const dim3 cg((unsigned)((n + 255) / 256));
-    const long* t10 = reinterpret_cast<const long*>(table);
-    if (filter == RS_BILINEAR)
-        hipLaunchKernelGGL(resample_coef_kernel<RS_BILINEAR>, cg, dim3(256), 0, stream, t10, 10, tab, bounds, coef, (long)B, (int)out, (int)kmax, (int*)err_flag);
-    else
-        hipLaunchKernelGGL(resample_coef_kernel<RS_BICUBIC>, cg, dim3(256), 0, stream, t10, 10, tab, bounds, coef, (long)B, (int)out, (int)kmax, (int*)err_flag);
-    const size_t shm = (size_t)kmax * out * sizeof(int);
-    rs_lds_optin();
-    const unsigned chunks = (unsigned)((max_h + RS_ROWS - 1) / RS_ROWS);   // max_h: the largest c * h
-    hipLaunchKernelGGL(resample_h_kernel<true>, dim3(chunks, (unsigned)B), dim3(512), shm, stream, src, tab, bounds, coef, tmp, (int)out, (int)kmax);
-    const unsigned vblocks = (unsigned)(((long)out * out + RS_VC_THREADS - 1) / RS_VC_THREADS);
-    hipLaunchKernelGGL(resample_v_rgb_kernel, dim3(vblocks, (unsigned)B), dim3(RS_VC_THREADS), 0, stream, tmp, tab, bounds, coef, dst, (int)out, (int)kmax);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    return rs_run({"resample_boxes_rgb_u8", 10, filter, filter == RS_BICUBIC ? 5 : 3, true}, src, table, dst, B, out, kmax, tmp_rows, max_h, ws, ws_bytes, err_flag, stream);
 }

@@ -884,42 +884,38 @@ def resample_crops_workspace_bytes(B, out, kmax, tmp_rows):
     return int(_lib.load().ecamp_resample_crops_workspace_bytes(int(B), int(out), int(kmax), int(tmp_rows)))
 
 
-def resample_crops_u8(flat, table, out_t, out, kmax, tmp_rows, max_h, ws, err):
-    """B crops (flat uint8 + int64 table [B, 6], both on the device) -> out_t uint8 [B, out, out]: Pillow's crop().resize(BICUBIC) + flip,
-    byte for byte (csrc/augment.hip; pretrain_datasets.py:47-52)."""
-    _chk(flat, table, out_t, ws, err)
-    assert flat.dtype == torch.uint8 and table.dtype == torch.int64 and table.is_contiguous() and out_t.dtype == torch.uint8 and out_t.is_contiguous()
-    call("ecamp_resample_crops_u8", ptr(flat), ptr(table), ptr(out_t), table.shape[0], int(out), int(kmax), int(tmp_rows), int(max_h), ptr(ws), ws.numel(),
-         ptr(err), stream())
-    return out_t
+def resample_boxes_workspace_bytes(B, out, kmax, tmp_rows):
+    return int(_lib.load().ecamp_resample_boxes_workspace_bytes(int(B), int(out), int(kmax), int(tmp_rows)))
 
 
 BILINEAR, BICUBIC = 0, 1   # the `filter` argument of ecamp_resample_boxes_u8
 
 
-def resample_boxes_workspace_bytes(B, out, kmax, tmp_rows):
-    return int(_lib.load().ecamp_resample_boxes_workspace_bytes(int(B), int(out), int(kmax), int(tmp_rows)))
+def _resample(name, width, flat, table, out_t, out, kmax, tmp_rows, max_h, ws, err, *filter):
+    """The one body of the three resample entry points: `width` is the table's, `filter` is given where the entry point takes one."""
+    _chk(flat, table, out_t, ws, err)
+    assert flat.dtype == torch.uint8 and table.dtype == torch.int64 and table.is_contiguous() and table.shape[1] == width
+    assert out_t.dtype == torch.uint8 and out_t.is_contiguous() and tuple(out_t.shape) == (table.shape[0], out, out)
+    call(name, ptr(flat), ptr(table), ptr(out_t), table.shape[0], int(out), int(kmax), int(tmp_rows), int(max_h), *map(int, filter), ptr(ws), ws.numel(), ptr(err),
+         stream())
+    return out_t
+
+
+def resample_crops_u8(flat, table, out_t, out, kmax, tmp_rows, max_h, ws, err):
+    """B crops (flat uint8 + int64 table [B, 6], both on the device) -> out_t uint8 [B, out, out]: Pillow's crop().resize(BICUBIC) + flip,
+    byte for byte (csrc/augment.hip; pretrain_datasets.py:47-52)."""
+    return _resample("ecamp_resample_crops_u8", 6, flat, table, out_t, out, kmax, tmp_rows, max_h, ws, err)
 
 
 def resample_boxes_u8(flat, table, out_t, out, kmax, tmp_rows, max_h, ws, err, filter=BILINEAR):
     """B boxes (flat uint8 + int64 table [B, 10]: off, h, w, flip, row0, full_w, shift_w, full_h, shift_h, 0; both on the device) -> out_t
     uint8 [B, out, out]: Pillow's resize of every axis to `full` (BILINEAR or BICUBIC), the `out` pixels from `shift` on, zero outside, +
     flip -- byte for byte the classification transforms (csrc/augment.hip; module/finetune_datasets.py)."""
-    _chk(flat, table, out_t, ws, err)
-    assert flat.dtype == torch.uint8 and table.dtype == torch.int64 and table.is_contiguous() and table.shape[1] == 10
-    assert out_t.dtype == torch.uint8 and out_t.is_contiguous() and tuple(out_t.shape) == (table.shape[0], out, out)
-    call("ecamp_resample_boxes_u8", ptr(flat), ptr(table), ptr(out_t), table.shape[0], int(out), int(kmax), int(tmp_rows), int(max_h), int(filter), ptr(ws),
-         ws.numel(), ptr(err), stream())
-    return out_t
+    return _resample("ecamp_resample_boxes_u8", 10, flat, table, out_t, out, kmax, tmp_rows, max_h, ws, err, filter)
 
 
 def resample_boxes_rgb_u8(flat, table, out_t, out, kmax, tmp_rows, max_h, ws, err, filter=BILINEAR):
     """`resample_boxes_u8` for batches with colour samples: table column 9 is the plane count c (3: planar R, G, B, 3 x h x w bytes at off and
     3 h intermediate rows from row0; else one plane), tmp_rows / max_h count c * h.  Three planes through the same taps, then Pillow's
     convert("L") -- byte for byte Grayscale after the resize of the RGB image; a one-plane sample gets `resample_boxes_u8`'s byte."""
-    _chk(flat, table, out_t, ws, err)
-    assert flat.dtype == torch.uint8 and table.dtype == torch.int64 and table.is_contiguous() and table.shape[1] == 10
-    assert out_t.dtype == torch.uint8 and out_t.is_contiguous() and tuple(out_t.shape) == (table.shape[0], out, out)
-    call("ecamp_resample_boxes_rgb_u8", ptr(flat), ptr(table), ptr(out_t), table.shape[0], int(out), int(kmax), int(tmp_rows), int(max_h), int(filter), ptr(ws),
-         ws.numel(), ptr(err), stream())
-    return out_t
+    return _resample("ecamp_resample_boxes_rgb_u8", 10, flat, table, out_t, out, kmax, tmp_rows, max_h, ws, err, filter)

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 from torch.utils.data import Dataset
 
-from .pretrain_datasets import pil_loader, random_flip, random_resized_crop_params
+from .pretrain_datasets import DeviceResampler, pil_loader, random_flip, random_resized_crop_params
 
 # utils/data_utils.py:25,33.  NOT the pre-training constants (0.4721 / 0.3037, pretrain_datasets.py:51): the reference has both.
 FT_MEAN, FT_STD = 0.4722, 0.3028
@@ -300,30 +300,16 @@ def check_shard(path, list_path):
         raise ValueError("image shard %s holds %d images, %s lists %d: the shard was made from another list" % (path, n, list_path, want))
 
 
-class DeviceBoxResampler:
+class DeviceBoxResampler(DeviceResampler):
     """boxes (flat uint8 + table [B, 10] + meta, host or device) -> uint8 [B, size, size] on the device: the classification transforms'
     resample (+ flip), Pillow-exact (ecamp_resample_boxes_u8, BILINEAR; ecamp_resample_boxes_rgb_u8 -- three planes, then Grayscale -- when
-    meta's fourth field says the batch holds a colour sample).  The workspace grows to the largest batch seen and is reused."""
-
-    def __init__(self, device, size):
-        self.device, self.size = torch.device(device), int(size)
-        self.ws = None
-        self.err = torch.zeros((1,), dtype=torch.int32, device=self.device)
+    meta's fourth field says the batch holds a colour sample)."""
 
     def __call__(self, flat, table, meta, check=False):
         from .. import hip_ops as ops
-        B = table.shape[0]
         kmax, rows, max_h = (int(v) for v in meta[:3])
-        call = ops.resample_boxes_rgb_u8 if len(meta) > 3 and meta[3] else ops.resample_boxes_u8
-        need = ops.resample_boxes_workspace_bytes(B, self.size, kmax, rows)
-        if self.ws is None or self.ws.numel() < need:
-            self.ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
-        out = torch.empty((B, self.size, self.size), dtype=torch.uint8, device=self.device)
-        call(flat.to(self.device, non_blocking=True), table.to(self.device, non_blocking=True), out, self.size, kmax, rows, max_h, self.ws, self.err,
-             filter=ops.BILINEAR)
-        if check and int(self.err.item()) != 0:
-            raise RuntimeError("ecamp_" + call.__name__ + ": a box needed more taps than the table was sized for")
-        return out
+        op = ops.resample_boxes_rgb_u8 if len(meta) > 3 and meta[3] else ops.resample_boxes_u8   # filter: their default, BILINEAR
+        return self.run(op, ops.resample_boxes_workspace_bytes, "box", flat, table, kmax, rows, max_h, check)
 
 
 class DeviceImageLoader:

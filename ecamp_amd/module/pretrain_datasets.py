@@ -341,14 +341,34 @@ def pack_crops(items, pin=False):
     return flat, table
 
 
-class DeviceAugmenter:
-    """crops (flat uint8 + table, host or device) -> uint8 [B, size, size] on the device: RandomResizedCrop's resize + flip + Grayscale,
-    Pillow-exact (csrc/augment.hip).  The workspace grows to the largest batch seen and is reused (kernels never allocate)."""
+class DeviceResampler:
+    """The host side of one resample call (csrc/augment.hip): flat uint8 + table, host or device -> uint8 [B, size, size] on the device.
+    The workspace grows to the largest batch seen and is reused (kernels never allocate).  A subclass's `__call__` states how the op and
+    (kmax, rows, max_h) come from its meta and hands them to `run`."""
 
-    def __init__(self, device, size=448):
-        self.device, self.size = torch.device(device), size
+    def __init__(self, device, size):
+        self.device, self.size = torch.device(device), int(size)
         self.ws = None
         self.err = torch.zeros((1,), dtype=torch.int32, device=self.device)
+
+    def run(self, op, workspace_bytes, what, flat, table, kmax, rows, max_h, check):
+        B = table.shape[0]
+        need = workspace_bytes(B, self.size, kmax, rows)
+        if self.ws is None or self.ws.numel() < need:
+            self.ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        out = torch.empty((B, self.size, self.size), dtype=torch.uint8, device=self.device)
+        op(flat.to(self.device, non_blocking=True), table.to(self.device, non_blocking=True), out, self.size, kmax, rows, max_h, self.ws, self.err)
+        if check and int(self.err.item()) != 0:
+            raise RuntimeError("ecamp_%s: a %s needed more taps than the table was sized for" % (op.__name__, what))
+        return out
+
+
+class DeviceAugmenter(DeviceResampler):
+    """crops (flat uint8 + table, host or device) -> uint8 [B, size, size] on the device: RandomResizedCrop's resize + flip + Grayscale,
+    Pillow-exact (ecamp_resample_crops_u8)."""
+
+    def __init__(self, device, size=448):
+        super().__init__(device, size)
 
     @staticmethod
     def taps(max_side, size):
@@ -362,18 +382,8 @@ class DeviceAugmenter:
         from .. import hip_ops as ops
         if meta is None:
             meta = crops_meta(table if table.device.type == "cpu" else table.cpu())
-        B = table.shape[0]
         max_side, rows, max_h = (int(v) for v in meta)
-        kmax = self.taps(max_side, self.size)
-        need = ops.resample_crops_workspace_bytes(B, self.size, kmax, rows)
-        if self.ws is None or self.ws.numel() < need:
-            self.ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
-        out = torch.empty((B, self.size, self.size), dtype=torch.uint8, device=self.device)
-        ops.resample_crops_u8(flat.to(self.device, non_blocking=True), table.to(self.device, non_blocking=True), out, self.size, kmax, rows, max_h,
-                              self.ws, self.err)
-        if check and int(self.err.item()) != 0:
-            raise RuntimeError("ecamp_resample_crops_u8: a crop needed more taps than the table was sized for")
-        return out
+        return self.run(ops.resample_crops_u8, ops.resample_crops_workspace_bytes, "crop", flat, table, self.taps(max_side, self.size), rows, max_h, check)
 
 
 class ContextBertDataset(Dataset):

@@ -247,7 +247,8 @@ int ecamp_assemble_tokens_x32(const void* x, float* out, const float* cls, const
  * src: the crops' bytes back to back (each h x w, contiguous); table int64 [B, 6] on the device = {byte offset in src, h, w, flip (0/1),
  * first row of the sample in the intermediate (prefix sum of h), 0}; kmax >= the tap count of the batch's largest scale factor
  * (2 * ceil(2 * max(1, size / out)) + 1); tmp_rows = sum of h; max_h = largest h; ws from ecamp_resample_crops_workspace_bytes;
- * err_flag: int32 on the device, set to 1 if a sample needs more than kmax taps (the result is then undefined). */
+ * err_flag: int32 on the device, set to 1 if a sample needs more than kmax taps (the result is then undefined).  B <= 65535, out <= 512.
+ * The three resample entry points share one launch path and one workspace layout; the boxes forms add a table copy at its end. */
 int64_t ecamp_resample_crops_workspace_bytes(int64_t B, int32_t out, int32_t kmax, int64_t tmp_rows);
 int ecamp_resample_crops_u8(const uint8_t* src, const int64_t* table, uint8_t* dst, int64_t B, int32_t out, int32_t kmax, int64_t tmp_rows,
                             int32_t max_h, void* ws, int64_t ws_bytes, int32_t* err_flag, ecampStream_t stream);

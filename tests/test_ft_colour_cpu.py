@@ -315,3 +315,115 @@ def test_colour_entry_point_refuses_bad_arguments_without_a_device(libs):
         assert rc < 0 and b"filter 2" in lib.ecamp_last_error()
         rc = lib.ecamp_resample_boxes_rgb_u8(one, one, one, 2, 16, 5, 64, 32, 0, one, 16, one, None)
         assert rc < 0 and b"too small" in lib.ecamp_last_error()
+
+
+# ------------------------------------------------------------------------------- the one launch path of the three resample entry points
+# name -> (the filters it takes, None: no filter argument; its workspace size function)
+ENTRY_POINTS = {"ecamp_resample_crops_u8": ((None,), "ecamp_resample_crops_workspace_bytes"),
+                "ecamp_resample_boxes_u8": ((0, 1), "ecamp_resample_boxes_workspace_bytes"),
+                "ecamp_resample_boxes_rgb_u8": ((0, 1), "ecamp_resample_boxes_workspace_bytes")}
+ONE = ctypes.c_void_p(16)   # never dereferenced: the argument checks fail first
+
+
+def _refused(lib, name, filt, match, src=ONE, table=ONE, dst=ONE, B=2, out=16, kmax=5, rows=64, max_h=32, ws=ONE, ws_bytes=1 << 40, err=ONE):
+    """One call that the argument checks must refuse, with the entry point's own name in front of a message that holds `match`."""
+    rc = getattr(lib, name)(src, table, dst, B, out, kmax, rows, max_h, *(() if filt is None else (filt,)), ws, ws_bytes, err, None)
+    msg = lib.ecamp_last_error()
+    assert rc < 0 and msg.startswith(name[len("ecamp_"):].encode() + b": ") and match in msg, (name, filt, rc, msg)
+
+
+@pytest.mark.parametrize("build", [0, 1], ids=["bf16", "f16"])
+@pytest.mark.parametrize("name", list(ENTRY_POINTS))
+def test_every_resample_entry_point_refuses_bad_arguments_under_its_own_name(libs, name, build):
+    lib = libs[build]
+    filters, size_fn = ENTRY_POINTS[name]
+    for filt in filters:
+        for null in ("src", "table", "dst", "ws", "err"):
+            _refused(lib, name, filt, b"null argument", **{null: None})
+        _refused(lib, name, filt, b"out=513 (<= 512)", out=513)
+        low = 4 if filt in (None, 1) else 2                               # one below Pillow's tap count at scale 1: 5 bicubic, 3 bilinear
+        _refused(lib, name, filt, b"kmax=%d " % low, kmax=low)
+        _refused(lib, name, filt, b"LDS", out=512, kmax=81)               # 81 * 512 * 4 = 165888 > 160 KB
+        _refused(lib, name, filt, b"max_h=65", rows=64, max_h=65)
+        _refused(lib, name, filt, b"too small", ws_bytes=getattr(lib, size_fn)(2, 16, 5, 64) - 1)
+        _refused(lib, name, filt, b"B=65536 (<= 65535)", B=65536)         # gridDim.y of the passes: crops included
+    if filters != (None,):
+        _refused(lib, name, 2, b"filter 2")
+
+
+def _align256(v):
+    return (v + 255) // 256 * 256
+
+
+def test_workspace_sizes_are_the_layout_restated(libs):
+    """bounds int2 [B][2][out] | coef int32 [B][2][out][kmax] | 256 spare | intermediate [rows][out], + RsTab [B] (48 B) for the boxes."""
+    grid = [(B, out, kmax, rows) for B in (1, 3, 16) for out in (7, 16) for kmax in (5, 32) for rows in (16, 40)]
+    terms = [(B * 2 * out * 8, B * 2 * out * kmax * 4, rows * out, B * 48) for B, out, kmax, rows in grid]
+    for n in range(4):                                                    # every term both is and is not a multiple of 256 somewhere
+        assert {t[n] % 256 == 0 for t in terms} == {True, False}, n
+    for lib in libs:
+        assert lib.ecamp_resample_crops_workspace_bytes(3, 16, 5, 40) == 3840 and lib.ecamp_resample_boxes_workspace_bytes(3, 16, 5, 40) == 4096
+        for args, (bounds, coef, tmp, tab) in zip(grid, terms):
+            crops = _align256(bounds) + _align256(coef) + 256 + _align256(tmp)
+            assert lib.ecamp_resample_crops_workspace_bytes(*args) == crops, args
+            assert lib.ecamp_resample_boxes_workspace_bytes(*args) == crops + _align256(tab), args
+        for n in range(4):
+            for bad in (0, -1):
+                args = [3, 16, 5, 40]
+                args[n] = bad
+                assert lib.ecamp_resample_crops_workspace_bytes(*args) == 0 and lib.ecamp_resample_boxes_workspace_bytes(*args) == 0, args
+
+
+def test_the_two_resampler_objects_share_one_base_and_choose_only_the_op_and_the_taps(monkeypatch):
+    """hip_ops recorded instead of called, tensors on the host: which op each object calls with which tap count, and the grow-only workspace."""
+    from ecamp_amd import hip_ops as ops
+    from ecamp_amd.module import finetune_datasets as fd
+    from ecamp_amd.module import pretrain_datasets as pd
+    calls, need = [], {"bytes": 1000}
+    for name in ("resample_crops_u8", "resample_boxes_u8", "resample_boxes_rgb_u8"):
+        def op(flat, table, out_t, out, kmax, tmp_rows, max_h, ws, err, name=name, **kw):
+            calls.append((name, tuple(out_t.shape), out, kmax, tmp_rows, max_h, ws, err, kw))
+        op.__name__ = name
+        monkeypatch.setattr(ops, name, op)
+    for name in ("resample_crops_workspace_bytes", "resample_boxes_workspace_bytes"):
+        monkeypatch.setattr(ops, name, lambda B, out, kmax, rows, name=name: calls.append((name, B, out, kmax, rows)) or need["bytes"])
+    assert issubclass(pd.DeviceAugmenter, pd.DeviceResampler) and issubclass(fd.DeviceBoxResampler, pd.DeviceResampler)
+    assert "__call__" not in vars(pd.DeviceResampler) and pd.DeviceAugmenter.run is fd.DeviceBoxResampler.run
+
+    crops = [(R.gray_image(h, w, seed=h), False) for h, w in ((70, 20), (9, 33), (16, 16))]
+    cflat, t6 = pd.pack_crops(crops)
+    aug = pd.DeviceAugmenter("cpu", 16)
+    for meta in (pd.crops_meta(t6), None):                                # None: the augmenter alone reads the table itself
+        del calls[:]
+        got = aug(cflat, t6, meta)
+        kmax = pd.DeviceAugmenter.taps(70, 16)
+        assert kmax == 19 and got.shape == (3, 16, 16) and got.dtype == torch.uint8
+        assert calls[0] == ("resample_crops_workspace_bytes", 3, 16, kmax, 95)
+        assert calls[1][:6] == ("resample_crops_u8", (3, 16, 16), 16, kmax, 95, 70) and calls[1][6] is aug.ws and calls[1][7] is aug.err and calls[1][8] == {}
+    assert pd.DeviceAugmenter("cpu").size == 448
+
+    gray = [(R.gray_image(20, 30, seed=1), True, (16, 0, 16, 0)), (R.gray_image(40, 12, seed=2), False, (16, 0, 16, 0))]
+    colour = gray + [(np.stack([R.gray_image(8, 8, seed=s) for s in (3, 4, 5)]), False, (16, 0, 16, 0))]
+    box = fd.DeviceBoxResampler("cpu", 16)
+    for items, meta4, want in ((gray, None, "resample_boxes_u8"), (colour, None, "resample_boxes_rgb_u8"), (gray, False, "resample_boxes_u8"),
+                               (gray, True, "resample_boxes_rgb_u8")):
+        flat, t10, meta = fd.pack_boxes(items)
+        meta = meta if meta4 is None else tuple(meta[:3]) + (meta4,)
+        del calls[:]
+        got = box(flat, t10, meta)
+        assert calls[0] == ("resample_boxes_workspace_bytes", len(items), 16, meta[0], meta[1])
+        assert calls[1][:6] == (want, (len(items), 16, 16), 16, meta[0], meta[1], meta[2]) and calls[1][6] is box.ws and calls[1][7] is box.err
+        assert calls[1][8] in ({}, {"filter": ops.BILINEAR}) and got.shape == (len(items), 16, 16)
+
+    flat, t10, meta = fd.pack_boxes(gray)
+    for obj, args in ((aug, (cflat, t6, pd.crops_meta(t6))), (box, (flat, t10, meta))):
+        need["bytes"] = 1000
+        obj(*args)
+        first = obj.ws
+        assert first.numel() == 1000 and first.dtype == torch.uint8
+        need["bytes"] = 800
+        obj(*args)
+        assert obj.ws is first                                            # large enough: reused
+        need["bytes"] = 2000
+        obj(*args)
+        assert obj.ws is not first and obj.ws.numel() == 2000             # too small: reallocated
