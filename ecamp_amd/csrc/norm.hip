@@ -414,6 +414,16 @@ static LnLayout ln_select(bool backward, bool rows16, int cols, bool al16, int o
     return {4, chunks4, 16, true, slices, 256};
 }
 
+// ln_select's answer for a call, as out = {vec, chunks, waves, greg, lds, grid_cap}: host arithmetic, nothing is launched.  For tests
+// (tests/_ln_ref.py mirrors ln_select and every case names the form it is meant to reach) and for tools that want to say which form ran.
+extern "C" int ecamp_layernorm_layout(int32_t backward, int32_t rows16, int32_t cols, int32_t al16, int32_t opt_bwd, int32_t* out) {
+    ECAMP_CHECK_ARG(out, "layernorm_layout: null pointer");
+    ECAMP_CHECK_ARG(cols > 0 && cols % 4 == 0 && cols <= 2048, "layernorm_layout: cols=%d must be a multiple of 4 and <= 2048", cols);
+    const LnLayout l = ln_select(backward != 0, rows16 != 0, cols, al16 != 0, opt_bwd);
+    out[0] = l.vec; out[1] = l.chunks; out[2] = l.waves; out[3] = l.greg ? 1 : 0; out[4] = (int32_t)l.lds; out[5] = l.grid_cap;
+    return 0;
+}
+
 // The launchers name every instantiation: f32 rows have the 4-wide forms only.  (vec, chunks) identifies one: waves and greg are
 // template parameters of the backward kernel, and each (vec, chunks) exists with one pair of them.
 template <typename T> constexpr bool ln_rows16 = sizeof(typename LnRow<T>::io) == 2;

@@ -308,6 +308,15 @@ def layernorm_bwd_z32(dy, z, mean, rstd, gamma, ggamma, gbeta, dres=None):
     return dz
 
 
+def layernorm_layout(backward, rows16, cols, al16=True, opt_bwd=0):
+    """-> (vec, chunks, waves, greg, lds, grid_cap): the layout the library selects for such a call (ecamp_layernorm_layout; host
+    arithmetic, nothing is launched).  rows16: 16-bit rows, the f32-stream entries included; al16: every row pointer 16-byte aligned."""
+    out = (ctypes.c_int32 * 6)()
+    call("ecamp_layernorm_layout", int(bool(backward)), int(bool(rows16)), int(cols), int(bool(al16)), int(opt_bwd),
+         ctypes.cast(out, ctypes.c_void_p))
+    return (out[0], out[1], out[2], bool(out[3]), out[4], out[5])
+
+
 # --------------------------------------------------------------------------------------------- attention
 def _st(t3):
     return _I64x3(*t3)

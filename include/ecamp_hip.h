@@ -30,7 +30,7 @@ typedef struct ihipStream_t* ecampStream_t; /* == hipStream_t */
  * returns the value the library was BUILT with; a consumer compares it with the header it was compiled against -- the Python binding
  * (ecamp_amd/_lib.py) refuses a library of another version, which is what protects an A/B of two builds (ECAMP_LIB, tools/ab_lib.sh)
  * from calling an older build with a newer argument list.  ecamp_ce_eval -- and later ecamp_drop_path_fwd / ecamp_drop_path_bwd, ecamp_pos_embed_grad,
- * ecamp_resample_boxes_u8 (+ its workspace function), ecamp_im2col_u8 and ecamp_resample_boxes_rgb_u8 -- were
+ * ecamp_resample_boxes_u8 (+ its workspace function), ecamp_im2col_u8, ecamp_resample_boxes_rgb_u8 and ecamp_layernorm_layout -- were
  * ADDED at version 5 without touching an existing signature: a build that lacks them is refused by the binding all the same, which
  * resolves every declared symbol when it loads. */
 #define ECAMP_ABI_VERSION 5
@@ -175,6 +175,11 @@ int ecamp_layernorm_fwd_x32(const float* x, const float* gamma, const float* bet
                             int32_t cols, float eps, int32_t dtype, ecampStream_t stream);
 int ecamp_layernorm_bwd_z32(const void* dy, const float* z, const float* mean, const float* rstd, const float* gamma, const void* dres_in,
                             void* dz, float* dgamma, float* dbeta, int64_t rows, int32_t cols, int32_t dtype, ecampStream_t stream);
+/* Which layout a LayerNorm call gets (no reference counterpart; host arithmetic, nothing is launched): out = int32[6] {elements per lane
+ * access, accesses per lane and row, waves per workgroup, gamma in registers (1) or in LDS (0), dynamic LDS bytes, most workgroups
+ * launched (0: no cap)} for (backward?, 16-bit rows? -- the f32-stream entries count as 16-bit --, cols, every row pointer on a 16-byte
+ * boundary?, the value of ECAMP_LN_BWD).  Added at version 5 without touching an existing signature. */
+int ecamp_layernorm_layout(int32_t backward, int32_t rows16, int32_t cols, int32_t al16, int32_t opt_bwd, int32_t* out);
 
 /* ---- attention (timm Attention.forward: softmax(q k^T * hd^-1/2) v; HF BertSelfAttention 4.42.4 incl. the
  * cross-attention mode of context_fusion.py:45-53).  strides = {batch, token, head} in elements, head_dim contiguous.

@@ -196,6 +196,32 @@ def emb_fwd_grid_y(B):
     return min(16, (B + 3) // 4)
 
 
+def ln_rows(z, de, gamma, beta, eps, sc, dt, magnitudes=False):
+    """The LayerNorm row arithmetic of the docstring above on z [R, H] in `dt` (shared with tests/_ln_ref.py, where sc == 1):
+    -> dict(mean, rstd [R]; e, dgamma, dbeta, dz [R, H], the parameter gradients per row).  sc: the keep-mask scale on e and de.
+    magnitudes: the same on absolute values (rs from the values themselves)."""
+    z, de, g, b = z.to(dt), de.to(dt), gamma.to(dt), beta.to(dt)
+    H = z.shape[1]
+    mu = z.sum(1, keepdim=True) / H
+    d = z - mu
+    var = (d * d).sum(1, keepdim=True) / H
+    rs = 1.0 / torch.sqrt(var + eps)
+    if not magnitudes:
+        xh = d * rs
+        dd = de * sc
+        gg = dd * g
+        dz = rs * (gg - gg.sum(1, keepdim=True) / H - xh * ((gg * xh).sum(1, keepdim=True) / H))
+        return dict(mean=mu[:, 0], rstd=rs[:, 0], e=(xh * g + b) * sc, dgamma=dd * xh, dbeta=dd, dz=dz)
+    muA = z.abs().sum(1, keepdim=True) / H
+    dA = z.abs() + muA
+    xhA = dA * rs
+    ddA = de.abs() * sc
+    ggA = ddA * g.abs()
+    dzA = rs * (ggA + ggA.sum(1, keepdim=True) / H + xhA * ((ggA * xhA).sum(1, keepdim=True) / H))
+    rsA = rs * (1.0 + (d.abs() * dA).sum(1, keepdim=True) / H / (var + eps))
+    return dict(mean=muA[:, 0], rstd=rsA[:, 0], e=(xhA * g.abs() + b.abs()) * sc, dgamma=ddA * xhA, dbeta=ddA, dz=dzA)
+
+
 class EmbCase:
     """One embedding case on the host.  variant: plain -- hot ids (2, 3), PAD 0; hot03 -- hot ids (0, 3), PAD 0 (the guard hot0 != pad);
     nohot -- hot ids (2, 3) that no token carries; type0 -- every token of type 0."""
@@ -270,26 +296,7 @@ class EmbCase:
     def rows(self, z, keep, dt, magnitudes=False):
         """The per-row arithmetic on the stored z in `dt` -> dict(mean, rstd, e, dgamma, dbeta, dz), the last three per row [R, H].
         magnitudes: the same on absolute values (rs from the values themselves)."""
-        z, de, g, b = z.to(dt), self.de.to(dt), self.gamma.to(dt), self.beta.to(dt)
-        H, sc = self.H, self._scale(keep, dt)
-        mu = z.sum(1, keepdim=True) / H
-        d = z - mu
-        var = (d * d).sum(1, keepdim=True) / H
-        rs = 1.0 / torch.sqrt(var + EMB_EPS)
-        if not magnitudes:
-            xh = d * rs
-            dd = de * sc
-            gg = dd * g
-            dz = rs * (gg - gg.sum(1, keepdim=True) / H - xh * ((gg * xh).sum(1, keepdim=True) / H))
-            return dict(mean=mu[:, 0], rstd=rs[:, 0], e=(xh * g + b) * sc, dgamma=dd * xh, dbeta=dd, dz=dz)
-        muA = z.abs().sum(1, keepdim=True) / H
-        dA = z.abs() + muA
-        xhA = dA * rs
-        ddA = de.abs() * sc
-        ggA = ddA * g.abs()
-        dzA = rs * (ggA + ggA.sum(1, keepdim=True) / H + xhA * ((ggA * xhA).sum(1, keepdim=True) / H))
-        rsA = rs * (1.0 + (d.abs() * dA).sum(1, keepdim=True) / H / (var + EMB_EPS))
-        return dict(mean=muA[:, 0], rstd=rsA[:, 0], e=(xhA * g.abs() + b.abs()) * sc, dgamma=ddA * xhA, dbeta=ddA, dz=dzA)
+        return ln_rows(z, self.de, self.gamma, self.beta, EMB_EPS, self._scale(keep, dt), dt, magnitudes)
 
     def _gather(self, rows, dt, magnitudes=False, chained=()):
         """prior + the sum of every row's share, per buffer.  chained: the buffers whose rows are added one after the other in `dt`, in

@@ -141,6 +141,8 @@ def test_gemm_rejects_bad_alignment(dev):
 @pytest.mark.parametrize("rows,cols,eps", [(100, 768, 1e-6), (394, 512, 1e-6), (7, 192, 1e-6), (256, 768, 1e-12), (33, 1024, 1e-6),
                                            (40, 2048, 1e-6)])   # 2048 = the documented maximum (64 KB of reduction slices in the backward)
 def test_layernorm(dev, dtype, rows, cols, eps):
+    """Forward and backward against F.layer_norm per tensor; the per-element float64 bounds on the same quantities (and on rstd) live in
+    test_ln_float64_gpu.py."""
     o = ops()
     x = rnd(gen(rows, cols, seed=1) * 2 + 0.3, dtype)
     res = rnd(gen(rows, cols, seed=2), dtype)

@@ -17,7 +17,9 @@ are never misaligned: the f32 kernels make 16-byte accesses and the library does
 
 Tolerances are those of the tests that hold the same quantities at round sizes: test_kernels_gpu.py (test_layernorm,
 test_layernorm_dropout_residual_matches_pytorch_under_the_same_mask, test_fp8_delayed_scaling_kernels) for the plain entries and
-test_f32_residual_gpu.py for the f32-stream entries."""
+test_f32_residual_gpu.py for the f32-stream entries.  The per-element float64 bounds on every quantity of these entries (rstd and
+nonzero prior contents of dgamma / dbeta included) live in test_ln_float64_gpu.py, which also checks the table above against
+ecamp_layernorm_layout for every case it runs."""
 import functools
 
 import pytest
@@ -135,11 +137,14 @@ def test_layernorm_dropout_layouts(dev, dtype, rows, cols):
     check("ln dropout dbeta", gb, br.grad, ptol)
 
 
-@pytest.mark.parametrize("rows", ROWS)
-@pytest.mark.parametrize("cols", DROP_COLS)
+Q8_SHAPES = [(c, r) for r in ROWS for c in DROP_COLS] + [(768, 5), (2048, 5)]   # + the production width and the documented maximum
+
+
+@pytest.mark.parametrize("cols,rows", Q8_SHAPES)
 def test_layernorm_q8_layouts(dev, rows, cols):
     """ecamp_layernorm_fwd_q8 (bf16): y is the plain entry's, the e4m3 copy is bit-identical to quantising that y afterwards and the
-    site's amax slots hold max|y| -- with and without the fused residual + dropout."""
+    site's amax slots hold max|y| -- with and without the fused residual + dropout.  (The plain entry itself is held to float64 per
+    element in test_ln_float64_gpu.py.)"""
     o = ops()
     assert h16() == torch.bfloat16
     xx, rr = _randn(dev, 3, rows, cols).to(h16()), _randn(dev, 4, rows, cols).to(h16())
