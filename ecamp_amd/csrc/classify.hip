@@ -11,30 +11,11 @@
 // workspace; a second, small kernel adds the partials in chunk order, divides, and normalises the row (one workgroup per sample).
 // Stage 1 layout: a 256-thread workgroup covers `cw` 16-byte column vectors x `rows_par` token lanes (768 columns of bf16 = 96 vectors
 // x 2 lanes); a thread walks its token lane four 16-byte loads at a time, the lanes are added through LDS in lane order.
-template <typename T, int VEC> struct PoolVec;
-template <> struct PoolVec<float, 4> {
-    typedef float4 raw_t;
-    static __device__ __forceinline__ void add(const float4& v, float (&a)[4]) { a[0] += v.x; a[1] += v.y; a[2] += v.z; a[3] += v.w; }
-};
-template <> struct PoolVec<bf16_t, 4> {
-    typedef uint2 raw_t;
-    static __device__ __forceinline__ void add(const uint2& v, float (&a)[4]) {
-        a[0] += h16_lo(v.x); a[1] += h16_hi(v.x); a[2] += h16_lo(v.y); a[3] += h16_hi(v.y);
-    }
-};
-template <> struct PoolVec<bf16_t, 8> {
-    typedef uint4 raw_t;
-    static __device__ __forceinline__ void add(const uint4& v, float (&a)[8]) {
-        a[0] += h16_lo(v.x); a[1] += h16_hi(v.x); a[2] += h16_lo(v.y); a[3] += h16_hi(v.y);
-        a[4] += h16_lo(v.z); a[5] += h16_hi(v.z); a[6] += h16_lo(v.w); a[7] += h16_hi(v.w);
-    }
-};
-
 template <typename T, int VEC>
 __global__ __launch_bounds__(POOL_THREADS) void pool_partial_kernel(const T* __restrict__ x, float* __restrict__ part, int64_t B, int Tn, int D,
                                                                     int t0, int t1, int nv, int cw, int rows_par, int nslab, int nchunk,
                                                                     int chunk_len) {
-    typedef PoolVec<T, VEC> V;
+    typedef Vec<T, VEC> V;
     typedef typename V::raw_t raw_t;
     __shared__ __attribute__((aligned(16))) float sh[POOL_THREADS * VEC];
     const int r = threadIdx.x / cw, c = threadIdx.x % cw;

@@ -33,10 +33,15 @@ int ecamp_set_error(int code, const char* fmt, ...);
         if (!(cond)) return ecamp_set_error(-1, __VA_ARGS__); \
     } while (0)
 
-#define ECAMP_LAUNCH_CHECK()                                                        \
-    do {                                                                            \
-        hipError_t e_ = hipGetLastError();                                          \
-        if (e_ != hipSuccess) return ecamp_set_error((int)e_, "%s: launch failed: %s", __func__, hipGetErrorString(e_)); \
+// what an entry returns after its (last) launch: 0, or the launch error under the entry's name
+static inline int ecamp_launch_status(const char* func) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : ecamp_set_error((int)e, "%s: launch failed: %s", func, hipGetErrorString(e));
+}
+#define ECAMP_LAUNCH_CHECK()                         \
+    do {                                             \
+        const int s_ = ecamp_launch_status(__func__); \
+        if (s_) return s_;                           \
     } while (0)
 
 // ---------------------------------------------------------------------------------------------
@@ -86,27 +91,67 @@ template <> __device__ __forceinline__ bf16_t from_f<bf16_t>(float v) { return f
 // value after a round trip through storage type T (used so fwd statistics match what bwd re-reads)
 template <typename T> __device__ __forceinline__ float rnd(float v) { return to_f<T>(from_f<T>(v)); }
 
-// 4-element vector load/store (16 B for f32, 8 B for bf16); pointers must be suitably aligned
-template <typename T> __device__ __forceinline__ void ld4(const T* p, float (&o)[4]);
-template <> __device__ __forceinline__ void ld4<float>(const float* p, float (&o)[4]) {
-    float4 v = *reinterpret_cast<const float4*>(p);
-    o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-}
-template <> __device__ __forceinline__ void ld4<bf16_t>(const bf16_t* p, float (&o)[4]) {
-    uint2 v = *reinterpret_cast<const uint2*>(p);
-    o[0] = h16_lo(v.x); o[1] = h16_hi(v.x);
-    o[2] = h16_lo(v.y); o[3] = h16_hi(v.y);
-}
-template <typename T> __device__ __forceinline__ void st4(T* p, const float (&o)[4]);
-template <> __device__ __forceinline__ void st4<float>(float* p, const float (&o)[4]) {
-    *reinterpret_cast<float4*>(p) = make_float4(o[0], o[1], o[2], o[3]);
-}
-template <> __device__ __forceinline__ void st4<bf16_t>(bf16_t* p, const float (&o)[4]) {
-    uint2 v;
-    v.x = pack_bf16x2(o[0], o[1]);
-    v.y = pack_bf16x2(o[2], o[3]);
-    *reinterpret_cast<uint2*>(p) = v;
-}
+// VEC consecutive elements of T, as they lie in memory (raw_t: one 8- or 16-byte access; two 16-byte ones for eight floats) and as floats.
+// Pointers must be aligned to the access.  VecFmt is the part that depends on the format: raw_t, cvt (raw -> floats), pack (floats -> raw,
+// one round-to-nearest-even per 16-bit element).
+template <typename T, int VEC> struct VecFmt;
+template <> struct VecFmt<float, 4> {
+    typedef float4 raw_t;
+    static __device__ __forceinline__ void cvt(const float4& v, float (&o)[4]) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
+    static __device__ __forceinline__ float4 pack(const float (&o)[4]) { return make_float4(o[0], o[1], o[2], o[3]); }
+};
+template <> struct VecFmt<float, 8> {
+    struct raw_t { float4 a, b; };
+    static __device__ __forceinline__ void cvt(const raw_t& v, float (&o)[8]) {
+        o[0] = v.a.x; o[1] = v.a.y; o[2] = v.a.z; o[3] = v.a.w; o[4] = v.b.x; o[5] = v.b.y; o[6] = v.b.z; o[7] = v.b.w;
+    }
+    static __device__ __forceinline__ raw_t pack(const float (&o)[8]) { return {make_float4(o[0], o[1], o[2], o[3]), make_float4(o[4], o[5], o[6], o[7])}; }
+};
+template <> struct VecFmt<bf16_t, 4> {
+    typedef uint2 raw_t;
+    static __device__ __forceinline__ void cvt(const uint2& v, float (&o)[4]) {
+        o[0] = h16_lo(v.x); o[1] = h16_hi(v.x);
+        o[2] = h16_lo(v.y); o[3] = h16_hi(v.y);
+    }
+    static __device__ __forceinline__ uint2 pack(const float (&o)[4]) { return make_uint2(pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3])); }
+};
+template <> struct VecFmt<bf16_t, 8> {
+    typedef uint4 raw_t;
+    static __device__ __forceinline__ void cvt(const uint4& v, float (&o)[8]) {
+        o[0] = h16_lo(v.x); o[1] = h16_hi(v.x);
+        o[2] = h16_lo(v.y); o[3] = h16_hi(v.y);
+        o[4] = h16_lo(v.z); o[5] = h16_hi(v.z);
+        o[6] = h16_lo(v.w); o[7] = h16_hi(v.w);
+    }
+    static __device__ __forceinline__ uint4 pack(const float (&o)[8]) {
+        return make_uint4(pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]), pack_bf16x2(o[4], o[5]), pack_bf16x2(o[6], o[7]));
+    }
+};
+template <typename T, int VEC> struct Vec : VecFmt<T, VEC> {
+    typedef VecFmt<T, VEC> F;
+    typedef typename F::raw_t raw_t;
+    static __device__ __forceinline__ raw_t load(const T* p) { return *reinterpret_cast<const raw_t*>(p); }
+    static __device__ __forceinline__ void store(T* p, const raw_t& v) { *reinterpret_cast<raw_t*>(p) = v; }
+    static __device__ __forceinline__ raw_t zero() {
+        const float z[VEC] = {};
+        return F::pack(z);
+    }
+    // the elements at p as floats, and back
+    static __device__ __forceinline__ void get(const T* p, float (&o)[VEC]) { F::cvt(*reinterpret_cast<const raw_t*>(p), o); }
+    static __device__ __forceinline__ void put(T* p, const float (&o)[VEC]) { *reinterpret_cast<raw_t*>(p) = F::pack(o); }
+    // the elements as raw BITS (no trip through f32, which may quiet a NaN)
+    static __device__ __forceinline__ void copy(const T* src, T* dst) { *reinterpret_cast<raw_t*>(dst) = *reinterpret_cast<const raw_t*>(src); }
+    // a[k] += element k
+    static __device__ __forceinline__ void add(const raw_t& v, float (&a)[VEC]) {
+        float o[VEC];
+        F::cvt(v, o);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) a[k] += o[k];
+    }
+};
+// the 4-element form most kernels use (16 B of f32, 8 B of 16-bit data)
+template <typename T> __device__ __forceinline__ void ld4(const T* p, float (&o)[4]) { Vec<T, 4>::get(p, o); }
+template <typename T> __device__ __forceinline__ void st4(T* p, const float (&o)[4]) { Vec<T, 4>::put(p, o); }
 
 // ---------------------------------------------------------------------------------------------
 // wave64 reductions (all 64 lanes end with the result)
@@ -311,3 +356,43 @@ void ecamp_prof_end(hipStream_t s);
 #define ECAMP_PROF_GEMM_FP8 3
 
 static inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// ---------------------------------------------------------------------------------------------
+// The flat launch path of the HBM-bound helpers (elementwise, vision outside the SR head, optim, finetune): an entry is
+// "check, grid, one launch expression".
+// The grid of a grid-stride kernel over `items` work items: 256 threads, ceil(items / 256) workgroups, at most `cap` (and at least one:
+// a launch over nothing is an idle workgroup, not a configuration error).
+static inline dim3 flat_grid(int64_t items, int64_t cap) {
+    const int64_t nb = (items + 255) / 256;
+    return dim3((unsigned)(nb < 1 ? 1 : nb > cap ? cap : nb));
+}
+// The one dtype dispatch: `launch` is a generic callable, called with a dtype_tag of float (ECAMP_F32) or bf16_t (ECAMP_BF16, the library's
+// 16-bit format); any other code is refused before anything is launched.  Returns what the entry returns.
+template <typename T> struct dtype_tag { typedef T type; };
+static inline bool dtype_known(int dtype) { return dtype == ECAMP_F32 || dtype == ECAMP_BF16; }
+static inline int refuse_dtype(const char* entry, int dtype) { return ecamp_set_error(-1, "%s: dtype %d", entry, dtype); }
+template <typename F> static inline int launch_typed(const char* entry, const char* func, int dtype, F&& launch) {
+    if (dtype == ECAMP_F32) launch(dtype_tag<float>{});
+    else if (dtype == ECAMP_BF16) launch(dtype_tag<bf16_t>{});
+    else return refuse_dtype(entry, dtype);
+    return ecamp_launch_status(func);
+}
+#define ECAMP_LAUNCH_TYPED(entry, dtype, ...) launch_typed(entry, __func__, dtype, __VA_ARGS__)
+#define ECAMP_TAG_T(tag) typename decltype(tag)::type
+
+// The tail of the 256-thread column reductions (colsum, seq_sum, masktok_grad): thread (tx, ty) = (threadIdx.x & 31, threadIdx.x >> 5) holds
+// the sums of columns tx * 4 .. + 3 of a 128-column tile over row slice ty.  The eight slices are added in the order 0 .. 7; the total of
+// tile column threadIdx.x comes back in threads 0 .. 127 (the others get 0).
+__device__ __forceinline__ float col_tile_sum(const float (&acc)[4]) {
+    __shared__ float sh[8][129];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) sh[ty][tx * 4 + r] = acc[r];
+    __syncthreads();
+    float t = 0.f;
+    if (threadIdx.x < 128) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) t += sh[j][threadIdx.x];
+    }
+    return t;
+}

@@ -14,57 +14,6 @@ constexpr int DP_THREADS = 256;
 constexpr int DP_MAX_BLOCKS = 4096;   // workgroups per launch, as the other element-wise kernels cap it
 constexpr int DP_VEC_PER_THREAD = 4;  // vectors a thread walks per sample when the sample is long enough
 
-// VEC consecutive elements as floats (VEC = 4: common.h's ld4 / st4; VEC = 8: 16 bytes of 16-bit data, or two float4)
-template <typename T, int VEC> __device__ __forceinline__ void ldv(const T* p, float (&o)[VEC]) {
-    if constexpr (VEC == 4) {
-        ld4<T>(p, o);
-    } else if constexpr (sizeof(T) == 4) {
-        const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-        o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-    } else {
-        const uint4 v = *reinterpret_cast<const uint4*>(p);
-        o[0] = h16_lo(v.x); o[1] = h16_hi(v.x); o[2] = h16_lo(v.y); o[3] = h16_hi(v.y);
-        o[4] = h16_lo(v.z); o[5] = h16_hi(v.z); o[6] = h16_lo(v.w); o[7] = h16_hi(v.w);
-    }
-}
-template <typename T, int VEC> __device__ __forceinline__ void stv(T* p, const float (&o)[VEC]) {
-    if constexpr (VEC == 4) {
-        st4<T>(p, o);
-    } else if constexpr (sizeof(T) == 4) {
-        reinterpret_cast<float4*>(p)[0] = make_float4(o[0], o[1], o[2], o[3]);
-        reinterpret_cast<float4*>(p)[1] = make_float4(o[4], o[5], o[6], o[7]);
-    } else {
-        uint4 v;
-        v.x = pack_bf16x2(o[0], o[1]); v.y = pack_bf16x2(o[2], o[3]);
-        v.z = pack_bf16x2(o[4], o[5]); v.w = pack_bf16x2(o[6], o[7]);
-        *reinterpret_cast<uint4*>(p) = v;
-    }
-}
-// the same elements as raw bits (a dropped sample's rows are the residual's BITS: no trip through f32, which may quiet a NaN)
-template <int BYTES> struct RawBits;
-template <> struct RawBits<8> { typedef uint2 type; };
-template <> struct RawBits<16> { typedef uint4 type; };
-template <typename T, int VEC> __device__ __forceinline__ void copyv(const T* src, T* dst) {
-    if constexpr (VEC * sizeof(T) == 32) {
-        const uint4 a = reinterpret_cast<const uint4*>(src)[0], b = reinterpret_cast<const uint4*>(src)[1];
-        reinterpret_cast<uint4*>(dst)[0] = a;
-        reinterpret_cast<uint4*>(dst)[1] = b;
-    } else {
-        typedef typename RawBits<VEC * sizeof(T)>::type raw_t;
-        *reinterpret_cast<raw_t*>(dst) = *reinterpret_cast<const raw_t*>(src);
-    }
-}
-template <typename T, int VEC> __device__ __forceinline__ void zerov(T* dst) {
-    if constexpr (VEC * sizeof(T) == 32) {
-        reinterpret_cast<uint4*>(dst)[0] = make_uint4(0u, 0u, 0u, 0u);
-        reinterpret_cast<uint4*>(dst)[1] = make_uint4(0u, 0u, 0u, 0u);
-    } else if constexpr (VEC * sizeof(T) == 16) {
-        *reinterpret_cast<uint4*>(dst) = make_uint4(0u, 0u, 0u, 0u);
-    } else {
-        *reinterpret_cast<uint2*>(dst) = make_uint2(0u, 0u);
-    }
-}
-
 // res, out: R [B, nv * VEC]; y: Y [B, nv * VEC].  `out` may be `y` itself (R == Y): a thread reads its vector of y before it writes
 // the same bytes, and nobody else touches them -- hence no __restrict__ on y and out.
 template <typename R, typename Y, int VEC>
@@ -75,15 +24,15 @@ __global__ __launch_bounds__(DP_THREADS) void drop_path_fwd_kernel(const R* __re
         const int64_t base = b * nv;
         if (s == 0.0f) {   // dropped: y is not read
             for (int64_t i = (int64_t)blockIdx.x * DP_THREADS + threadIdx.x; i < nv; i += (int64_t)gridDim.x * DP_THREADS)
-                copyv<R, VEC>(res + (base + i) * VEC, out + (base + i) * VEC);
+                Vec<R, VEC>::copy(res + (base + i) * VEC, out + (base + i) * VEC);   // the residual's BITS
         } else {
             for (int64_t i = (int64_t)blockIdx.x * DP_THREADS + threadIdx.x; i < nv; i += (int64_t)gridDim.x * DP_THREADS) {
                 float r[VEC], q[VEC];
-                ldv<R, VEC>(res + (base + i) * VEC, r);
-                ldv<Y, VEC>(y + (base + i) * VEC, q);
+                Vec<R, VEC>::get(res + (base + i) * VEC, r);
+                Vec<Y, VEC>::get(y + (base + i) * VEC, q);
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) r[k] = fmaf(s, q[k], r[k]);
-                stv<R, VEC>(out + (base + i) * VEC, r);
+                Vec<R, VEC>::put(out + (base + i) * VEC, r);
             }
         }
     }
@@ -97,14 +46,14 @@ __global__ __launch_bounds__(DP_THREADS) void drop_path_bwd_kernel(const T* __re
         const int64_t base = b * nv;
         if (s == 0.0f) {   // dropped: dout is not read, +0 is written
             for (int64_t i = (int64_t)blockIdx.x * DP_THREADS + threadIdx.x; i < nv; i += (int64_t)gridDim.x * DP_THREADS)
-                zerov<T, VEC>(dy + (base + i) * VEC);
+                Vec<T, VEC>::store(dy + (base + i) * VEC, Vec<T, VEC>::zero());
         } else {
             for (int64_t i = (int64_t)blockIdx.x * DP_THREADS + threadIdx.x; i < nv; i += (int64_t)gridDim.x * DP_THREADS) {
                 float g[VEC];
-                ldv<T, VEC>(dout + (base + i) * VEC, g);
+                Vec<T, VEC>::get(dout + (base + i) * VEC, g);
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) g[k] *= s;
-                stv<T, VEC>(dy + (base + i) * VEC, g);
+                Vec<T, VEC>::put(dy + (base + i) * VEC, g);
             }
         }
     }

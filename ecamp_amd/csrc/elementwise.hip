@@ -16,13 +16,11 @@ __global__ void add_kernel(const T* __restrict__ a, const T* __restrict__ b, T* 
 }
 extern "C" int ecamp_add(const void* a, const void* b, void* y, int64_t n, int32_t dtype, hipStream_t stream) {
     ECAMP_CHECK_ARG(a && b && y && n % 4 == 0, "ecamp_add: bad args (n=%ld must be a multiple of 4)", (long)n);
-    long n4 = n / 4;
-    int nb = (int)((n4 + 255) / 256);
-    if (nb > 4096) nb = 4096;
-    if (dtype == ECAMP_F32) hipLaunchKernelGGL(add_kernel<float>, dim3(nb), dim3(256), 0, stream, (const float*)a, (const float*)b, (float*)y, n4);
-    else hipLaunchKernelGGL(add_kernel<bf16_t>, dim3(nb), dim3(256), 0, stream, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)y, n4);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    const long n4 = n / 4;
+    return ECAMP_LAUNCH_TYPED("ecamp_add", dtype, [&](auto tag) {
+        typedef ECAMP_TAG_T(tag) T;
+        hipLaunchKernelGGL(add_kernel<T>, flat_grid(n4, 4096), dim3(256), 0, stream, (const T*)a, (const T*)b, (T*)y, n4);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -36,16 +34,13 @@ __global__ void cast_kernel(const S* __restrict__ s, D* __restrict__ d, long n4)
 }
 extern "C" int ecamp_cast(const void* src, void* dst, int64_t n, int32_t src_dtype, int32_t dst_dtype, hipStream_t stream) {
     ECAMP_CHECK_ARG(src && dst && n % 4 == 0, "ecamp_cast: bad args (n=%ld)", (long)n);
-    long n4 = n / 4;
-    int nb = (int)((n4 + 255) / 256);
-    if (nb > 4096) nb = 4096;
-    if (src_dtype == ECAMP_F32 && dst_dtype == ECAMP_BF16) hipLaunchKernelGGL((cast_kernel<float, bf16_t>), dim3(nb), dim3(256), 0, stream, (const float*)src, (bf16_t*)dst, n4);
-    else if (src_dtype == ECAMP_BF16 && dst_dtype == ECAMP_F32) hipLaunchKernelGGL((cast_kernel<bf16_t, float>), dim3(nb), dim3(256), 0, stream, (const bf16_t*)src, (float*)dst, n4);
-    else if (src_dtype == ECAMP_F32 && dst_dtype == ECAMP_F32) hipLaunchKernelGGL((cast_kernel<float, float>), dim3(nb), dim3(256), 0, stream, (const float*)src, (float*)dst, n4);
-    else if (src_dtype == ECAMP_BF16 && dst_dtype == ECAMP_BF16) hipLaunchKernelGGL((cast_kernel<bf16_t, bf16_t>), dim3(nb), dim3(256), 0, stream, (const bf16_t*)src, (bf16_t*)dst, n4);
-    else return ecamp_set_error(-1, "ecamp_cast: bad dtypes");
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    if (!dtype_known(dst_dtype)) return refuse_dtype("ecamp_cast", dst_dtype);
+    const long n4 = n / 4;
+    return ECAMP_LAUNCH_TYPED("ecamp_cast", src_dtype, [&](auto tag) {
+        typedef ECAMP_TAG_T(tag) S;
+        if (dst_dtype == ECAMP_F32) hipLaunchKernelGGL((cast_kernel<S, float>), flat_grid(n4, 4096), dim3(256), 0, stream, (const S*)src, (float*)dst, n4);
+        else hipLaunchKernelGGL((cast_kernel<S, bf16_t>), flat_grid(n4, 4096), dim3(256), 0, stream, (const S*)src, (bf16_t*)dst, n4);
+    });
 }
 
 // y = x * alpha * (alpha_dev ? *alpha_dev : 1), computed in f32 (x and y may be the same buffer): the upstream gradient applied to a tensor
@@ -64,13 +59,10 @@ __global__ void scale_kernel(const T* __restrict__ x, T* __restrict__ y, long n4
 extern "C" int ecamp_scale(const void* x, void* y, int64_t n, float alpha, const float* alpha_dev, int32_t dtype, hipStream_t stream) {
     ECAMP_CHECK_ARG(x && y && n > 0 && n % 4 == 0, "ecamp_scale: bad args (n=%ld)", (long)n);
     const long n4 = n / 4;
-    int nb = (int)((n4 + 255) / 256);
-    if (nb > 4096) nb = 4096;
-    if (dtype == ECAMP_F32) hipLaunchKernelGGL(scale_kernel<float>, dim3(nb), dim3(256), 0, stream, (const float*)x, (float*)y, n4, alpha, alpha_dev);
-    else if (dtype == ECAMP_BF16) hipLaunchKernelGGL(scale_kernel<bf16_t>, dim3(nb), dim3(256), 0, stream, (const bf16_t*)x, (bf16_t*)y, n4, alpha, alpha_dev);
-    else return ecamp_set_error(-1, "ecamp_scale: bad dtype");
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    return ECAMP_LAUNCH_TYPED("ecamp_scale", dtype, [&](auto tag) {
+        typedef ECAMP_TAG_T(tag) T;
+        hipLaunchKernelGGL(scale_kernel<T>, flat_grid(n4, 4096), dim3(256), 0, stream, (const T*)x, (T*)y, n4, alpha, alpha_dev);
+    });
 }
 
 extern "C" int ecamp_zero(void* p, int64_t bytes, hipStream_t stream) {
@@ -89,11 +81,8 @@ __global__ __launch_bounds__(256) void zero_blocks_kernel(float* __restrict__ g,
 extern "C" int ecamp_zero_blocks(float* g, const uint8_t* block_flags, int64_t n, hipStream_t stream) {
     ECAMP_CHECK_ARG(g && block_flags && n > 0 && n % 64 == 0, "ecamp_zero_blocks: bad args");
     const long n4 = n / 4;
-    int nb = (int)((n4 + 255) / 256);
-    if (nb > 4096) nb = 4096;
-    hipLaunchKernelGGL(zero_blocks_kernel, dim3(nb), dim3(256), 0, stream, g, block_flags, n4);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    hipLaunchKernelGGL(zero_blocks_kernel, flat_grid(n4, 4096), dim3(256), 0, stream, g, block_flags, n4);
+    return ecamp_launch_status(__func__);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -102,7 +91,6 @@ extern "C" int ecamp_zero_blocks(float* g, const uint8_t* block_flags, int64_t n
 template <typename T>
 __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ X, long ld, long M, int N, float alpha, const float* __restrict__ alpha_dev, int per,
                                                      int lo, int hi, float* __restrict__ out) {
-    __shared__ float sh[8][129];
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const int c0 = blockIdx.x * 128 + tx * 4;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -118,18 +106,9 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ X, lo
             for (int r = 0; r < 4; ++r) acc[r] += p[r];
         }
     }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) sh[ty][tx * 4 + r] = acc[r];
-    __syncthreads();
-    if (threadIdx.x < 128) {
-        int c = blockIdx.x * 128 + threadIdx.x;
-        if (c < N) {
-            float t = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) t += sh[j][threadIdx.x];
-            atomicAdd(out + c, (alpha_dev ? alpha * alpha_dev[0] : alpha) * t);
-        }
-    }
+    const float t = col_tile_sum(acc);
+    const int c = blockIdx.x * 128 + threadIdx.x;
+    if (threadIdx.x < 128 && c < N) atomicAdd(out + c, (alpha_dev ? alpha * alpha_dev[0] : alpha) * t);
 }
 extern "C" int ecamp_colsum(const void* X, int64_t ld, int64_t M, int64_t N, float alpha, const float* alpha_dev, int32_t period, int32_t lo,
                             int32_t hi, float* out, int32_t dtype, hipStream_t stream) {
@@ -140,11 +119,10 @@ extern "C" int ecamp_colsum(const void* X, int64_t ld, int64_t M, int64_t N, flo
     int cap = 2048 / nbx;
     if (cap < 1) cap = 1;
     if (nby > cap) nby = cap;
-    dim3 grid(nbx, nby), block(256);
-    if (dtype == ECAMP_F32) hipLaunchKernelGGL(colsum_kernel<float>, grid, block, 0, stream, (const float*)X, (long)ld, (long)M, (int)N, alpha, alpha_dev, period, lo, hi, out);
-    else hipLaunchKernelGGL(colsum_kernel<bf16_t>, grid, block, 0, stream, (const bf16_t*)X, (long)ld, (long)M, (int)N, alpha, alpha_dev, period, lo, hi, out);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    return ECAMP_LAUNCH_TYPED("ecamp_colsum", dtype, [&](auto tag) {
+        typedef ECAMP_TAG_T(tag) T;
+        hipLaunchKernelGGL(colsum_kernel<T>, dim3(nbx, nby), dim3(256), 0, stream, (const T*)X, (long)ld, (long)M, (int)N, alpha, alpha_dev, period, lo, hi, out);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -166,13 +144,10 @@ __global__ void bcast_add_kernel(const T* __restrict__ x, const T* __restrict__ 
 extern "C" int ecamp_bcast_add(const void* x, const void* g, void* y, int64_t B, int32_t S, int32_t H, int32_t dtype,
                                hipStream_t stream) {
     ECAMP_CHECK_ARG(x && g && y && H % 4 == 0, "ecamp_bcast_add: bad args");
-    long n4 = B * S * (H / 4);
-    int nb = (int)((n4 + 255) / 256);
-    if (nb > 4096) nb = 4096;
-    if (dtype == ECAMP_F32) hipLaunchKernelGGL(bcast_add_kernel<float>, dim3(nb), dim3(256), 0, stream, (const float*)x, (const float*)g, (float*)y, (long)B, S, H / 4);
-    else hipLaunchKernelGGL(bcast_add_kernel<bf16_t>, dim3(nb), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)g, (bf16_t*)y, (long)B, S, H / 4);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    return ECAMP_LAUNCH_TYPED("ecamp_bcast_add", dtype, [&](auto tag) {
+        typedef ECAMP_TAG_T(tag) T;
+        hipLaunchKernelGGL(bcast_add_kernel<T>, flat_grid(B * S * (H / 4), 4096), dim3(256), 0, stream, (const T*)x, (const T*)g, (T*)y, (long)B, S, H / 4);
+    });
 }
 
 // out[b, :] = scale * sum_{s in [s0, s1)} x[b, s, :]     (deterministic; one block column-stripe per b)
@@ -180,7 +155,6 @@ extern "C" int ecamp_bcast_add(const void* x, const void* g, void* y, int64_t B,
 template <typename T>
 __global__ __launch_bounds__(256) void seq_sum_kernel(const T* __restrict__ x, T* __restrict__ out, int S, int H, int s0,
                                                       int s1, float scale) {
-    __shared__ float sh[8][129];
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const long b = blockIdx.y;
     const int c0 = blockIdx.x * 128 + tx * 4;
@@ -193,27 +167,17 @@ __global__ __launch_bounds__(256) void seq_sum_kernel(const T* __restrict__ x, T
             for (int r = 0; r < 4; ++r) acc[r] += p[r];
         }
     }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) sh[ty][tx * 4 + r] = acc[r];
-    __syncthreads();
-    if (threadIdx.x < 128) {
-        int c = blockIdx.x * 128 + threadIdx.x;
-        if (c < H) {
-            float t = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) t += sh[j][threadIdx.x];
-            out[b * H + c] = from_f<T>(t * scale);
-        }
-    }
+    const float t = col_tile_sum(acc);
+    const int c = blockIdx.x * 128 + threadIdx.x;
+    if (threadIdx.x < 128 && c < H) out[b * H + c] = from_f<T>(t * scale);
 }
 extern "C" int ecamp_seq_sum(const void* x, void* out, int64_t B, int32_t S, int32_t H, int32_t s0, int32_t s1, float scale,
                              int32_t dtype, hipStream_t stream) {
     ECAMP_CHECK_ARG(x && out && H % 4 == 0 && s0 >= 0 && s1 <= S && s0 < s1, "ecamp_seq_sum: bad args");
-    dim3 grid(ceil_div(H, 128), (unsigned)B), block(256);
-    if (dtype == ECAMP_F32) hipLaunchKernelGGL(seq_sum_kernel<float>, grid, block, 0, stream, (const float*)x, (float*)out, S, H, s0, s1, scale);
-    else hipLaunchKernelGGL(seq_sum_kernel<bf16_t>, grid, block, 0, stream, (const bf16_t*)x, (bf16_t*)out, S, H, s0, s1, scale);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    return ECAMP_LAUNCH_TYPED("ecamp_seq_sum", dtype, [&](auto tag) {
+        typedef ECAMP_TAG_T(tag) T;
+        hipLaunchKernelGGL(seq_sum_kernel<T>, dim3(ceil_div(H, 128), (unsigned)B), dim3(256), 0, stream, (const T*)x, (T*)out, S, H, s0, s1, scale);
+    });
 }
 
 // y[b, s, :] (+)= g[b, :] * scale for s in [s0, s1), and optionally zero / keep other rows:
@@ -243,13 +207,10 @@ __global__ void seq_bcast_kernel(const T* __restrict__ g, T* __restrict__ y, lon
 extern "C" int ecamp_seq_bcast(const void* g, void* y, int64_t B, int32_t S, int32_t H, int32_t s0, int32_t s1, float scale,
                                int32_t mode, int32_t dtype, hipStream_t stream) {
     ECAMP_CHECK_ARG(g && y && H % 4 == 0, "ecamp_seq_bcast: bad args");
-    long n4 = B * S * (H / 4);
-    int nb = (int)((n4 + 255) / 256);
-    if (nb > 4096) nb = 4096;
-    if (dtype == ECAMP_F32) hipLaunchKernelGGL(seq_bcast_kernel<float>, dim3(nb), dim3(256), 0, stream, (const float*)g, (float*)y, (long)B, S, H / 4, s0, s1, scale, mode);
-    else hipLaunchKernelGGL(seq_bcast_kernel<bf16_t>, dim3(nb), dim3(256), 0, stream, (const bf16_t*)g, (bf16_t*)y, (long)B, S, H / 4, s0, s1, scale, mode);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    return ECAMP_LAUNCH_TYPED("ecamp_seq_bcast", dtype, [&](auto tag) {
+        typedef ECAMP_TAG_T(tag) T;
+        hipLaunchKernelGGL(seq_bcast_kernel<T>, flat_grid(B * S * (H / 4), 4096), dim3(256), 0, stream, (const T*)g, (T*)y, (long)B, S, H / 4, s0, s1, scale, mode);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -263,11 +224,8 @@ __global__ void dropout_mask_kernel(uint8_t* __restrict__ keep, long n, float p,
 }
 extern "C" int ecamp_dropout_mask(uint8_t* keep, int64_t n, float p, uint64_t seed, uint64_t offset, hipStream_t stream) {
     ECAMP_CHECK_ARG(keep && n > 0 && p >= 0.f && p < 1.f, "ecamp_dropout_mask: bad args");
-    int nb = (int)((n + 255) / 256);
-    if (nb > 8192) nb = 8192;
-    hipLaunchKernelGGL(dropout_mask_kernel, dim3(nb), dim3(256), 0, stream, keep, (long)n, p, seed, offset);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    hipLaunchKernelGGL(dropout_mask_kernel, flat_grid(n, 8192), dim3(256), 0, stream, keep, (long)n, p, seed, offset);
+    return ecamp_launch_status(__func__);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -283,12 +241,8 @@ __global__ void uniform_kernel(float* __restrict__ out, long n, uint64_t seed, u
 }
 extern "C" int ecamp_uniform(float* out, int64_t n, uint64_t seed, uint64_t offset, hipStream_t stream) {
     ECAMP_CHECK_ARG(out && n > 0, "ecamp_uniform: bad args");
-    long n4 = (n + 3) / 4;
-    int nb = (int)((n4 + 255) / 256);
-    if (nb > 2048) nb = 2048;
-    hipLaunchKernelGGL(uniform_kernel, dim3(nb), dim3(256), 0, stream, out, (long)n, seed, offset);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    hipLaunchKernelGGL(uniform_kernel, flat_grid((n + 3) / 4, 2048), dim3(256), 0, stream, out, (long)n, seed, offset);
+    return ecamp_launch_status(__func__);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -306,11 +260,9 @@ __global__ void gelu_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ 
 }
 extern "C" int ecamp_gelu_bwd(const void* dy, const void* pre, void* dx, int64_t n, int32_t dtype, hipStream_t stream) {
     ECAMP_CHECK_ARG(dy && pre && dx && n % 4 == 0, "ecamp_gelu_bwd: bad args");
-    long n4 = n / 4;
-    int nb = (int)((n4 + 255) / 256);
-    if (nb > 4096) nb = 4096;
-    if (dtype == ECAMP_F32) hipLaunchKernelGGL(gelu_bwd_kernel<float>, dim3(nb), dim3(256), 0, stream, (const float*)dy, (const float*)pre, (float*)dx, n4);
-    else hipLaunchKernelGGL(gelu_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, stream, (const bf16_t*)dy, (const bf16_t*)pre, (bf16_t*)dx, n4);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    const long n4 = n / 4;
+    return ECAMP_LAUNCH_TYPED("ecamp_gelu_bwd", dtype, [&](auto tag) {
+        typedef ECAMP_TAG_T(tag) T;
+        hipLaunchKernelGGL(gelu_bwd_kernel<T>, flat_grid(n4, 4096), dim3(256), 0, stream, (const T*)dy, (const T*)pre, (T*)dx, n4);
+    });
 }

@@ -36,11 +36,8 @@ extern "C" int ecamp_cls_head_dgrad(const float* dlogits, const float* W, float*
     ECAMP_CHECK_ARG(D >= 4 && D % 4 == 0, "cls_head_dgrad: D=%d must be a positive multiple of 4", D);
     ECAMP_CHECK_ARG(B >= 1, "cls_head_dgrad: B=%lld must be positive", (long long)B);
     ECAMP_CHECK_ARG(((reinterpret_cast<uintptr_t>(W) | reinterpret_cast<uintptr_t>(dfeat)) & 15) == 0, "cls_head_dgrad: W and dfeat must be 16-byte aligned");
-    const int64_t blocks = (B * (D / 4) + 255) / 256;
-    hipLaunchKernelGGL(cls_head_dgrad_kernel, dim3((unsigned)(blocks < CLS_MAX_GRID ? blocks : CLS_MAX_GRID)), dim3(256), 0, stream, dlogits, W, dfeat,
-                       B, C, D);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    hipLaunchKernelGGL(cls_head_dgrad_kernel, flat_grid(B * (D / 4), CLS_MAX_GRID), dim3(256), 0, stream, dlogits, W, dfeat, B, C, D);
+    return ecamp_launch_status(__func__);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -141,34 +138,11 @@ __global__ __launch_bounds__(256) void pool_norm_bwd_affine_kernel(const float* 
     }
 }
 
-template <typename T, int VEC> struct RowVec;
-template <> struct RowVec<float, 4> {
-    typedef float4 raw_t;
-    static __device__ __forceinline__ float4 pack(const float* v) { return *reinterpret_cast<const float4*>(v); }
-    static __device__ __forceinline__ float4 zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-};
-template <> struct RowVec<bf16_t, 4> {
-    typedef uint2 raw_t;
-    static __device__ __forceinline__ uint2 pack(const float* v) {
-        const float4 a = *reinterpret_cast<const float4*>(v);
-        return make_uint2(pack_bf16x2(a.x, a.y), pack_bf16x2(a.z, a.w));
-    }
-    static __device__ __forceinline__ uint2 zero() { return make_uint2(0u, 0u); }
-};
-template <> struct RowVec<bf16_t, 8> {
-    typedef uint4 raw_t;
-    static __device__ __forceinline__ uint4 pack(const float* v) {
-        const float4 a = *reinterpret_cast<const float4*>(v), c = *reinterpret_cast<const float4*>(v + 4);
-        return make_uint4(pack_bf16x2(a.x, a.y), pack_bf16x2(a.z, a.w), pack_bf16x2(c.x, c.y), pack_bf16x2(c.z, c.w));
-    }
-    static __device__ __forceinline__ uint4 zero() { return make_uint4(0u, 0u, 0u, 0u); }
-};
-
 template <typename T, int VEC>
 __global__ __launch_bounds__(256) void pool_norm_bwd_store_kernel(const float* __restrict__ dpool, T* __restrict__ dx, int64_t B, int Tn, int D,
                                                                   int t0, int t1, int nv, int cw, int rows_par, int nslab, int nchunk,
                                                                   int chunk_len) {
-    typedef RowVec<T, VEC> V;
+    typedef Vec<T, VEC> V;
     typedef typename V::raw_t raw_t;
     const int r = threadIdx.x / cw, c = threadIdx.x % cw;
     const int64_t items = B * nchunk * nslab;
@@ -180,7 +154,9 @@ __global__ __launch_bounds__(256) void pool_norm_bwd_store_kernel(const float* _
         if (r >= rows_par || cv >= nv) continue;
         const int ta = chunk * chunk_len;
         const int tb = ta + chunk_len < Tn ? ta + chunk_len : Tn;
-        const raw_t val = V::pack(dpool + b * D + (int64_t)cv * VEC), zero = V::zero();
+        float v[VEC];
+        Vec<float, VEC>::cvt(Vec<float, VEC>::load(dpool + b * D + (int64_t)cv * VEC), v);
+        const raw_t val = V::pack(v), zero = V::zero();
         T* base = dx + b * Tn * (int64_t)D + (int64_t)cv * VEC;
         for (int t = ta + r; t < tb; t += rows_par) *reinterpret_cast<raw_t*>(base + (int64_t)t * D) = (t >= t0 && t < t1) ? val : zero;
     }
@@ -266,27 +242,12 @@ static bool peg_shape_ok(int64_t B, int32_t T, int32_t D, int32_t dtype) {
     return B >= 1 && T >= 2 && D >= 1 && D % (dtype == ECAMP_F32 ? 4 : 8) == 0;
 }
 
-template <typename T> struct PegVec;
-template <> struct PegVec<float> {
-    static constexpr int VEC = 4;
-    typedef float4 raw_t;
-    static __device__ __forceinline__ void add(float* a, const float4& v) { a[0] += v.x; a[1] += v.y; a[2] += v.z; a[3] += v.w; }
-};
-template <> struct PegVec<bf16_t> {
-    static constexpr int VEC = 8;
-    typedef uint4 raw_t;
-    static __device__ __forceinline__ void add(float* a, const uint4& v) {
-        a[0] += h16_lo(v.x); a[1] += h16_hi(v.x); a[2] += h16_lo(v.y); a[3] += h16_hi(v.y);
-        a[4] += h16_lo(v.z); a[5] += h16_hi(v.z); a[6] += h16_lo(v.w); a[7] += h16_hi(v.w);
-    }
-};
-
 template <typename T>
 __global__ __launch_bounds__(256) void pos_embed_grad_stream_kernel(const T* __restrict__ dx, float* __restrict__ part, int64_t B, int64_t nv,
                                                                     int ntile, int nsplit, int64_t bchunk) {
-    typedef PegVec<T> V;
+    constexpr int VEC = 16 / sizeof(T);   // one 16-byte access: peg_plan's `vec`
+    typedef Vec<T, VEC> V;
     typedef typename V::raw_t raw_t;
-    constexpr int VEC = V::VEC;
     __shared__ float sh[PEG_LANES - 1][VEC][PEG_CW];   // [lane][element][column]: a wave writes 64 consecutive floats
     const int c = threadIdx.x & (PEG_CW - 1), lane = threadIdx.x / PEG_CW;
     const int64_t items = (int64_t)ntile * nsplit;
@@ -306,9 +267,9 @@ __global__ __launch_bounds__(256) void pos_embed_grad_stream_kernel(const T* __r
 #pragma unroll
                 for (int k = 0; k < 4; ++k) v[k] = src[(b + k * PEG_LANES) * nv];
 #pragma unroll
-                for (int k = 0; k < 4; ++k) V::add(acc, v[k]);
+                for (int k = 0; k < 4; ++k) V::add(v[k], acc);
             }
-            for (; b < b1; b += PEG_LANES) V::add(acc, src[b * nv]);
+            for (; b < b1; b += PEG_LANES) V::add(src[b * nv], acc);
         }
         if (lane > 0) {
 #pragma unroll
@@ -423,12 +384,11 @@ extern "C" int ecamp_pos_embed_grad(const void* dx, float* dpos, float* dcls, fl
     const PegPlan p = peg_plan(B, T, D, dtype);
     const int64_t items = (int64_t)p.ntile * p.nsplit;
     const dim3 grid((unsigned)(items < CLS_MAX_GRID ? items : CLS_MAX_GRID)), block(256);
-    if (dtype == ECAMP_F32)
-        hipLaunchKernelGGL(pos_embed_grad_stream_kernel<float>, grid, block, 0, stream, (const float*)dx, (float*)ws, B, p.nv, p.ntile, p.nsplit, p.bchunk);
-    else
-        hipLaunchKernelGGL(pos_embed_grad_stream_kernel<bf16_t>, grid, block, 0, stream, (const bf16_t*)dx, (float*)ws, B, p.nv, p.ntile, p.nsplit,
-                           p.bchunk);
-    ECAMP_LAUNCH_CHECK();
+    const int rc = ECAMP_LAUNCH_TYPED("pos_embed_grad", dtype, [&](auto tag) {
+        typedef ECAMP_TAG_T(tag) T;
+        hipLaunchKernelGGL(pos_embed_grad_stream_kernel<T>, grid, block, 0, stream, (const T*)dx, (float*)ws, B, p.nv, p.ntile, p.nsplit, p.bchunk);
+    });
+    if (rc) return rc;
     const int64_t pos_wg = ((int64_t)T * D / 4 + 255) / 256;
     const int npos = (int)(pos_wg < PEG_APPLY_GRID ? pos_wg : PEG_APPLY_GRID);
     const int bias_wg = ceil_div(D, PEG_BIAS_COLS);
@@ -549,12 +509,9 @@ extern "C" int ecamp_sgd_grouped(float* p, const float* g, float* buf, void* p16
         hp.wd[i] = i < ngroups ? wd_host[i] : 0.f;
     }
     const long n4 = n / 4;
-    int nb = (int)((n4 + 255) / 256);
-    if (nb > GROUPED_MAX_GRID) nb = GROUPED_MAX_GRID;
-    hipLaunchKernelGGL(sgd_grouped_kernel, dim3(nb), dim3(256), 0, stream, p, g, buf, (bf16_t*)p16, block_group, n4, hp, momentum, max_norm, partials,
-                       npart, grad_scale, ctl, norm_out);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    hipLaunchKernelGGL(sgd_grouped_kernel, flat_grid(n4, GROUPED_MAX_GRID), dim3(256), 0, stream, p, g, buf, (bf16_t*)p16, block_group, n4, hp, momentum,
+                       max_norm, partials, npart, grad_scale, ctl, norm_out);
+    return ecamp_launch_status(__func__);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -601,6 +558,5 @@ extern "C" int ecamp_sgd_scale_update(const float* partials, int32_t npart, floa
     ECAMP_CHECK_ARG(max_scale > 0.f, "sgd_scale_update: max_scale=%g must be positive", (double)max_scale);
     hipLaunchKernelGGL(sgd_scale_update_kernel, dim3(1), dim3(256), 0, stream, partials, npart, state, ctl, norm_out, growth, backoff, (float)window,
                        max_scale);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    return ecamp_launch_status(__func__);
 }

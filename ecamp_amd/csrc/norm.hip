@@ -8,39 +8,8 @@
 
 // VEC elements per lane access: 4 (16 B of f32, 8 B of bf16) or, for bf16 rows whose length is a multiple of 8, 8 (16 B -- the
 // streaming optimum of this chip; a 768-column row is 96 such chunks = one full wave access and one half-filled one, instead of three
-// 8-byte ones).  Round 4: the 8-byte form ran at 3 TB/s inside the step (fwd 27.7 us, bwd 31.8 us on 12800 x 768).
-template <typename T, int VEC> struct LnVec;
-template <> struct LnVec<float, 4> {
-    typedef float4 raw_t;
-    static __device__ __forceinline__ void cvt(const float4& v, float (&o)[4]) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
-    static __device__ __forceinline__ float4 pack(const float (&o)[4]) { return make_float4(o[0], o[1], o[2], o[3]); }
-};
-template <> struct LnVec<float, 8> {   // (the f32 residual stream read beside 8-wide 16-bit rows: two 16-B accesses)
-    struct raw_t { float4 a, b; };
-    static __device__ __forceinline__ void cvt(const raw_t& v, float (&o)[8]) {
-        o[0] = v.a.x; o[1] = v.a.y; o[2] = v.a.z; o[3] = v.a.w; o[4] = v.b.x; o[5] = v.b.y; o[6] = v.b.z; o[7] = v.b.w;
-    }
-};
-template <> struct LnVec<bf16_t, 4> {
-    typedef uint2 raw_t;
-    static __device__ __forceinline__ void cvt(const uint2& v, float (&o)[4]) {
-        o[0] = h16_lo(v.x); o[1] = h16_hi(v.x);
-        o[2] = h16_lo(v.y); o[3] = h16_hi(v.y);
-    }
-    static __device__ __forceinline__ uint2 pack(const float (&o)[4]) { return make_uint2(pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3])); }
-};
-template <> struct LnVec<bf16_t, 8> {
-    typedef uint4 raw_t;
-    static __device__ __forceinline__ void cvt(const uint4& v, float (&o)[8]) {
-        o[0] = h16_lo(v.x); o[1] = h16_hi(v.x);
-        o[2] = h16_lo(v.y); o[3] = h16_hi(v.y);
-        o[4] = h16_lo(v.z); o[5] = h16_hi(v.z);
-        o[6] = h16_lo(v.w); o[7] = h16_hi(v.w);
-    }
-    static __device__ __forceinline__ uint4 pack(const float (&o)[8]) {
-        return make_uint4(pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]), pack_bf16x2(o[4], o[5]), pack_bf16x2(o[6], o[7]));
-    }
-};
+// 8-byte ones).  Round 4: the 8-byte form ran at 3 TB/s inside the step (fwd 27.7 us, bwd 31.8 us on 12800 x 768).  The accesses are
+// common.h's Vec<T, VEC>; (float, 8) is the f32 residual stream read beside 8-wide 16-bit rows.
 // keep-mask scales of the VEC elements of chunk `c` of a row of `nv` chunks (element index row * cols + c * VEC + r): a whole Philox call
 // for an 8-wide chunk, half a call for a 4-wide one (common.h: eight consecutive elements share a call)
 template <int VEC>
@@ -68,8 +37,8 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
                                                      float* __restrict__ q8_amax) {
     typedef typename LnRow<T>::io TY;
     typedef typename LnRow<T>::z TX;
-    typedef LnVec<TY, VEC> V;
-    typedef LnVec<TX, VEC> VX;
+    typedef Vec<TY, VEC> V;
+    typedef Vec<TX, VEC> VX;
     typedef typename V::raw_t raw_t;
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -204,8 +173,8 @@ __global__ __launch_bounds__(LN_BWD_WAVES * 64) void ln_bwd_kernel(const T* __re
                                                      uint64_t seed, uint64_t offset) {
     typedef typename LnRow<T>::io TY;
     typedef typename LnRow<T>::z TZ;
-    typedef LnVec<TY, VEC> V;
-    typedef LnVec<TZ, VEC> VZ;
+    typedef Vec<TY, VEC> V;
+    typedef Vec<TZ, VEC> VZ;
     typedef typename V::raw_t raw_t;
     typedef typename VZ::raw_t zraw_t;
     extern __shared__ __attribute__((aligned(16))) float sh[];  // [8][cols]

@@ -16,13 +16,9 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ x,
 }
 extern "C" int ecamp_sumsq(const float* x, int64_t n, float* out, hipStream_t stream) {
     ECAMP_CHECK_ARG(x && out && n % 4 == 0, "ecamp_sumsq: n=%ld must be a multiple of 4", (long)n);
-    long n4 = n / 4;
-    int nb = (int)((n4 + 255) / 256);
-    if (nb > 2048) nb = 2048;
-    if (nb < 1) nb = 1;
-    hipLaunchKernelGGL(sumsq_kernel, dim3(nb), dim3(256), 0, stream, x, n4, out);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    const long n4 = n / 4;
+    hipLaunchKernelGGL(sumsq_kernel, flat_grid(n4, 2048), dim3(256), 0, stream, x, n4, out);
+    return ecamp_launch_status(__func__);
 }
 
 // p *= 1 - lr*wd ; m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ; p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)
@@ -53,15 +49,11 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
 extern "C" int ecamp_adamw(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1,
                            float beta2, float eps, float weight_decay, int64_t step, float grad_scale, hipStream_t stream) {
     ECAMP_CHECK_ARG(p && g && m && v && n % 4 == 0 && step >= 1, "ecamp_adamw: bad args (n=%ld)", (long)n);
-    long n4 = n / 4;
-    int nb = (int)((n4 + 255) / 256);
-    if (nb > 4096) nb = 4096;
-    if (nb < 1) nb = 1;
-    double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-    hipLaunchKernelGGL(adamw_kernel, dim3(nb), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, n4, lr, beta1, beta2, eps,
+    const long n4 = n / 4;
+    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+    hipLaunchKernelGGL(adamw_kernel, flat_grid(n4, 4096), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, n4, lr, beta1, beta2, eps,
                        weight_decay, (float)bc1, (float)(1.0 / sqrt(bc2)), grad_scale);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    return ecamp_launch_status(__func__);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -121,14 +113,11 @@ extern "C" int ecamp_adamw_grouped(float* p, const float* g, float* m, float* v,
         hp.lr[i] = i < ngroups ? lr_host[i] : 0.f;
         hp.wd[i] = i < ngroups ? wd_host[i] : 0.f;
     }
-    long n4 = n / 4;
-    int nb = (int)((n4 + 255) / 256);
-    if (nb > GROUPED_MAX_GRID) nb = GROUPED_MAX_GRID;
-    double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-    hipLaunchKernelGGL(adamw_grouped_kernel, dim3(nb), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, block_group, n4, hp, beta1,
-                       beta2, eps, (float)bc1, (float)(1.0 / sqrt(bc2)), grad_scale, grad_sumsq, ctl);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    const long n4 = n / 4;
+    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+    hipLaunchKernelGGL(adamw_grouped_kernel, flat_grid(n4, GROUPED_MAX_GRID), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, block_group, n4, hp,
+                       beta1, beta2, eps, (float)bc1, (float)(1.0 / sqrt(bc2)), grad_scale, grad_sumsq, ctl);
+    return ecamp_launch_status(__func__);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -169,6 +158,5 @@ extern "C" int ecamp_loss_scale_update(const float* sumsq, float* state, float* 
     ECAMP_CHECK_ARG(growth_factor > 1.f && backoff_factor > 0.f && backoff_factor < 1.f && growth_interval >= 1, "ecamp_loss_scale_update: bad factors");
     hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(64), 0, stream, sumsq, state, opt_step, ctl, norm_out, growth_factor, backoff_factor,
                        (float)growth_interval, beta1, beta2);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    return ecamp_launch_status(__func__);
 }

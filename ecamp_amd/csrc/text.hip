@@ -214,11 +214,11 @@ extern "C" int ecamp_bert_embed_fwd(const int64_t* ids, const int64_t* type_ids,
     dim3 grid(S, gy), block(256);
     const int it = ceil_div(cols / 4, 64);
 #define L(T_, IT_) hipLaunchKernelGGL((bert_embed_fwd_kernel<T_, IT_>), grid, block, 0, stream, (const long*)ids, (const long*)type_ids, word, pos, type, gamma, beta, (T_*)z, (T_*)e, mean, rstd, (long)B, S, cols, eps, drop_p, seed, offset)
-    if (dtype == ECAMP_F32) { if (it <= 1) L(float, 1); else if (it <= 2) L(float, 2); else if (it <= 3) L(float, 3); else L(float, 4); }
-    else { if (it <= 1) L(bf16_t, 1); else if (it <= 2) L(bf16_t, 2); else if (it <= 3) L(bf16_t, 3); else L(bf16_t, 4); }
+    return ECAMP_LAUNCH_TYPED("bert_embed_fwd", dtype, [&](auto tag) {
+        typedef ECAMP_TAG_T(tag) T;
+        if (it <= 1) L(T, 1); else if (it <= 2) L(T, 2); else if (it <= 3) L(T, 3); else L(T, 4);
+    });
 #undef L
-    ECAMP_LAUNCH_CHECK();
-    return 0;
 }
 
 extern "C" int ecamp_bert_embed_bwd(const void* de, const void* z, const float* mean, const float* rstd, const float* gamma,
@@ -236,11 +236,11 @@ extern "C" int ecamp_bert_embed_bwd(const void* de, const void* z, const float* 
     size_t shm = (size_t)4 * cols * sizeof(float);
     const int it = ceil_div(cols / 4, 64);
 #define L(T_, IT_) hipLaunchKernelGGL((bert_embed_bwd_kernel<T_, IT_>), grid, block, shm, stream, (const T_*)de, (const T_*)z, mean, rstd, gamma, (const long*)ids, (const long*)type_ids, gword, gpos, gtype, dgamma, dbeta, (long)B, S, cols, pad_id, hot0, hot1, drop_p, seed, offset)
-    if (dtype == ECAMP_F32) { if (it <= 1) L(float, 1); else if (it <= 2) L(float, 2); else if (it <= 3) L(float, 3); else L(float, 4); }
-    else { if (it <= 1) L(bf16_t, 1); else if (it <= 2) L(bf16_t, 2); else if (it <= 3) L(bf16_t, 3); else L(bf16_t, 4); }
+    return ECAMP_LAUNCH_TYPED("bert_embed_bwd", dtype, [&](auto tag) {
+        typedef ECAMP_TAG_T(tag) T;
+        if (it <= 1) L(T, 1); else if (it <= 2) L(T, 2); else if (it <= 3) L(T, 3); else L(T, 4);
+    });
 #undef L
-    ECAMP_LAUNCH_CHECK();
-    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------

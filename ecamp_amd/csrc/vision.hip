@@ -183,38 +183,23 @@ extern "C" int ecamp_bicubic_resize_u8(const unsigned char* src, float* dst, int
                                        const float* lut, hipStream_t stream) {
     ECAMP_CHECK_ARG(src && dst && lut && B > 0 && Hs > 0 && Ws > 0 && Hd > 0 && Wd > 0, "bicubic_u8: bad args");
     if (Hs == 2 * Hd && Ws == 2 * Wd && (Wd & 3) == 0 && ((uintptr_t)src & 7) == 0 && ((uintptr_t)dst & 15) == 0) {
-        long n4 = B * Hd * (Wd >> 2);
-        int nb4 = (int)((n4 + 255) / 256);
-        if (nb4 > 16384) nb4 = 16384;
-        hipLaunchKernelGGL(bicubic_half_u8_kernel, dim3(nb4), dim3(256), 0, stream, src, dst, (long)B, Hd, Wd, lut);
-        ECAMP_LAUNCH_CHECK();
-        return 0;
+        hipLaunchKernelGGL(bicubic_half_u8_kernel, flat_grid(B * Hd * (Wd >> 2), 16384), dim3(256), 0, stream, src, dst, (long)B, Hd, Wd, lut);
+        return ecamp_launch_status(__func__);
     }
-    long n = B * Hd * Wd;
-    int nb = (int)((n + 255) / 256);
-    if (nb > 8192) nb = 8192;
-    hipLaunchKernelGGL(bicubic_u8_kernel, dim3(nb), dim3(256), 0, stream, src, dst, (long)B, Hs, Ws, Hd, Wd, (float)Hs / (float)Hd, (float)Ws / (float)Wd, lut);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    hipLaunchKernelGGL(bicubic_u8_kernel, flat_grid(B * Hd * Wd, 8192), dim3(256), 0, stream, src, dst, (long)B, Hs, Ws, Hd, Wd, (float)Hs / (float)Hd,
+                       (float)Ws / (float)Wd, lut);
+    return ecamp_launch_status(__func__);
 }
 extern "C" int ecamp_bicubic_resize(const float* src, float* dst, int64_t planes, int32_t Hs, int32_t Ws, int32_t Hd,
                                     int32_t Wd, hipStream_t stream) {
     ECAMP_CHECK_ARG(src && dst && planes > 0, "bicubic: bad args");
     if (Hs == 2 * Hd && Ws == 2 * Wd && (Wd & 3) == 0 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 15) == 0) {
-        long n4 = planes * Hd * (Wd >> 2);
-        int nb4 = (int)((n4 + 255) / 256);
-        if (nb4 > 16384) nb4 = 16384;
-        hipLaunchKernelGGL(bicubic_half_kernel, dim3(nb4), dim3(256), 0, stream, src, dst, (long)planes, Hd, Wd);
-        ECAMP_LAUNCH_CHECK();
-        return 0;
+        hipLaunchKernelGGL(bicubic_half_kernel, flat_grid(planes * Hd * (Wd >> 2), 16384), dim3(256), 0, stream, src, dst, (long)planes, Hd, Wd);
+        return ecamp_launch_status(__func__);
     }
-    long n = planes * Hd * Wd;
-    int nb = (int)((n + 255) / 256);
-    if (nb > 8192) nb = 8192;
-    hipLaunchKernelGGL(bicubic_kernel, dim3(nb), dim3(256), 0, stream, src, dst, (long)planes, Hs, Ws, Hd, Wd,
+    hipLaunchKernelGGL(bicubic_kernel, flat_grid(planes * Hd * Wd, 8192), dim3(256), 0, stream, src, dst, (long)planes, Hs, Ws, Hd, Wd,
                        (float)Hs / (float)Hd, (float)Ws / (float)Wd);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    return ecamp_launch_status(__func__);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -277,13 +262,11 @@ __global__ void im2col_gather_kernel(const float* __restrict__ imgs, const int* 
 extern "C" int ecamp_im2col_gather(const float* imgs, const int32_t* ids_keep, void* out, int64_t B, int32_t Lk, int32_t C,
                                    int32_t R, int32_t p, int32_t dtype, hipStream_t stream) {
     ECAMP_CHECK_ARG(imgs && ids_keep && out && p % 4 == 0 && R % p == 0, "im2col_gather: bad args");
-    long n = B * (Lk + 1) * (long)(C * p * p / 4);
-    int nb = (int)((n + 255) / 256);
-    if (nb > 8192) nb = 8192;
-    if (dtype == ECAMP_F32) hipLaunchKernelGGL(im2col_gather_kernel<float>, dim3(nb), dim3(256), 0, stream, imgs, ids_keep, (float*)out, (long)B, Lk, C, R, p);
-    else hipLaunchKernelGGL(im2col_gather_kernel<bf16_t>, dim3(nb), dim3(256), 0, stream, imgs, ids_keep, (bf16_t*)out, (long)B, Lk, C, R, p);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    const dim3 grid = flat_grid(B * (Lk + 1) * (long)(C * p * p / 4), 8192);
+    return ECAMP_LAUNCH_TYPED("im2col_gather", dtype, [&](auto tag) {
+        typedef ECAMP_TAG_T(tag) T;
+        hipLaunchKernelGGL(im2col_gather_kernel<T>, grid, dim3(256), 0, stream, imgs, ids_keep, (T*)out, (long)B, Lk, C, R, p);
+    });
 }
 
 // K2a from the uint8 grayscale image itself (the classifier's device image pipeline: uint8 [B, R, R] at the model's own size): the
@@ -316,21 +299,22 @@ extern "C" int ecamp_im2col_u8(const uint8_t* img, const float* lut, const int32
                                int32_t dtype, hipStream_t stream) {
     ECAMP_CHECK_ARG(img && lut && ids_keep && out && B > 0 && Lk >= 0 && p > 0 && p % 4 == 0 && R > 0 && R % p == 0 && ((uintptr_t)img & 3) == 0 && ((uintptr_t)out & 15) == 0,
                     "im2col_u8: bad args (p %% 4 == 0, R %% p == 0, img 4-byte and out 16-byte aligned)");
-    ECAMP_CHECK_ARG(dtype == ECAMP_F32 || dtype == ECAMP_BF16, "im2col_u8: dtype %d", dtype);
-    const long n = B * (Lk + 1) * (long)(p * p / 4);
-    const int nb = (int)std::min<long>((n + 255) / 256, 8192);
-    if (dtype == ECAMP_F32) hipLaunchKernelGGL(im2col_u8_kernel<float>, dim3(nb), dim3(256), 0, stream, img, lut, ids_keep, (float*)out, (long)B, Lk, R, p);
-    else hipLaunchKernelGGL(im2col_u8_kernel<bf16_t>, dim3(nb), dim3(256), 0, stream, img, lut, ids_keep, (bf16_t*)out, (long)B, Lk, R, p);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    const dim3 grid = flat_grid(B * (Lk + 1) * (long)(p * p / 4), 8192);
+    return ECAMP_LAUNCH_TYPED("im2col_u8", dtype, [&](auto tag) {
+        typedef ECAMP_TAG_T(tag) T;
+        hipLaunchKernelGGL(im2col_u8_kernel<T>, grid, dim3(256), 0, stream, img, lut, ids_keep, (T*)out, (long)B, Lk, R, p);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
-// K2b/K4  in place on the patch-embed GEMM output x[B, Lk+1, D]:
-//      x[b,0,:] = cls + pos[0] ;  x[b,t,:] += pos[1 + ids_keep[b,t-1]]     (model_ecamp.py:222,228-230)
+// K2b/K4  on the patch-embed GEMM output x[B, Lk+1, D], into out[B, Lk+1, D]:
+//      out[b,0,:] = cls + pos[0] ;  out[b,t,:] = x[b,t,:] + pos[1 + ids_keep[b,t-1]]     (model_ecamp.py:222,228-230)
+// `out` is x itself (ecamp_assemble_tokens, in place) or -- the f32 residual stream, ECAMP(f32_residual=True) -- a separate f32 tensor
+// (ecamp_assemble_tokens_x32: the 16-bit patch embedding plus the f32 tables, autocast's `half conv output + f32 pos_embed -> f32`).
+// A thread reads its vector of x before it writes the same bytes, and nobody else touches them -- hence no __restrict__ on x and out.
 // ---------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void assemble_tokens_kernel(T* __restrict__ x, const float* __restrict__ cls, const float* __restrict__ pos,
+template <typename TI, typename TO>
+__global__ void assemble_tokens_kernel(const TI* x, TO* out, const float* __restrict__ cls, const float* __restrict__ pos,
                                        const int* __restrict__ ids_keep, long B, int Lk, int D4) {
     const int Tt = Lk + 1;
     long n = B * Tt * D4;
@@ -344,61 +328,34 @@ __global__ void assemble_tokens_kernel(T* __restrict__ x, const float* __restric
             ld4<float>(cls + d * 4, v);
             ld4<float>(pos + d * 4, q);
         } else {
-            ld4<T>(x + i * 4, v);
+            ld4<TI>(x + i * 4, v);
             ld4<float>(pos + (long)(1 + ids_keep[b * Lk + t - 1]) * D4 * 4 + d * 4, q);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] += q[r];
-        st4<T>(x + i * 4, v);
+        st4<TO>(out + i * 4, v);
     }
+}
+template <typename TI, typename TO>
+static void assemble_tokens_launch(const void* x, void* out, const float* cls, const float* pos, const int32_t* ids_keep, int64_t B, int32_t Lk, int32_t D,
+                                   hipStream_t stream) {
+    hipLaunchKernelGGL((assemble_tokens_kernel<TI, TO>), flat_grid(B * (Lk + 1) * (long)(D / 4), 8192), dim3(256), 0, stream, (const TI*)x, (TO*)out, cls,
+                       pos, ids_keep, (long)B, Lk, D / 4);
 }
 extern "C" int ecamp_assemble_tokens(void* x, const float* cls, const float* pos, const int32_t* ids_keep, int64_t B, int32_t Lk,
                                      int32_t D, int32_t dtype, hipStream_t stream) {
     ECAMP_CHECK_ARG(x && cls && pos && ids_keep && D % 4 == 0, "assemble_tokens: bad args");
-    long n = B * (Lk + 1) * (long)(D / 4);
-    int nb = (int)((n + 255) / 256);
-    if (nb > 8192) nb = 8192;
-    if (dtype == ECAMP_F32) hipLaunchKernelGGL(assemble_tokens_kernel<float>, dim3(nb), dim3(256), 0, stream, (float*)x, cls, pos, ids_keep, (long)B, Lk, D / 4);
-    else hipLaunchKernelGGL(assemble_tokens_kernel<bf16_t>, dim3(nb), dim3(256), 0, stream, (bf16_t*)x, cls, pos, ids_keep, (long)B, Lk, D / 4);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
-}
-
-// the f32 residual stream (ECAMP(f32_residual=True)): the same tokens into a separate f32 tensor out[B, Lk+1, D] -- the 16-bit patch embedding
-// plus the f32 tables, autocast's `half conv output + f32 pos_embed -> f32` (model_ecamp.py:222,228-230)
-template <typename T>
-__global__ void assemble_tokens_x32_kernel(const T* __restrict__ x, float* __restrict__ out, const float* __restrict__ cls, const float* __restrict__ pos,
-                                           const int* __restrict__ ids_keep, long B, int Lk, int D4) {
-    const int Tt = Lk + 1;
-    long n = B * Tt * D4;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        int d = (int)(i % D4);
-        long row = i / D4;
-        int t = (int)(row % Tt);
-        long b = row / Tt;
-        float v[4], q[4];
-        if (t == 0) {
-            ld4<float>(cls + d * 4, v);
-            ld4<float>(pos + d * 4, q);
-        } else {
-            ld4<T>(x + i * 4, v);
-            ld4<float>(pos + (long)(1 + ids_keep[b * Lk + t - 1]) * D4 * 4 + d * 4, q);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] += q[r];
-        st4<float>(out + i * 4, v);
-    }
+    return ECAMP_LAUNCH_TYPED("assemble_tokens", dtype, [&](auto tag) {
+        typedef ECAMP_TAG_T(tag) T;
+        assemble_tokens_launch<T, T>(x, x, cls, pos, ids_keep, B, Lk, D, stream);
+    });
 }
 extern "C" int ecamp_assemble_tokens_x32(const void* x, float* out, const float* cls, const float* pos, const int32_t* ids_keep, int64_t B, int32_t Lk,
                                          int32_t D, int32_t dtype, hipStream_t stream) {
     ECAMP_CHECK_ARG(x && out && cls && pos && ids_keep && D % 4 == 0, "assemble_tokens_x32: bad args");
     ECAMP_CHECK_ARG(dtype == ECAMP_BF16, "assemble_tokens_x32: 16-bit patch embedding (dtype 1) expected, got %d", dtype);
-    long n = B * (Lk + 1) * (long)(D / 4);
-    int nb = (int)((n + 255) / 256);
-    if (nb > 8192) nb = 8192;
-    hipLaunchKernelGGL(assemble_tokens_x32_kernel<bf16_t>, dim3(nb), dim3(256), 0, stream, (const bf16_t*)x, out, cls, pos, ids_keep, (long)B, Lk, D / 4);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    assemble_tokens_launch<bf16_t, float>(x, out, cls, pos, ids_keep, B, Lk, D, stream);
+    return ecamp_launch_status(__func__);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -406,9 +363,11 @@ extern "C" int ecamp_assemble_tokens_x32(const void* x, float* out, const float*
 //   fwd: xd[b,0] = y[b,0] + dpos[0] ; xd[b,1+j] = (r=ids_restore[b,j]) < Lk ? y[b,1+r] : mask_token) + dpos[1+j]
 //   bwd: dy[b,0] = dxd[b,0] ; dy[b,1+r] = dxd[b, 1+ids_keep[b,r]] ; dmask_token += sum over masked slots
 // ---------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void unshuffle_fwd_kernel(const T* __restrict__ y, const int* __restrict__ ids_restore, const float* __restrict__ mtok,
-                                     const float* __restrict__ dpos, T* __restrict__ xd, long B, int L, int Lk, int D4) {
+// (fwd: T xd for T y, or -- the f32 residual stream -- f32 xd for 16-bit y, autocast's promotion of torch.cat([half, f32 mask tokens]) +
+// f32 table.  y and xd never alias; as assemble_tokens_kernel's x and out they carry no __restrict__, so that the pair is one template.)
+template <typename TI, typename TO>
+__global__ void unshuffle_fwd_kernel(const TI* y, const int* __restrict__ ids_restore, const float* __restrict__ mtok,
+                                     const float* __restrict__ dpos, TO* xd, long B, int L, int Lk, int D4) {
     long n = B * (L + 1) * D4;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         int d = (int)(i % D4);
@@ -421,12 +380,12 @@ __global__ void unshuffle_fwd_kernel(const T* __restrict__ y, const int* __restr
             int r = ids_restore[b * L + t - 1];
             src = r < Lk ? 1 + r : -1;
         }
-        if (src >= 0) ld4<T>(y + ((b * (Lk + 1) + src) * (long)D4 + d) * 4, v);
+        if (src >= 0) ld4<TI>(y + ((b * (Lk + 1) + src) * (long)D4 + d) * 4, v);
         else ld4<float>(mtok + d * 4, v);
         ld4<float>(dpos + ((long)t * D4 + d) * 4, q);
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] += q[r];
-        st4<T>(xd + i * 4, v);
+        st4<TO>(xd + i * 4, v);
     }
 }
 template <typename T>
@@ -448,7 +407,6 @@ __global__ void unshuffle_bwd_kernel(const T* __restrict__ dxd, const int* __res
 template <typename T>
 __global__ __launch_bounds__(256) void masktok_grad_kernel(const T* __restrict__ dxd, const int* __restrict__ ids_restore,
                                                            float* __restrict__ out, long B, int L, int Lk, int D) {
-    __shared__ float sh[8][129];
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const int c0 = blockIdx.x * 128 + tx * 4;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -464,86 +422,45 @@ __global__ __launch_bounds__(256) void masktok_grad_kernel(const T* __restrict__
             for (int r = 0; r < 4; ++r) acc[r] += p[r];
         }
     }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) sh[ty][tx * 4 + r] = acc[r];
-    __syncthreads();
-    if (threadIdx.x < 128) {
-        int c = blockIdx.x * 128 + threadIdx.x;
-        if (c < D) {
-            float t = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) t += sh[j][threadIdx.x];
-            atomicAdd(out + c, t);
-        }
-    }
+    const float t = col_tile_sum(acc);
+    const int c = blockIdx.x * 128 + threadIdx.x;
+    if (threadIdx.x < 128 && c < D) atomicAdd(out + c, t);
+}
+template <typename TI, typename TO>
+static void unshuffle_fwd_launch(const void* y, const int32_t* ids_restore, const float* mask_token, const float* dpos, void* xd, int64_t B, int32_t L,
+                                 int32_t Lk, int32_t D, hipStream_t stream) {
+    hipLaunchKernelGGL((unshuffle_fwd_kernel<TI, TO>), flat_grid(B * (L + 1) * (long)(D / 4), 8192), dim3(256), 0, stream, (const TI*)y, ids_restore,
+                       mask_token, dpos, (TO*)xd, (long)B, L, Lk, D / 4);
 }
 extern "C" int ecamp_unshuffle_fwd(const void* y, const int32_t* ids_restore, const float* mask_token, const float* dpos, void* xd,
                                    int64_t B, int32_t L, int32_t Lk, int32_t D, int32_t dtype, hipStream_t stream) {
     ECAMP_CHECK_ARG(y && ids_restore && mask_token && dpos && xd && D % 4 == 0, "unshuffle_fwd: bad args");
-    long n = B * (L + 1) * (long)(D / 4);
-    int nb = (int)((n + 255) / 256);
-    if (nb > 8192) nb = 8192;
-    if (dtype == ECAMP_F32) hipLaunchKernelGGL(unshuffle_fwd_kernel<float>, dim3(nb), dim3(256), 0, stream, (const float*)y, ids_restore, mask_token, dpos, (float*)xd, (long)B, L, Lk, D / 4);
-    else hipLaunchKernelGGL(unshuffle_fwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, stream, (const bf16_t*)y, ids_restore, mask_token, dpos, (bf16_t*)xd, (long)B, L, Lk, D / 4);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
-}
-// the f32 residual stream: xd f32 = (16-bit decoder_embed output | f32 mask token) + f32 decoder_pos_embed, autocast's promotion of
-// torch.cat([half, f32 mask tokens]) + f32 table (model_ecamp.py:245-251)
-template <typename T>
-__global__ void unshuffle_fwd_x32_kernel(const T* __restrict__ y, const int* __restrict__ ids_restore, const float* __restrict__ mtok,
-                                         const float* __restrict__ dpos, float* __restrict__ xd, long B, int L, int Lk, int D4) {
-    long n = B * (L + 1) * D4;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        int d = (int)(i % D4);
-        long row = i / D4;
-        int t = (int)(row % (L + 1));
-        long b = row / (L + 1);
-        float v[4], q[4];
-        int src = 0;
-        if (t > 0) {
-            int r = ids_restore[b * L + t - 1];
-            src = r < Lk ? 1 + r : -1;
-        }
-        if (src >= 0) ld4<T>(y + ((b * (Lk + 1) + src) * (long)D4 + d) * 4, v);
-        else ld4<float>(mtok + d * 4, v);
-        ld4<float>(dpos + ((long)t * D4 + d) * 4, q);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] += q[r];
-        st4<float>(xd + i * 4, v);
-    }
+    return ECAMP_LAUNCH_TYPED("unshuffle_fwd", dtype, [&](auto tag) {
+        typedef ECAMP_TAG_T(tag) T;
+        unshuffle_fwd_launch<T, T>(y, ids_restore, mask_token, dpos, xd, B, L, Lk, D, stream);
+    });
 }
 extern "C" int ecamp_unshuffle_fwd_x32(const void* y, const int32_t* ids_restore, const float* mask_token, const float* dpos, float* xd,
                                        int64_t B, int32_t L, int32_t Lk, int32_t D, int32_t dtype, hipStream_t stream) {
     ECAMP_CHECK_ARG(y && ids_restore && mask_token && dpos && xd && D % 4 == 0, "unshuffle_fwd_x32: bad args");
     ECAMP_CHECK_ARG(dtype == ECAMP_BF16, "unshuffle_fwd_x32: 16-bit decoder_embed output (dtype 1) expected, got %d", dtype);
-    long n = B * (L + 1) * (long)(D / 4);
-    int nb = (int)((n + 255) / 256);
-    if (nb > 8192) nb = 8192;
-    hipLaunchKernelGGL(unshuffle_fwd_x32_kernel<bf16_t>, dim3(nb), dim3(256), 0, stream, (const bf16_t*)y, ids_restore, mask_token, dpos, xd, (long)B, L, Lk, D / 4);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    unshuffle_fwd_launch<bf16_t, float>(y, ids_restore, mask_token, dpos, xd, B, L, Lk, D, stream);
+    return ecamp_launch_status(__func__);
 }
 extern "C" int ecamp_unshuffle_bwd(const void* dxd, const int32_t* ids_restore, const int32_t* ids_keep, void* dy,
                                    float* dmask_token, int64_t B, int32_t L, int32_t Lk, int32_t D, int32_t dtype,
                                    hipStream_t stream) {
     ECAMP_CHECK_ARG(dxd && ids_restore && ids_keep && dy && dmask_token && D % 4 == 0, "unshuffle_bwd: bad args");
-    long n = B * (Lk + 1) * (long)(D / 4);
-    int nb = (int)((n + 255) / 256);
-    if (nb > 8192) nb = 8192;
+    const dim3 grid = flat_grid(B * (Lk + 1) * (long)(D / 4), 8192);
     int nbx = ceil_div(D, 128), nby = ceil_div(B * L, 8 * 16);
     int cap = 1024 / nbx;
     if (nby > cap) nby = cap;
     if (nby < 1) nby = 1;
-    if (dtype == ECAMP_F32) {
-        hipLaunchKernelGGL(unshuffle_bwd_kernel<float>, dim3(nb), dim3(256), 0, stream, (const float*)dxd, ids_keep, (float*)dy, (long)B, L, Lk, D / 4);
-        hipLaunchKernelGGL(masktok_grad_kernel<float>, dim3(nbx, nby), dim3(256), 0, stream, (const float*)dxd, ids_restore, dmask_token, (long)B, L, Lk, D);
-    } else {
-        hipLaunchKernelGGL(unshuffle_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, stream, (const bf16_t*)dxd, ids_keep, (bf16_t*)dy, (long)B, L, Lk, D / 4);
-        hipLaunchKernelGGL(masktok_grad_kernel<bf16_t>, dim3(nbx, nby), dim3(256), 0, stream, (const bf16_t*)dxd, ids_restore, dmask_token, (long)B, L, Lk, D);
-    }
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    return ECAMP_LAUNCH_TYPED("unshuffle_bwd", dtype, [&](auto tag) {
+        typedef ECAMP_TAG_T(tag) T;
+        hipLaunchKernelGGL(unshuffle_bwd_kernel<T>, grid, dim3(256), 0, stream, (const T*)dxd, ids_keep, (T*)dy, (long)B, L, Lk, D / 4);
+        hipLaunchKernelGGL(masktok_grad_kernel<T>, dim3(nbx, nby), dim3(256), 0, stream, (const T*)dxd, ids_restore, dmask_token, (long)B, L, Lk, D);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -583,13 +500,11 @@ __global__ __launch_bounds__(256) void unpatchify_mim_kernel(const T* __restrict
 extern "C" int ecamp_unpatchify_mim(const void* pred, const float* imgs, const float* mask, float* pred_img, float* loss_sum,
                                     int64_t B, int32_t R, int32_t p, int32_t dtype, hipStream_t stream) {
     ECAMP_CHECK_ARG(pred && imgs && mask && pred_img && loss_sum, "unpatchify_mim: bad args");
-    long n = B * (long)R * R;
-    int nb = (int)((n + 255) / 256);
-    if (nb > 4096) nb = 4096;
-    if (dtype == ECAMP_F32) hipLaunchKernelGGL(unpatchify_mim_kernel<float>, dim3(nb), dim3(256), 0, stream, (const float*)pred, imgs, mask, pred_img, loss_sum, (long)B, R, p);
-    else hipLaunchKernelGGL(unpatchify_mim_kernel<bf16_t>, dim3(nb), dim3(256), 0, stream, (const bf16_t*)pred, imgs, mask, pred_img, loss_sum, (long)B, R, p);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    return ECAMP_LAUNCH_TYPED("unpatchify_mim", dtype, [&](auto tag) {
+        typedef ECAMP_TAG_T(tag) T;
+        hipLaunchKernelGGL(unpatchify_mim_kernel<T>, flat_grid(B * (long)R * R, 4096), dim3(256), 0, stream, (const T*)pred, imgs, mask, pred_img, loss_sum,
+                           (long)B, R, p);
+    });
 }
 
 // d_pred[b, t, :] (T, incl. a zero cls row) = gm * mask * (pred_img - imgs) + gs * dsr    (patchify of the image-space gradient)
@@ -624,13 +539,11 @@ extern "C" int ecamp_img_loss_bwd(const float* pred_img, const float* imgs, cons
                                   const float* gm_gs, void* dpred, int64_t B, int32_t R, int32_t p, int32_t dtype,
                                   hipStream_t stream) {
     ECAMP_CHECK_ARG(pred_img && imgs && mask && dsr && gm_gs && dpred, "img_loss_bwd: bad args");
-    long n = B * (long)((R / p) * (R / p) + 1) * p * p;
-    int nb = (int)((n + 255) / 256);
-    if (nb > 4096) nb = 4096;
-    if (dtype == ECAMP_F32) hipLaunchKernelGGL(img_loss_bwd_kernel<float>, dim3(nb), dim3(256), 0, stream, pred_img, imgs, mask, dsr, gm_gs, (float*)dpred, (long)B, R, p);
-    else hipLaunchKernelGGL(img_loss_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, stream, pred_img, imgs, mask, dsr, gm_gs, (bf16_t*)dpred, (long)B, R, p);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    const dim3 grid = flat_grid(B * (long)((R / p) * (R / p) + 1) * p * p, 4096);
+    return ECAMP_LAUNCH_TYPED("img_loss_bwd", dtype, [&](auto tag) {
+        typedef ECAMP_TAG_T(tag) T;
+        hipLaunchKernelGGL(img_loss_bwd_kernel<T>, grid, dim3(256), 0, stream, pred_img, imgs, mask, dsr, gm_gs, (T*)dpred, (long)B, R, p);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1629,7 +1542,6 @@ __global__ void scaled_accum_kernel(const float* __restrict__ ws, float* __restr
 }
 extern "C" int ecamp_scaled_accum(const float* ws, float* grad, const float* scale_dev, int32_t idx, int32_t n, hipStream_t stream) {
     ECAMP_CHECK_ARG(ws && grad && scale_dev && n > 0, "scaled_accum: bad args");
-    hipLaunchKernelGGL(scaled_accum_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, ws, grad, scale_dev, idx, n);
-    ECAMP_LAUNCH_CHECK();
-    return 0;
+    hipLaunchKernelGGL(scaled_accum_kernel, flat_grid(n, INT32_MAX), dim3(256), 0, stream, ws, grad, scale_dev, idx, n);   // (no stride loop: no cap)
+    return ecamp_launch_status(__func__);
 }

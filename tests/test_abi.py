@@ -90,6 +90,13 @@ def test_argument_errors_are_reported_without_a_device(lib):
     st = (ctypes.c_int64 * 3)(64, 64, 64)
     rc = lib.ecamp_attn_fwd(one, one, one, one, one, None, 1, 1, 8, 300, 48, st, st, st, st, 1.0, 0.0, 0, 0, 0, None, None)
     assert rc < 0 and b"head_dim 48" in lib.ecamp_last_error()  # (Tk > 256 in f32 is served by the long-key kernels since round 2)
+    # the flat entries check their pointers before they look at the dtype code (tests/test_flat_kernels_gpu.py: the dtype refusal itself)
+    rc = lib.ecamp_add(None, None, None, 4, 2, None)
+    assert rc < 0 and b"ecamp_add: bad args" in lib.ecamp_last_error()
+    rc = lib.ecamp_assemble_tokens(None, None, None, None, 1, 1, 4, 2, None)
+    assert rc < 0 and b"assemble_tokens: bad args" in lib.ecamp_last_error()
+    rc = lib.ecamp_unshuffle_bwd(None, None, None, None, None, 1, 1, 1, 4, -1, None)
+    assert rc < 0 and b"unshuffle_bwd: bad args" in lib.ecamp_last_error()
 
 
 def test_product_never_imports_the_oracle():
