@@ -928,3 +928,16 @@ def resample_boxes_rgb_u8(flat, table, out_t, out, kmax, tmp_rows, max_h, ws, er
     3 h intermediate rows from row0; else one plane), tmp_rows / max_h count c * h.  Three planes through the same taps, then Pillow's
     convert("L") -- byte for byte Grayscale after the resize of the RGB image; a one-plane sample gets `resample_boxes_u8`'s byte."""
     return _resample("ecamp_resample_boxes_rgb_u8", 10, flat, table, out_t, out, kmax, tmp_rows, max_h, ws, err, filter)
+
+
+def resample_shard_u8(shard, table, out_t, out, kmax, tmp_rows, max_h, ws, err, filter=BILINEAR):
+    """`resample_boxes_rgb_u8` on a shard that stays in device memory: `shard` is the whole uploaded file (flat uint8), table int64 [B, 12] =
+    the stride-10 row + (pitch, plane_pitch) of the stored image, `off` the byte offset in `shard` of the box's first pixel -- the boxes are
+    read where they lie.  A row that points outside `shard` gives a sample of zeros and ORs 2 into `err` (1: more than `kmax` taps)."""
+    _chk(shard, table, out_t, ws, err)
+    assert shard.dtype == torch.uint8 and shard.dim() == 1 and shard.is_contiguous()
+    assert table.dtype == torch.int64 and table.is_contiguous() and table.shape[1] == 12
+    assert out_t.dtype == torch.uint8 and out_t.is_contiguous() and tuple(out_t.shape) == (table.shape[0], out, out)
+    call("ecamp_resample_shard_u8", ptr(shard), shard.numel(), ptr(table), ptr(out_t), table.shape[0], int(out), int(kmax), int(tmp_rows), int(max_h), int(filter),
+         ptr(ws), ws.numel(), ptr(err), stream())
+    return out_t

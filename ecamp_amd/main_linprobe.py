@@ -10,7 +10,8 @@ ECAMP/Fine-tuning/Classification (run_lp.sh), on one MI355X:
 The reference's flag names are kept.  Added: --list_dir (the reference hard-codes ./datasets/<task>), --compute_dtype {bf16,fp16,fp32}
 (--fp16 is --compute_dtype fp16; --fp16_opt_level is accepted and ignored), --pool {avg,cls}, --f32_residual, --synthetic,
 --synthetic_len, --num_workers, --print_freq, --image_shard_dir (the image pipeline on the device, over pre-decoded uint8 shards; see its
-help), --drop_path_rate (main_finetune's stochastic depth; refused here unless 0: the frozen
+help), --image_shard_resident / --image_shard_resident_max_gb (keep those shards in device memory: workers then send table rows, no pixels),
+--drop_path_rate (main_finetune's stochastic depth; refused here unless 0: the frozen
 encoder of the probe is deterministic), --train_pos_embed (main_finetune's trained position table; refused here), --fp16_loss_scale (main_finetune's loss scale of IEEE-half
 fine-tuning; ignored here: the head and its gradient are f32).  `--stage train` trains, then tests the best checkpoint, as the reference does.
 
@@ -87,6 +88,14 @@ def get_args_parser():
                         "host transforms.  Colour sources (Aptos, ODIR5K, MURED): make the shards with --colour; a colour shard is recognised from "
                         "its index, its colour images travel as three planes and the device folds them to luma behind the resample, as "
                         "Grayscale after the resize does (without --colour the tool ends at the first colour image)")
+    p.add_argument("--image_shard_resident", action="store_true",
+                   help="with --image_shard_dir: upload the shard of every split this run reads into device memory once, when its loader is "
+                        "built, and resample each crop box where it lies in the stored image; a loader worker then sends one table row per "
+                        "sample and no pixels.  The same bytes as without the flag.  A shard must fit in half of the memory that is free when "
+                        "it is uploaded (or in --image_shard_resident_max_gb); one that does not ends the run with a message.  "
+                        "Classification shards only: pre-training's --image_shard is not covered")
+    p.add_argument("--image_shard_resident_max_gb", type=float, default=None, metavar="N",
+                   help="with --image_shard_resident: a shard may hold at most N GB (10^9 bytes), in place of the one-half rule")
     return p
 
 
@@ -121,6 +130,15 @@ def check_common(args):
     shard_dir = getattr(args, "image_shard_dir", "")
     if shard_dir and args.synthetic:
         raise SystemExit("--image_shard_dir with --synthetic: the synthetic stand-in reads no images, there is nothing to resample on the device")
+    if getattr(args, "image_shard_resident", False):
+        if args.synthetic:
+            raise SystemExit("--image_shard_resident with --synthetic: the synthetic stand-in reads no images, there is no shard to keep on the device")
+        if not shard_dir:
+            raise SystemExit("--image_shard_resident needs --image_shard_dir DIR: it keeps the shards of DIR in device memory")
+    elif getattr(args, "image_shard_resident_max_gb", None) is not None:
+        raise SystemExit("--image_shard_resident_max_gb without --image_shard_resident: there is no resident shard to limit")
+    if getattr(args, "image_shard_resident_max_gb", None) is not None and not args.image_shard_resident_max_gb > 0:
+        raise SystemExit("--image_shard_resident_max_gb must be positive, got %g" % args.image_shard_resident_max_gb)
     if not args.synthetic and not args.dataset_path and not shard_dir:   # (the shards hold the images: --dataset_path is then not read)
         raise SystemExit("--dataset_path is required (or --synthetic)")
     if not args.list_dir:
@@ -148,12 +166,38 @@ def build_model(args):
                             f32_residual=args.f32_residual)
 
 
-def build_loader(args, split):
+def resident_max_bytes(args):
+    gb = getattr(args, "image_shard_resident_max_gb", None)
+    return None if gb is None else int(gb * 1e9)
+
+
+def check_resident_shards(args, device):
+    """`--image_shard_resident`: refuse a shard that does not fit before the model is built (each is checked again when it is uploaded)."""
+    from .module import finetune_datasets as fd
+    for split in (("train", "val", "test") if args.stage == "train" else ("test",)):
+        try:
+            fd.ResidentShard.check_fits(fd.shard_path(args.image_shard_dir, split, args.data_volume), device, resident_max_bytes(args))
+        except MemoryError as e:
+            raise SystemExit("--image_shard_resident, %s split: %s" % (split, e))
+
+
+def build_loader(args, split, log=print):
     from torch.utils.data import DataLoader
 
     from .module import finetune_datasets as fd
     train = split == "train"
     batch_size = args.train_batch_size if train else args.eval_batch_size
+    if getattr(args, "image_shard_dir", "") and getattr(args, "image_shard_resident", False):
+        ds = fd.ShardListDataset(args.image_shard_dir, args.list_dir, split, data_volume=args.data_volume, img_size=args.img_size, ratio=args.ratio,
+                                 resident=True)
+        print("%s set: %d samples (image shard %s)" % (split, len(ds), ds.shard_path))
+        try:
+            shard = fd.ResidentShard(ds.shard_path, torch.device("cuda"), resident_max_bytes(args))
+        except MemoryError as e:
+            raise SystemExit("--image_shard_resident, %s split: %s" % (split, e))
+        log("%s set: image shard %s resident on the device: %d bytes uploaded in %.3f s" % (split, shard.path, shard.nbytes, shard.seconds))
+        loader = DataLoader(ds, shuffle=train, batch_size=batch_size, num_workers=args.num_workers, pin_memory=True, collate_fn=fd.collate_resident)
+        return fd.DeviceImageLoader(loader, torch.device("cuda"), args.img_size, shard=shard)
     if getattr(args, "image_shard_dir", ""):
         ds = fd.ShardListDataset(args.image_shard_dir, args.list_dir, split, data_volume=args.data_volume, img_size=args.img_size, ratio=args.ratio)
         print("%s set: %d samples (image shard %s)" % (split, len(ds), ds.shard_path))
@@ -191,6 +235,8 @@ def run(args, engine, build_model, count_parameters, opening, eval_mode=False):
         log(line)
     if getattr(args, "image_shard_dir", ""):
         log(IMAGE_PIPELINE_LINE % args.image_shard_dir)
+    if getattr(args, "image_shard_resident", False):
+        check_resident_shards(args, device)
     if args.stage == "train":
         writer = None
         try:
@@ -205,7 +251,7 @@ def run(args, engine, build_model, count_parameters, opening, eval_mode=False):
         model.to(device)
         log("Training parameters %s" % args)
         log("Total Parameter: \t%2.4fM" % (count_parameters(model) / 1e6))
-        engine.train(model, build_loader(args, "train"), build_loader(args, "val"), args, log=log, writer=writer)
+        engine.train(model, build_loader(args, "train", log), build_loader(args, "val", log), args, log=log, writer=writer)
         if writer is not None:
             writer.close()
         del model
@@ -218,7 +264,7 @@ def run(args, engine, build_model, count_parameters, opening, eval_mode=False):
     model.to(device)
     if eval_mode:
         model.eval()
-    return engine.test(model, build_loader(args, "test"), args, log=log)
+    return engine.test(model, build_loader(args, "test", log), args, log=log)
 
 
 def main(args):

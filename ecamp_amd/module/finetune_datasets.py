@@ -262,23 +262,121 @@ def collate_boxes(batch):
     return flat, table, meta, torch.stack([y for _, y in batch])
 
 
+# ---- the shard in device memory (csrc/augment.hip: ecamp_resample_shard_u8) ---------------------------------------------------------------
+# A classification shard is small beside the device's memory and never changes, yet the path above sends every box's bytes through a
+# worker's shared memory, the pinning thread and PCIe again in every epoch.  `ResidentShard` uploads the file once; a worker then draws the
+# same box from the index row alone and sends twelve numbers, and the device reads the box where it lies in the stored image (two pitches
+# more per row).  The transforms and their bytes are the ones above.  Pre-training's `--image_shard` is not covered: MIMIC-CXR does not fit.
+def resident_item(index_row, train, img_size, ratio=1.0):
+    """`device_train_item` / `device_eval_item` on an index row (byte offset, H, W[, C]) instead of the image: the same torch-RNG calls in
+    the same order (training), `eval_geometry` (evaluation) -> int64 [12], the row of ecamp_resample_shard_u8 but for column 4 (the first
+    intermediate row, which `pack_resident` fills): off of the box's first pixel, h, w, flip, 0, full_w, shift_w, full_h, shift_h, C, pitch =
+    W, plane_pitch = H W."""
+    off, H, W = (int(v) for v in index_row[:3])
+    c = int(index_row[3]) if len(index_row) > 3 else 1
+    if train:
+        i, j, h, w = random_resized_crop_params(W, H, scale=(0.08, 1.0))
+        flip = random_flip()
+        geometry = (int(img_size), 0, int(img_size), 0)
+    else:
+        i, j, h, w, flip = 0, 0, H, W, False
+        geometry = eval_geometry(W, H, img_size, ratio)
+    return np.array((off + i * W + j, h, w, int(flip), 0) + geometry + (3 if c == 3 else 0, W, H * W), dtype=np.int64)
+
+
+def pack_resident(items, pin=False):
+    """Batch of `resident_item` rows -> (int64 table [B, 12] for ecamp_resample_shard_u8, meta): columns 1 to 9 and meta are `pack_boxes`' on
+    the same items -- the first intermediate rows are the prefix sum of c h, meta = (tap count, sum of c h, largest c h[, True: a colour
+    sample is present])."""
+    table = torch.zeros((len(items), 12), dtype=torch.int64, pin_memory=pin)
+    ta = table.numpy()
+    row = max_h = 0
+    kmax = 3
+    colour = False
+    for n, r in enumerate(items):
+        ta[n] = r
+        ta[n, 4] = row
+        h, w, planes = int(r[1]), int(r[2]), (3 if r[9] == 3 else 1)
+        colour = colour or planes == 3
+        kmax = max(kmax, bilinear_taps(w, r[5]), bilinear_taps(h, r[7]))
+        row += planes * h
+        max_h = max(max_h, planes * h)
+    return table, ((kmax, row, max_h, True) if colour else (kmax, row, max_h))
+
+
+def collate_resident(batch):
+    """collate_fn of `ShardListDataset(resident=True)`: [(row, labels)] -> (table, meta, labels [B, k])."""
+    table, meta = pack_resident([item for item, _ in batch])
+    return table, meta, torch.stack([y for _, y in batch])
+
+
+class ResidentShard:
+    """A shard file (`U8ShardWriter`) uploaded once into ONE device uint8 tensor (`tensor`, `nbytes`), in chunks through a reused pinned
+    staging buffer -- no whole-file host copy; the index stays on the host (`index`).  Refuses, before anything is allocated, a file that
+    does not fit: `fits`.  `seconds`: what the upload took."""
+
+    FREE_DIVISOR = 2          # without a limit of the caller's, a shard may take 1 / FREE_DIVISOR of the memory that is free when it is uploaded
+    CHUNK_BYTES = 64 << 20    # the staging buffer
+
+    @staticmethod
+    def fits(nbytes, free_bytes, max_bytes=None):
+        return nbytes <= max_bytes if max_bytes is not None else nbytes <= free_bytes // ResidentShard.FREE_DIVISOR
+
+    @classmethod
+    def check_fits(cls, path, device, max_bytes=None):
+        """-> the file's size; raises MemoryError with the whole story if `fits` says no.  Allocates nothing."""
+        nbytes = os.path.getsize(path)
+        torch.cuda.empty_cache()   # what a released shard held is free again
+        free = int(torch.cuda.mem_get_info(device)[0])
+        if not cls.fits(nbytes, free, max_bytes):
+            limit = ("the limit given (--image_shard_resident_max_gb) is %d bytes" % max_bytes if max_bytes is not None
+                     else "the limit is 1/%d of the free memory, %d bytes" % (cls.FREE_DIVISOR, free // cls.FREE_DIVISOR))
+            raise MemoryError("image shard %s holds %d bytes and does not fit in device memory: %d bytes are free, %s.  The run works without "
+                              "--image_shard_resident (the boxes then travel from the host in every pass)" % (path, nbytes, free, limit))
+        return nbytes
+
+    def __init__(self, path, device, max_bytes=None):
+        import time
+        self.path, self.device = path, torch.device(device)
+        self.nbytes = self.check_fits(path, self.device, max_bytes)
+        t0 = time.time()
+        self.index = np.load(path + ".idx.npy")
+        self.tensor = torch.empty((self.nbytes,), dtype=torch.uint8, device=self.device)
+        if self.nbytes:
+            data = np.memmap(path, dtype=np.uint8, mode="r")
+            stage = torch.empty((min(self.nbytes, self.CHUNK_BYTES),), dtype=torch.uint8, pin_memory=True)
+            for a in range(0, self.nbytes, stage.numel()):
+                n = min(stage.numel(), self.nbytes - a)
+                stage.numpy()[:n] = data[a:a + n]
+                self.tensor[a:a + n].copy_(stage[:n])   # blocking: the staging buffer is free again when it returns
+            del data, stage
+        self.seconds = time.time() - t0
+
+
 class ShardListDataset(Dataset):
     """The labels of `<list_dir>/<list of the split>` over the shard that holds the list's images in list order
     (`<shard_dir>/<list file name>.u8`, tools/make_image_shard.py --list_dir): (`device_train_item` or `device_eval_item`, labels)."""
 
-    def __init__(self, shard_dir, list_dir, split, data_volume=None, img_size=224, ratio=1.0):
+    def __init__(self, shard_dir, list_dir, split, data_volume=None, img_size=224, ratio=1.0, resident=False):
+        """resident: the shard's bytes live in device memory (`ResidentShard`) -- an item is then `resident_item`'s table row instead of a
+        box's bytes, made from the index alone: the file is never mapped here."""
         from .pretrain_datasets import U8ShardReader
-        self.split, self.img_size, self.ratio = split, int(img_size), ratio
+        self.split, self.img_size, self.ratio, self.resident = split, int(img_size), ratio, bool(resident)
         self.list_path = os.path.join(list_dir, list_file(split, data_volume))
         self.shard_path = shard_path(shard_dir, split, data_volume)
         check_shard(self.shard_path, self.list_path)
         _, self.labels = read_list(self.list_path)
-        self.shard = U8ShardReader(self.shard_path)
+        if self.resident:
+            self.shard, self.index = None, np.load(self.shard_path + ".idx.npy")
+        else:
+            self.shard = U8ShardReader(self.shard_path)
 
     def __len__(self):
         return len(self.labels)
 
     def __getitem__(self, index):
+        if self.resident:
+            return resident_item(self.index[index], self.split == "train", self.img_size, self.ratio), torch.FloatTensor(self.labels[index])
         img = self.shard[index]
         item = device_train_item(img, self.img_size) if self.split == "train" else device_eval_item(img, self.img_size, self.ratio)
         return item, torch.FloatTensor(self.labels[index])
@@ -303,26 +401,49 @@ def check_shard(path, list_path):
 class DeviceBoxResampler(DeviceResampler):
     """boxes (flat uint8 + table [B, 10] + meta, host or device) -> uint8 [B, size, size] on the device: the classification transforms'
     resample (+ flip), Pillow-exact (ecamp_resample_boxes_u8, BILINEAR; ecamp_resample_boxes_rgb_u8 -- three planes, then Grayscale -- when
-    meta's fourth field says the batch holds a colour sample)."""
+    meta's fourth field says the batch holds a colour sample).  With a `ResidentShard` in place of the flat bytes and a table [B, 12]
+    (`pack_resident`): ecamp_resample_shard_u8 on the shard's tensor -- the same bytes, no box travels."""
 
     def __call__(self, flat, table, meta, check=False):
         from .. import hip_ops as ops
         kmax, rows, max_h = (int(v) for v in meta[:3])
+        if isinstance(flat, ResidentShard):   # table [B, 12]: the boxes are read where they lie in the uploaded shard
+            out = self.run(ops.resample_shard_u8, ops.resample_boxes_workspace_bytes, "box", flat.tensor, table, kmax, rows, max_h, False)
+            if check:
+                self.raise_on_err(flat)
+            return out
         op = ops.resample_boxes_rgb_u8 if len(meta) > 3 and meta[3] else ops.resample_boxes_u8   # filter: their default, BILINEAR
         return self.run(op, ops.resample_boxes_workspace_bytes, "box", flat, table, kmax, rows, max_h, check)
+
+    def raise_on_err(self, shard):
+        """Read the flag of the resident calls made so far (one 4-byte read, a host synchronisation), clear it, and raise if it is set."""
+        v = int(self.err.item())
+        if v == 0:
+            return
+        self.err.zero_()
+        said = [text for bit, text in ((1, "a box needed more taps than the table was sized for (1)"),
+                                       (2, "a table row pointed outside the resident shard; its sample was zeros (2)")) if v & bit]
+        raise RuntimeError("ecamp_resample_shard_u8 on %s: err_flag = %d: %s" % (shard.path, v, "; ".join(said)))
 
 
 class DeviceImageLoader:
     """A DataLoader over a `ShardListDataset` (collate_fn=collate_boxes) -> (uint8 [B, R, R] on the device, labels): what
-    engine_linprobe's loops iterate, the image being the bytes `ECAMPClassifier` normalises in its stem."""
+    engine_linprobe's loops iterate, the image being the bytes `ECAMPClassifier` normalises in its stem.
+    shard: the `ResidentShard` of a `ShardListDataset(resident=True)` (collate_fn=collate_resident) -- the loader then yields table rows
+    alone, the boxes are read from the shard in device memory, and the end of every pass reads the calls' error flag once."""
 
-    def __init__(self, loader, device, img_size):
-        self.loader, self.dataset = loader, loader.dataset
+    def __init__(self, loader, device, img_size, shard=None):
+        self.loader, self.dataset, self.shard = loader, loader.dataset, shard
         self.resample = DeviceBoxResampler(device, img_size)
 
     def __len__(self):
         return len(self.loader)
 
     def __iter__(self):
+        if self.shard is not None:
+            for table, meta, y in self.loader:
+                yield self.resample(self.shard, table, meta), y
+            self.resample.raise_on_err(self.shard)   # once per pass: nothing else on the training path reads the flag
+            return
         for flat, table, meta, y in self.loader:
             yield self.resample(flat, table, meta), y

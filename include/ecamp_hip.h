@@ -30,7 +30,8 @@ typedef struct ihipStream_t* ecampStream_t; /* == hipStream_t */
  * returns the value the library was BUILT with; a consumer compares it with the header it was compiled against -- the Python binding
  * (ecamp_amd/_lib.py) refuses a library of another version, which is what protects an A/B of two builds (ECAMP_LIB, tools/ab_lib.sh)
  * from calling an older build with a newer argument list.  ecamp_ce_eval -- and later ecamp_drop_path_fwd / ecamp_drop_path_bwd, ecamp_pos_embed_grad,
- * ecamp_resample_boxes_u8 (+ its workspace function), ecamp_im2col_u8, ecamp_resample_boxes_rgb_u8 and ecamp_layernorm_layout -- were
+ * ecamp_resample_boxes_u8 (+ its workspace function), ecamp_im2col_u8, ecamp_resample_boxes_rgb_u8, ecamp_layernorm_layout and
+ * ecamp_resample_shard_u8 -- were
  * ADDED at version 5 without touching an existing signature: a build that lacks them is refused by the binding all the same, which
  * resolves every declared symbol when it loads. */
 #define ECAMP_ABI_VERSION 5
@@ -253,7 +254,7 @@ int ecamp_assemble_tokens_x32(const void* x, float* out, const float* cls, const
  * first row of the sample in the intermediate (prefix sum of h), 0}; kmax >= the tap count of the batch's largest scale factor
  * (2 * ceil(2 * max(1, size / out)) + 1); tmp_rows = sum of h; max_h = largest h; ws from ecamp_resample_crops_workspace_bytes;
  * err_flag: int32 on the device, set to 1 if a sample needs more than kmax taps (the result is then undefined).  B <= 65535, out <= 512.
- * The three resample entry points share one launch path and one workspace layout; the boxes forms add a table copy at its end. */
+ * The four resample entry points share one launch path and one workspace layout; the boxes forms add a table copy at its end. */
 int64_t ecamp_resample_crops_workspace_bytes(int64_t B, int32_t out, int32_t kmax, int64_t tmp_rows);
 int ecamp_resample_crops_u8(const uint8_t* src, const int64_t* table, uint8_t* dst, int64_t B, int32_t out, int32_t kmax, int64_t tmp_rows,
                             int32_t max_h, void* ws, int64_t ws_bytes, int32_t* err_flag, ecampStream_t stream);
@@ -276,6 +277,19 @@ int ecamp_resample_boxes_u8(const uint8_t* src, const int64_t* table, uint8_t* d
  * ecamp_resample_boxes_workspace_bytes; both filters; the same argument checks and err_flag. */
 int ecamp_resample_boxes_rgb_u8(const uint8_t* src, const int64_t* table, uint8_t* dst, int64_t B, int32_t out, int32_t kmax, int64_t tmp_rows,
                                 int32_t max_h, int32_t filter, void* ws, int64_t ws_bytes, int32_t* err_flag, ecampStream_t stream);
+/* ecamp_resample_boxes_rgb_u8 on a shard that STAYS in device memory: `shard` is the whole uploaded file of `shard_bytes` bytes and every
+ * box is read where it lies in its stored image -- no box is copied.  table int64 [B, 12] on the device = the stride-10 row of
+ * ecamp_resample_boxes_rgb_u8 (column 9: the plane count c) + {pitch, plane_pitch}: pitch = bytes between two rows of the stored image (its
+ * width W), plane_pitch = bytes between two of its planes (H * W); `off` = byte offset in `shard` of the box's first pixel in plane 0 (image
+ * offset + y0 * W + x0), row r of plane p of the box starts at off + p * plane_pitch + r * pitch.  Everything else as
+ * ecamp_resample_boxes_rgb_u8 (both filters, full / shift, flip, the luma fold, tmp_rows / max_h counting c * h, kmax, B <= 65535,
+ * out <= 512, ws from ecamp_resample_boxes_workspace_bytes); with pitch = w, plane_pitch = h * w and a packed source: that function's bytes.
+ * Every row is checked on the device before a byte is read: h > 0, w > 0, pitch >= w, off >= 0, plane_pitch >= 0 and
+ * off + (c - 1) * plane_pitch + (h - 1) * pitch + w <= shard_bytes.  A row that fails reads nothing, its sample is all zeros, and 2 is ORed
+ * into err_flag (1 keeps its meaning: more than kmax taps).  Added at version 5 without touching an existing signature. */
+int ecamp_resample_shard_u8(const uint8_t* shard, int64_t shard_bytes, const int64_t* table, uint8_t* dst, int64_t B, int32_t out,
+                            int32_t kmax, int64_t tmp_rows, int32_t max_h, int32_t filter, void* ws, int64_t ws_bytes,
+                            int32_t* err_flag, ecampStream_t stream);
 /* ecamp_im2col_gather straight from a uint8 grayscale image [B, R, R] at the model's own size: out [B * (Lk + 1), 3 * p * p] (f32 or the
  * build's 16-bit format), the cls row zero, the three channel slabs the same values lut[byte] -- bit for bit ecamp_im2col_gather on
  * lut[img] expanded to three planes (lut as in ecamp_bicubic_resize_u8, built from the caller's mean / std). */

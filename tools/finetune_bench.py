@@ -54,6 +54,15 @@ profiles/finetune_image_pipeline_colour.txt (`--image_pipeline_colour_out`):
   16 `ecamp_resample_boxes_rgb_u8` on B three-plane training crops of 1024 x 1024 sources with three different planes, beside
      `ecamp_resample_boxes_u8` on the first planes of the same boxes (the boxes of leg 13: the same seed draws them), alternating in one loop.
   17 leg 15 over colour PNG files and a colour shard (`U8ShardWriter(colour=True)`); `--loader_images 0` skips it.
+
+`--image_pipeline --resident` measures the shard kept in device memory (`--image_shard_resident`) on gray sources and then on colour ones
+(`--colour`: colour alone) and writes profiles/finetune_image_resident.txt (`--image_resident_out`):
+
+  (a) `ecamp_resample_shard_u8` on boxes read where they lie in the resident images beside `ecamp_resample_boxes_u8` / `_rgb_u8` on the same
+      boxes packed, alternating in groups inside one process; medians, the packed call's own spread, the verdict by leg 14's rule -- once with
+      the same batch in every call, once with batches in rotation whose box bytes (`--resident_fresh_mb`) exceed the 256 MB Infinity Cache.
+  (b) the resident loader beside the device loader of leg 15 / 17 on the same shard and list, `--loader_workers` workers each, passes after
+      the first; the fine-tune step's rate on a uint8 batch is taken in the same process, and a loader FEEDS a step by leg 15's rule.
 """
 import argparse
 import os
@@ -587,6 +596,164 @@ def image_pipeline_colour_leg(args, say):
         shutil.rmtree(root, ignore_errors=True)
 
 
+def image_resident_leg(args, say):
+    """Legs (a) and (b) of `--image_pipeline --resident` (see the module docstring)."""
+    import shutil
+    import tempfile
+
+    import numpy as np
+    from torch.utils.data import DataLoader
+
+    from ecamp_amd import engine_finetune
+    from ecamp_amd.module import finetune_datasets as fd
+    from ecamp_amd.module.classifier import build_classifier
+    from ecamp_amd.module.pretrain_datasets import U8ShardWriter
+    dev = torch.device("cuda")
+    C, R, S = args.classes, 224, args.resident_source
+    batches = [int(b) for b in args.batches.split(",")]
+    N, W, rep = args.loader_images, args.loader_workers, args.loader_repeat
+    say("classification image shards resident in HBM (--image_shard_resident), on %s: R = %d, sources %d x %d, training crop scales 0.08 to 1"
+        % (torch.cuda.get_device_name(0), R, S, S))
+    rng = np.random.default_rng(0)
+    base = [np.clip(127 + 80 * np.sin(np.add.outer(np.arange(S) / (5.0 + k), np.arange(S) / (9.0 - k))) + rng.integers(-30, 31, (S, S)), 0, 255).astype(np.uint8)
+            for k in range(4)]
+    # the fine-tune step's rate on a uint8 batch, in this process (leg 14's block: host clock around steps that end in a device synchronise)
+    torch.manual_seed(0)
+    clf = build_classifier("vit_base_patch16", C, True, img_size=R, compute_dtype=torch.bfloat16, train_encoder=True).to(dev)
+    step_args = argparse.Namespace(learning_rate=3e-2, weight_decay=1e-4, decay_type="cosine", warmup_steps=50, num_steps=3000, max_grad_norm=1.0)
+    opt = engine_finetune.make_optimizer(clf, step_args)
+    step_rate, n = {}, 0
+    for B in batches:
+        x = torch.randint(0, 256, (B, R, R), dtype=torch.uint8, device=dev)
+        y = (torch.rand(B, C, device=dev) < 0.3).float()
+        per = []
+        for steps in (args.warmup, args.iters, args.iters, args.iters):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                engine_finetune.train_step(clf, opt, x, y, n, step_args)
+                n += 1
+            torch.cuda.synchronize()
+            per.append((time.perf_counter() - t0) / max(1, steps))
+        step_rate[B] = B / statistics.median(per[1:])
+    del clf, opt
+    torch.cuda.empty_cache()
+    say("the fine-tune step (ViT-B/16, bf16, forward + backward + clip + SGD) on a resident uint8 batch, this process, median of three blocks of %d steps: %s"
+        % (args.iters, ", ".join("B = %d: %.0f images/s" % (B, r) for B, r in step_rate.items())))
+    for colour in ((True,) if args.colour else (False, True)):
+        kind = "colour" if colour else "gray"
+
+        def source(k):
+            if colour:
+                return np.roll(np.stack([base[k % 4], base[(k + 1) % 4], base[(k + 2) % 4]]), 37 * k, axis=2)
+            return np.roll(base[k % 4], 37 * k, axis=1)
+
+        root = tempfile.mkdtemp(prefix="ecamp_image_resident_")
+        try:
+            lines = ["img/i%d.png %s" % (k, " ".join(str((k >> c) & 1) for c in range(C))) for k in range(N)]
+            open(os.path.join(root, "train_list.txt"), "w").write("\n".join(lines * rep) + "\n")
+            path = os.path.join(root, "train_list.txt.u8")
+            with U8ShardWriter(path, colour=colour) as w:
+                for _ in range(rep):
+                    for k in range(N):
+                        w.add(np.ascontiguousarray(source(k).transpose(1, 2, 0)) if colour else source(k))
+            shard = fd.ResidentShard(path, dev)
+            say("== %s sources: a shard of %d images (%d different ones, each listed %d times), %s%d x %d" % (kind, N * rep, N, rep, "3 x " if colour else "", S, S))
+            say("   upload: %d bytes resident (%.2f GB) in %.2f s = %.2f GB/s, through a pinned staging buffer of %d MB"
+                % (shard.nbytes, shard.nbytes / 1e9, shard.seconds, shard.nbytes / 1e9 / shard.seconds, fd.ResidentShard.CHUNK_BYTES >> 20))
+            say("(a) the call, per call (coefficients + horizontal + vertical pass), from event pairs around 10 back-to-back calls, the two alternating in one "
+                "loop (%d groups after %d warm-up groups); sample b of a batch is a box in image b of the shard; the packed call gets the same boxes copied "
+                "back to back" % (args.iters, args.warmup))
+            data = np.memmap(path, dtype=np.uint8, mode="r")
+            packed_name = "ecamp_resample_boxes_rgb_u8 (packed)" if colour else "ecamp_resample_boxes_u8 (packed)"
+            for B in batches:
+                torch.manual_seed(B)
+
+                def draw(first):
+                    """One batch: sample b is a box in image first + b of the shard -> (resident arguments, packed arguments, box bytes)"""
+                    rows = [fd.resident_item(shard.index[(first + b) % len(shard.index)], True, R) for b in range(B)]
+                    table, meta = fd.pack_resident(rows)
+                    items = []
+                    for r in rows:
+                        off, h, w, flip = (int(v) for v in r[:4])
+                        planes = [np.lib.stride_tricks.as_strided(data[off + p * int(r[11]):], shape=(h, w), strides=(int(r[10]), 1)) for p in range(3 if r[9] == 3 else 1)]
+                        items.append((np.stack(planes) if colour else planes[0], bool(flip), tuple(int(v) for v in r[5:9])))
+                    flat, ptable, pmeta = fd.pack_boxes(items)
+                    assert pmeta == meta and torch.equal(ptable[:, 1:10], table[:, 1:10])
+                    return (shard, table.to(dev), meta), (flat.to(dev), ptable.to(dev), pmeta), flat.numel()
+
+                def rotate(rs, calls):
+                    at = [0]
+
+                    def fn():
+                        rs(*calls[at[0] % len(calls)])
+                        at[0] += 1
+                    return fn
+
+                sets = [draw(0)]
+                rs_r, rs_p = fd.DeviceBoxResampler(dev, R), fd.DeviceBoxResampler(dev, R)
+                assert torch.equal(rs_r(*sets[0][0], check=True), rs_p(*sets[0][1], check=True))      # the same bytes, before anything is timed
+                while sum(n for _, _, n in sets) < args.resident_fresh_mb * 1e6:
+                    sets.append(draw(len(sets) * B))
+                say("   B = %3d: %.1f MB of box bytes, %d taps, tallest sample %d intermediate rows" % (B, sets[0][2] / 1e6, sets[0][0][2][0], sets[0][0][2][2]))
+                for what, use in (("the same batch in every call", sets[:1]),
+                                  ("another batch in every call: %d batches in rotation, %.0f MB of box bytes, more than the 256 MB Infinity Cache holds"
+                                   % (len(sets), sum(n for _, _, n in sets) / 1e6), sets)):
+                    us = event_groups([(packed_name, rotate(rs_p, [p for _, p, _ in use])),
+                                       ("ecamp_resample_shard_u8 (resident)", rotate(rs_r, [r for r, _, _ in use]))], args.iters, args.warmup, 10)
+                    say("      %s" % what)
+                    med = {}
+                    for name, xs in us.items():
+                        med[name], lo, hi = stats(xs)
+                        say("         %-40s median %8.1f us (min %.1f, max %.1f)" % (name, med[name], lo, hi))
+                    spread = max(us[packed_name]) - min(us[packed_name])
+                    diff = med["ecamp_resample_shard_u8 (resident)"] - med[packed_name]
+                    say("         resident - packed = %+.1f us (medians); the packed call's own spread across its groups: %.1f us -> %s"
+                        % (diff, spread, "not slower" if diff <= spread else "SLOWER than the packed call by more than its spread"))
+                del sets, rs_r, rs_p
+            del data
+            if N * rep < 96:
+                continue
+            say("(b) loaders: one pass over the list of %d samples, batch 96, %d workers each, pinned memory, shuffled; passes after the first are timed, "
+                "each ends in a device synchronise; device loader: ShardListDataset + collate_boxes (box bytes from the shard's pages over PCIe); resident "
+                "loader: ShardListDataset(resident=True) + collate_resident (one table row per sample) on the uploaded shard" % (N * rep, W))
+
+            def loader(resident):
+                ds = fd.ShardListDataset(root, root, "train", data_volume="100", img_size=R, resident=resident)
+                dl = DataLoader(ds, shuffle=True, batch_size=96, num_workers=W, pin_memory=True, collate_fn=fd.collate_resident if resident else fd.collate_boxes,
+                                persistent_workers=W > 0)
+                return fd.DeviceImageLoader(dl, dev, R, shard=shard if resident else None)
+
+            rates, slowest = {}, {}
+            for name, ld in (("device loader", loader(False)), ("resident loader", loader(True))):
+                per = []
+                for _ in range(4):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    seen = 0
+                    for x, _ in ld:
+                        seen += x.shape[0]
+                    torch.cuda.synchronize()
+                    per.append(seen / (time.perf_counter() - t0))
+                rates[name], slowest[name] = statistics.median(per[1:]), min(per[1:])
+                say("   %-18s %8.0f images/s (passes after the first: %s)" % (name, rates[name], " ".join("%.0f" % v for v in per[1:])))
+                del ld
+            say("   resident / device = %.2f x (medians); slowest passes: resident %.0f, device %.0f images/s -> %s"
+                % (rates["resident loader"] / rates["device loader"], slowest["resident loader"], slowest["device loader"],
+                   "the resident loader is not below the device loader" if slowest["resident loader"] >= slowest["device loader"]
+                   else "the resident loader is BELOW the device loader: the feature is not done"))
+            say("   a loader FEEDS a step when its SLOWEST timed pass is at least the step's rate (fine-tune: this process, above; probe step: 19 700 images/s, "
+                "profiles/linprobe.txt):")
+            for name in rates:
+                verdict = ["fine-tune step at B = %d (%.0f): %s" % (B, r, "FEEDS it" if slowest[name] >= r else "does NOT feed it") for B, r in step_rate.items()]
+                verdict.append("probe step (19 700): %s" % ("FEEDS it" if slowest[name] >= 19700 else "does NOT feed it"))
+                say("   %-18s slowest pass %6.0f images/s -> %s" % (name, slowest[name], "; ".join(verdict)))
+            del shard
+        finally:
+            shutil.rmtree(root, ignore_errors=True)
+    say("NOT covered: pre-training's --image_shard (MIMIC-CXR shards do not fit in HBM).  NOT measured: real fundus photographs, larger than %d x %d." % (S, S))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
@@ -610,7 +777,16 @@ def main():
     ap.add_argument("--loader_images", type=int, default=384, help="--image_pipeline: PNG files of the loader comparison")
     ap.add_argument("--loader_repeat", type=int, default=8, help="--image_pipeline: times the list names each file")
     ap.add_argument("--loader_workers", type=int, default=8, help="--image_pipeline: workers of both loaders (the drivers' default)")
+    ap.add_argument("--resident", action="store_true", help="--image_pipeline: the shard resident in device memory beside the packed call and the device loader, "
+                                                            "gray sources then colour ones (--colour: colour alone) (profiles/finetune_image_resident.txt)")
+    ap.add_argument("--resident_fresh_mb", type=float, default=600.0, help="--resident, leg (a): box bytes of the batches in rotation when every call gets another batch")
+    ap.add_argument("--resident_source", type=int, default=1024, help="--resident: side of the square sources (1024: the other legs'; another value moves the rows and "
+                                                                        "planes of a stored image off the power-of-two pitches)")
+    ap.add_argument("--image_resident_out", type=str,
+                    default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "finetune_image_resident.txt"))
     args = ap.parse_args()
+    if args.resident and not args.image_pipeline:
+        ap.error("--resident goes with --image_pipeline")
     if args.colour and not args.image_pipeline:
         ap.error("--colour goes with --image_pipeline")
     if not torch.cuda.is_available():
@@ -622,8 +798,8 @@ def main():
             print(msg, flush=True)
             lines.append(msg)
 
-        out = args.image_pipeline_colour_out if args.colour else args.image_pipeline_out
-        (image_pipeline_colour_leg if args.colour else image_pipeline_leg)(args, say_ip)
+        out = args.image_resident_out if args.resident else args.image_pipeline_colour_out if args.colour else args.image_pipeline_out
+        (image_resident_leg if args.resident else image_pipeline_colour_leg if args.colour else image_pipeline_leg)(args, say_ip)
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         with open(out, "w") as f:
             f.write("\n".join(lines) + "\n")
