@@ -38,6 +38,9 @@ static OptRow g_opts[OPT_COUNT] = {
     /* OPT_Q8_SCH */           {"q8_sch", "ECAMP_Q8_SCH", 7, [](int v) { return v >= 0 ? v : OPT_ENV; }},
     // the four-wave kernel: 0 never, 1 where the 192-column tile pays, 2 every eligible call, 3 (tests) as 2 whatever the size
     /* OPT_Q16_MODE */         {"q16_mode", "ECAMP_Q16", 1, [](int v) { return v >= 0 && v <= 3 ? v : OPT_ENV; }},
+    // the four-wave kernel's weight-gradient form (gemm_q16.h, q16w_body): 0 never, 1 the classes the measurements keep (gemm.hip,
+    // q16_wgrad_on), 2 wherever legal (lab, tests); anything else: back to the environment
+    /* OPT_Q16_WGRAD */        {"q16_wgrad", "ECAMP_Q16_WGRAD", 1, [](int v) { return v >= 0 && v <= 2 ? v : OPT_ENV; }},
     /* OPT_F8_Q8 */            {nullptr, "ECAMP_F8_Q8", 1, nullptr},             // 0: the 128^2 e4m3 kernel everywhere
     /* OPT_Q8_MIN_ITEMS */     {nullptr, "ECAMP_Q8_MIN_ITEMS", OPT_AUTO, nullptr},   // 256^2 work items from which Q8 is chosen; default half the CU count
     // workgroups of the data-gradient form (gemm.hip, gemm_select); 0 = one per CU, and back to the environment

@@ -751,6 +751,20 @@ static gemm_fn q16_pick(int b_kc, int epi, int nw) {
     if (nw == 8) return epi == 0 ? (gemm_fn)gemm_bf16_q16_kernel<0, 8, false> : (gemm_fn)gemm_bf16_q16_kernel<2, 8, false>;
     return epi == 0 ? (gemm_fn)gemm_bf16_q16_kernel<0, 6, false> : (gemm_fn)gemm_bf16_q16_kernel<2, 6, false>;
 }
+// Q16, weight-gradient form (gemm_q16.h, q16w_body): per-layer launches (split-K slabs or C) and the grouped item-table launch; switch
+// "q16_wgrad".  Legal wherever Q8's weight-gradient form is (same tile, same rings, same 16-B rules).  At 1 (the default) the classes
+// whose alternating lab runs were ALL faster than the eight-wave kernel's move (profiles/wgrad_q16.txt: grouped launches -6..-8 %, the
+// vocabulary head -9.6 %, a 768 x 768 layer -5.6 %): every grouped launch, and the per-layer launches the size rule selects by itself
+// whose output is at least one whole tile both ways (narrower outputs were not measured and stay).  "q16_mode" 0 -- never the four-wave
+// kernel -- holds for 1 as well; 2 is the lab's and the tests': wherever legal.
+enum Q16WgradClass { Q16W_GROUPED = 1, Q16W_LAYER = 2 };
+static bool q16_wgrad_on(int cls, const GemmArgs* g = nullptr) {
+    const int m = ecamp_opt(OPT_Q16_WGRAD);
+    if (m >= 2) return true;
+    if (m != 1 || ecamp_opt(OPT_Q16_MODE) == 0) return false;
+    if (cls == Q16W_GROUPED) return true;
+    return g && g->M >= 256 && g->N >= 256 && (long)ceil_div(g->M, 256) * ceil_div(g->N, 256) * g->nsplit >= q8_min_items();
+}
 
 // What serves one ecamp_gemm / ecamp_gemm_res32 call.  The profiler tag is name:form:e<epi>:M:N:K:<tail><n> with n the split count
 // (tail 's') or the tile width (tail 'w'); tools/gemm_in_step.py and the ecamp_prof_dump consumers parse it.
@@ -771,7 +785,8 @@ static GemmChoice gemm_select(const GemmArgs& g, int a_kc, int b_kc, int dtype, 
     // the persistent kernels: from q8_min_items() work items up ("q16_mode" 3, the tests', whatever the size), where Q8 is legal
     const int q8m = ecamp_opt(OPT_Q8_MODE), m16 = ecamp_opt(OPT_Q16_MODE);
     const long items8 = (long)ceil_div(g.M, 256) * ceil_div(g.N, 256) * g.nsplit;
-    if (q8m == 0 || !(q8m == 2 || items8 >= q8_min_items() || m16 == 3) || !(a_kc || b_kc || ecamp_opt(OPT_P8_WGRAD)) || !q8_legal(g, a_kc, b_kc, dtype, res32))
+    const bool w16 = !a_kc && !b_kc && ecamp_opt(OPT_Q16_WGRAD) == 2;   // "q16_wgrad" 2: the weight-gradient form wherever legal, whatever the size
+    if (q8m == 0 || !(q8m == 2 || items8 >= q8_min_items() || m16 == 3 || w16) || !(a_kc || b_kc || ecamp_opt(OPT_P8_WGRAD)) || !q8_legal(g, a_kc, b_kc, dtype, res32))
         return c;
     const int epi = q8_epi(g, res32), ncu = p8_num_cu();
     c.epi = (char)('0' + epi);
@@ -793,6 +808,11 @@ static GemmChoice gemm_select(const GemmArgs& g, int a_kc, int b_kc, int dtype, 
             c.cap = bwd_grid > 0 ? bwd_grid : ncu;
             return c;
         }
+    }
+    if (!a_kc && !b_kc && epi == 4 && q16_wgrad_on(Q16W_LAYER, &g)) {
+        c.family = GEMM_Q16; c.fn = g.rowsum ? (gemm_fn)gemm_bf16_q16_wgrad_kernel<true> : (gemm_fn)gemm_bf16_q16_wgrad_kernel<false>;
+        c.tm = 256; c.tn = 256; c.block = 256; c.name = "q16"; c.cap = p8_bwd_cus();
+        return c;
     }
     c.family = GEMM_Q8; c.fn = q8_pick(a_kc, b_kc, epi, g.rowsum != nullptr); c.tm = 256; c.tn = 256; c.block = 512; c.name = "q8";
     c.cap = bwd_grid > 0 ? bwd_grid : a_kc && b_kc ? ncu : p8_bwd_cus();
@@ -1206,18 +1226,21 @@ extern "C" int ecamp_wgrad_group(int32_t n, const void* const* dy, const void* c
     g.out_f32 = 1; g.alpha_out = alpha; g.nbm = 1; g.nbn = 1; g.wide = 1; g.partial = ws;
     typedef void (*q8i_fn)(GemmArgs, Q8Group);
     const bool lean = (ecamp_opt(OPT_Q8_SCH) & 8) != 0;
-    const q8i_fn fn = any_bias ? (lean ? (q8i_fn)gemm_bf16_q8_items_kernel<true, 1> : (q8i_fn)gemm_bf16_q8_items_kernel<true, 0>)
+    const bool four = q16_wgrad_on(Q16W_GROUPED);   // the four-wave kernel fills the slabs (same table, same slabs, same reduce)
+    const q8i_fn fn = four ? (any_bias ? (q8i_fn)gemm_bf16_q16_wgrad_items_kernel<true> : (q8i_fn)gemm_bf16_q16_wgrad_items_kernel<false>)
+                    : any_bias ? (lean ? (q8i_fn)gemm_bf16_q8_items_kernel<true, 1> : (q8i_fn)gemm_bf16_q8_items_kernel<true, 0>)
                                : (lean ? (q8i_fn)gemm_bf16_q8_items_kernel<false, 1> : (q8i_fn)gemm_bf16_q8_items_kernel<false, 0>);
     double work = 0.0;
     for (int p = 0; p < n; ++p) work += 2.0 * (double)n_out[p] * (double)k_in[p] * (double)rows;
     const bool prof = ecamp_prof_active();
     if (prof) {
         char tag[40];
-        snprintf(tag, sizeof tag, "grp:w:n%d:%ld:%ld:%ld:wg%d", n, (long)rows, (long)n_out[0], (long)k_in[0], pl->nwg);
+        snprintf(tag, sizeof tag, "%s:w:n%d:%ld:%ld:%ld:wg%d", four ? "grp16" : "grp", n, (long)rows, (long)n_out[0], (long)k_in[0], pl->nwg);
         ecamp_prof_begin(ECAMP_PROF_GEMM_BF16, work, stream, tag);
     }
-    launch_persistent(fn, (long)pl->nwg, (long)pl->nwg, 512, stream, g, G);   // the plan's workgroup count: each has its range of the table
-    g_q8_launches += n;
+    launch_persistent(fn, (long)pl->nwg, (long)pl->nwg, four ? 256 : 512, stream, g, G);   // the plan's workgroup count: each has its range of the table
+    g_q8_launches += n;          // (layer problems served by a grouped persistent launch, whichever kernel fills the slabs)
+    if (four) ++g_q16_launches;
     ++g_wg_launches;
     hipLaunchKernelGGL(wgrad_group_reduce_kernel, dim3(pl->ntiles * 16), dim3(256), 0, stream, R);
     if (prof) ecamp_prof_end(stream);

@@ -1,6 +1,7 @@
 // "Q16": the persistent bf16 GEMM as FOUR waves (2 x 2, one per SIMD) on v_mfma_f32_16x16x32_bf16 (round 5).  Forward form
 // (y = x w^T (+ b) (+ residual): nn.Linear forward, model_ecamp.py:233-234,254-255 / bert_modeling.py:131) and data-gradient form
-// (dx = dy w (+ residual): its autograd), bf16 outputs, tile 256 x 256 (NW = 8) or 256 x 192 (NW = 6).
+// (dx = dy w (+ residual): its autograd), bf16 outputs, tile 256 x 256 (NW = 8) or 256 x 192 (NW = 6).  The weight-gradient form
+// (dW = dy^T x, f32 outputs, per-layer and grouped launches) is q16w_body at the end of this file.
 //
 // Why it exists beside gemm_q8.h (profiles/r05_vendor_vs_q8.txt, r05_gemm_in_step_vs_lab.txt):
 //  * POWER.  On random operands the chip is power-limited (rounds 3-4).  The same 4096^3 problem, back to back until the clocks settle: the
@@ -413,4 +414,379 @@ __device__ __forceinline__ void q16_body(const GemmArgs& g) {
 template <int EPI, int NW, bool B_KC, int DBG = 0>
 __global__ __launch_bounds__(256) void gemm_bf16_q16_kernel(GemmArgs g) {
     q16_body<EPI, NW, B_KC, DBG>(g);
+}
+
+// ---- the WEIGHT-GRADIENT form: dW[n_out, k_in] (+)= dY^T X, both operands strided (they lie in HBM with the contraction over the rows).
+// Tile 256 x 256, the rings, the DMA pieces, the k-step schedule and the N side are q16_body's data-gradient form.  The M side (dY) is
+// staged like the N side -- half-tiles of 64 k-rows x 256 B as they lie in HBM, chunk j of k-row kr at position j ^ ((kr & 3) << 2) -- and
+// read with the same two ds_read_b64_tr_b16 per fragment: lane (r = (l & 15) >> 2, q = l & 3) of 16-lane group g addresses k-row
+// 32 ks + 8 g + r (+ 4 for the second read), rows 16 I + 4 q .. + 3 of the wave's 128, and receives row 16 I + (l & 15): the fragment rows
+// stay in natural order, so the epilogue's row map is q16_body's.  Chunk 2 I + (q >> 1): the XOR touches the bits of I >> 1 (one per-lane
+// offset each), I & 1 is + 32 B.  Banks: a 16-lane group covers 4 x 8 banks, the two k-groups of a 32-lane half meet on them (2-way, as
+// on the N side).  K ends need no lane mask: k-rows past the item's range fall outside the descriptors and read as zero.
+//   ROWSUM: the bias gradient = column sums of dY, from the M-side fragments of the tiles in the first N-tile column: one v_dot2c per
+//   fragment dword against a pair of ones, ONE behind every MFMA pair.  The VALU work is NOT hidden by the matrix pipe -- summed by
+//   every wave of every tile through operands of zeros, as the eight-wave kernel does it, it costs 10-14 % of a grouped launch
+//   (profiles/wgrad_q16.txt) -- so the K loop exists in three versions chosen per item by a wave-uniform branch: no sums (every other
+//   tile), sums in k-step 0 (wave column 0) or in k-step 1 (wave column 1: both wave columns hold the same M-side fragments, each
+//   sums half of the contraction).  The four k-groups of a row meet by two lane exchanges, 8 buffer atomics per wave and tile.
+//   ITEMS: the work list is a Q8Group's (gemm_args.h) -- operands and leading dimensions change with the item's problem, every piece
+//   stores a dense 256 x 256 f32 slab.  Otherwise the tile x split arithmetic of q8_decode with gemm_q8.h's EPI == 4 outputs (f32 only):
+//   a split-K slab, or C (+= old) with alpha / alpha_dev.
+template <bool ROWSUM, bool ITEMS>
+__device__ __forceinline__ void q16w_body(const GemmArgs& g, const Q8Group& GR) {
+    constexpr int NSLOT = 5, NW = 8;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];   // A ring (5 x 16 KB) | B ring (5 x 16 KB); the ONLY LDS object
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wr = wave >> 1, wc = wave & 1;
+    const int l15 = lane & 15, lq = lane >> 4;
+    typedef const int __attribute__((address_space(4))) cint4;
+    const int it_beg = ITEMS ? *(cint4*)(GR.wg_first + blockIdx.x) : (int)blockIdx.x;
+    const int total = ITEMS ? *(cint4*)(GR.wg_first + blockIdx.x + 1) : g.nbm * g.nbn * g.nsplit, G = ITEMS ? 1 : (int)gridDim.x;
+    // The group's problems are read where they lie, in the kernel-argument segment, by scalar loads with the item's problem index (the
+    // eight-wave kernel keeps all four problems' fields in SGPRs and selects: 56 SGPRs this kernel does not have -- beside 256
+    // accumulators and two fragment sets they spill to VGPR lanes and from there to scratch).  ITEMS kernels take (GemmArgs, Q8Group).
+    typedef int q16_i32x8 __attribute__((ext_vector_type(8)));
+    typedef const q16_i32x8 __attribute__((address_space(4))) crec4;
+    static_assert(sizeof(Q8Prob) == 64 && offsetof(Q8Prob, A) == 0 && offsetof(Q8Prob, B) == 8 && offsetof(Q8Prob, lda) == 16 && offsetof(Q8Prob, ldb) == 24 &&
+                  offsetof(Q8Prob, M) == 32 && offsetof(Q8Prob, rowsum) == 40 && offsetof(Q8Prob, alpha_dev_out) == 48 && offsetof(Q8Prob, alpha_out) == 56 &&
+                  alignof(Q8Group) == 8, "q16w_body reads Q8Prob as two 32-byte records");
+    const unsigned char __attribute__((address_space(4)))* const probs =
+        (const unsigned char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr() + ((sizeof(GemmArgs) + 7) & ~(size_t)7) + offsetof(Q8Group, p);
+    auto prob_half = [&](int prob, int half) { return *(crec4*)(probs + prob * 64 + half * 32); };   // half 0: A B lda ldb; 1: M N rowsum alpha_dev_out alpha_out
+    auto ptr_of = [](int lo, int hi) {
+        return (const void*)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(hi) << 32) | (unsigned)__builtin_amdgcn_readfirstlane(lo));
+    };
+    float* const gr_slabs = GR.slabs;
+    auto item_at = [&](int i) {   // record i of the table, through scalar loads
+        const q16_i32x8 w = *(crec4*)(reinterpret_cast<const int*>(GR.items) + (long)i * 8);
+        Q8ItemRec r;
+#define Q16W_U(X) __builtin_amdgcn_readfirstlane(X)
+        r.prob = Q16W_U(w[0]); r.m0 = Q16W_U(w[1]); r.n0 = Q16W_U(w[2]); r.kbeg = Q16W_U(w[3]); r.kend = Q16W_U(w[4]); r.slab = Q16W_U(w[5]); r.flags = Q16W_U(w[6]); r.pad = 0;
+#undef Q16W_U
+        return r;
+    };
+    auto uniform_ptr = [](const void* q) {
+        const unsigned long long v = (unsigned long long)q;
+        const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+        return (const void*)(((unsigned long long)hi << 32) | lo);
+    };
+
+    // per-lane fragment offsets inside a half-tile.  M: per tile pair I >> 1, tile parity at + 32 B; N: per tile pair t >> 1, tile parity at
+    // + 8 B; both: k-step at + 8192, second read at + 1024
+    unsigned offM[4], offN[4];
+    {
+        const int r = l15 >> 2, q = l15 & 3;
+#pragma unroll
+        for (int T = 0; T < 4; ++T) {
+            offM[T] = (unsigned)((8 * lq + r) * 256 + ((((T ^ r) << 2) | (q >> 1)) << 4) + (q & 1) * 8);
+            offN[T] = (unsigned)((8 * lq + r) * 256 + ((((4 * T + q) ^ (r << 2)) & 15) << 4));
+        }
+    }
+    q16_f32x4 acc[8][NW];
+
+    // ---- the operand stream: wave w owns pieces 4 w .. 4 w + 3 (4 k-rows x 256 B each) of every half-tile
+    const unsigned char *qa = reinterpret_cast<const unsigned char*>(g.A), *qb = reinterpret_cast<const unsigned char*>(g.B);
+    int qa_rec = 0, qb_rec = 0, q_krem = 1 << 30, qv = it_beg;
+    int a_step = (int)g.lda * 128, b_step = (int)g.ldb * 128;   // bytes per K tile (ITEMS: follow the staged item's problem)
+    long q_lda = ITEMS ? -1 : g.lda, q_ldb = ITEMS ? -1 : g.ldb;
+    unsigned cvA[8], cvB[8];   // [half * 4 + j]
+    int dA = wave * 4096, dB = NSLOT * Q8_HALF + wave * 4096;
+    auto q_cv = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int kr = (wave * 4 + j) * 4 + (lane >> 4);
+            const int oc = (lane & 15) ^ ((kr & 3) << 2);
+            cvA[j] = (unsigned)(((long)kr * q_lda + oc * 8) * 2); cvA[4 + j] = cvA[j] + 256u;   // second half-tile: 128 rows / columns on
+            cvB[j] = (unsigned)(((long)kr * q_ldb + oc * 8) * 2); cvB[4 + j] = cvB[j] + 256u;
+        }
+    };
+#define Q16W_ITEM()                                                                                                      \
+    do {                                                                                                                 \
+        if (ITEMS) {                                                                                                     \
+            const Q8ItemRec r_ = item_at(qv);                                                                            \
+            const q16_i32x8 p_ = prob_half(r_.prob, 0);                                                                  \
+            const long la_ = __builtin_amdgcn_readfirstlane(p_[4]), lb_ = __builtin_amdgcn_readfirstlane(p_[6]);   /* (< 2^31: host-checked) */ \
+            const unsigned char* A_ = reinterpret_cast<const unsigned char*>(ptr_of(p_[0], p_[1]));                      \
+            const unsigned char* B_ = reinterpret_cast<const unsigned char*>(ptr_of(p_[2], p_[3]));                      \
+            q_krem = r_.kend - r_.kbeg;                                                                                  \
+            qa = A_ + ((long)r_.kbeg * la_ + r_.m0) * 2; qa_rec = (int)(((long)q_krem * la_ - r_.m0) * 2);               \
+            qb = B_ + ((long)r_.kbeg * lb_ + r_.n0) * 2; qb_rec = (int)(((long)q_krem * lb_ - r_.n0) * 2);               \
+            a_step = (int)la_ * 128; b_step = (int)lb_ * 128;                                                            \
+            if (la_ != q_lda || lb_ != q_ldb) { q_lda = la_; q_ldb = lb_; q_cv(); }                                      \
+        } else {                                                                                                         \
+            const Q8Item n_ = q8_decode<6>(g, qv, total);                                                                \
+            q_krem = n_.kend - n_.kbeg;                                                                                  \
+            qa = reinterpret_cast<const unsigned char*>(g.A) + ((long)n_.kbeg * g.lda + n_.m0) * 2; qa_rec = (int)(((long)q_krem * g.lda - n_.m0) * 2); \
+            qb = reinterpret_cast<const unsigned char*>(g.B) + ((long)n_.kbeg * g.ldb + n_.n0) * 2; qb_rec = (int)(((long)q_krem * g.ldb - n_.n0) * 2); \
+        }                                                                                                                \
+        qa_rec = max(qa_rec, 0); qb_rec = max(qb_rec, 0);                                                                \
+    } while (0)
+    typedef void __attribute__((address_space(3))) lds_void_;
+    // piece J of part PART (0: A half 0, 1: B half 0, 2: A half 1, 3: B half 1)
+#define Q16W_ISSUE1(PART, J)                                                                                             \
+    do {                                                                                                                 \
+        constexpr bool isA_ = (((PART) & 1) == 0);                                                                       \
+        constexpr int h_ = (PART) >> 1;                                                                                  \
+        const __amdgpu_buffer_rsrc_t rs_ = __builtin_amdgcn_make_buffer_rsrc((void*)(isA_ ? qa : qb), 0, isA_ ? qa_rec : qb_rec, 0x00020000); \
+        unsigned char* d_ = lds + (isA_ ? dA : dB) + (J) * 1024;                                                         \
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_, (lds_void_*)d_, 16, (int)(isA_ ? cvA[4 * h_ + (J)] : cvB[4 * h_ + (J)]), 0, 0, 0); \
+    } while (0)
+#define Q16W_ADVANCE(PART)                                                                                               \
+    do {                                                                                                                 \
+        if (((PART) & 1) == 0) { dA += Q8_HALF; if (dA >= NSLOT * Q8_HALF) dA -= NSLOT * Q8_HALF; }                      \
+        else                   { dB += Q8_HALF; if (dB >= 2 * NSLOT * Q8_HALF) dB -= NSLOT * Q8_HALF; }                  \
+        if ((PART) == 3) {                                                                                               \
+            q_krem -= 64;                                                                                                \
+            qa += a_step; qb += b_step; qa_rec = max(qa_rec - a_step, 0); qb_rec = max(qb_rec - b_step, 0);              \
+            if (q_krem <= 0) {                                                                                           \
+                qv += G;                                                                                                 \
+                if (qv < total) Q16W_ITEM(); else { qa_rec = 0; qb_rec = 0; q_krem = 1 << 30; }                          \
+            }                                                                                                            \
+        }                                                                                                                \
+    } while (0)
+#define Q16W_ISSUE_ALL(PART) do { Q16W_ISSUE1(PART, 0); Q16W_ISSUE1(PART, 1); Q16W_ISSUE1(PART, 2); Q16W_ISSUE1(PART, 3); } while (0)
+#define Q16W_SB() __builtin_amdgcn_sched_barrier(0)
+
+    // ---- bias gradient: rs[I] = this lane's share (its eight k of every k-step) of the column sum of row 16 I + l15 of the wave's rows
+    float rs[8];
+    const unsigned rs_ones = H16_ONE_X2;
+    typedef unsigned q16_u32x2 __attribute__((ext_vector_type(2)));
+
+    // ---- epilogue: 32-column block P of the wave's tile, all eight 16-row MFMA tiles of it; a lane holds row l15 and columns 8 lq .. + 7
+    // pm0 / pn0 / pz: the tile's first row and column and its split slice (ITEMS: pz is the slab index, the rest is unused)
+    const unsigned lane_slab = (unsigned)(((wr * 128 + l15) * 256 + wc * 128 + 8 * lq) * 4);
+    auto store_block = [&](int pm0, int pn0, int pz, auto p_c) __attribute__((always_inline)) {
+        constexpr int P = decltype(p_c)::value;
+        typedef const float __attribute__((address_space(4))) cfloat4;
+        unsigned uo[8];
+        int so[8];     // wave-uniform part of the offsets (ITEMS only: one lane offset serves the whole tile, hipcc would keep 32 of them live across the K loop)
+        float al = 1.f;
+        bool accum = false;
+        __amdgpu_buffer_rsrc_t rO;
+        if constexpr (ITEMS) {   // dense slab: no bounds, no scaling (the grouped reduce applies alpha)
+            rO = __builtin_amdgcn_make_buffer_rsrc((void*)uniform_ptr(gr_slabs + (long)pz * 65536), 0, 262144, 0x00020000);
+#pragma unroll
+            for (int I = 0; I < 8; ++I) { uo[I] = lane_slab; so[I] = (I * 16 * 256 + P * 32) * 4; }   // (every offset lies inside the dense slab)
+        } else {
+            const int nb = pn0 + wc * 128 + P * 32 + 8 * lq;
+            const bool oob = nb >= g.N;     // (N % 8 == 0, host-checked)
+            if (g.partial) {                // rows past M would land in the next slice's slab: dropped here
+                rO = __builtin_amdgcn_make_buffer_rsrc((void*)g.partial, 0, (int)(unsigned)((long)g.nsplit * g.M * g.N * 4), 0x00020000);
+#pragma unroll
+                for (int I = 0; I < 8; ++I) {
+                    const int row = pm0 + wr * 128 + I * 16 + l15;
+                    uo[I] = (oob || row >= g.M) ? 0x80000000u : (unsigned)((((long)pz * g.M + row) * g.N + nb) * 4);
+                    so[I] = 0;
+                }
+            } else {                        // rows past M fall outside the descriptor
+                rO = __builtin_amdgcn_make_buffer_rsrc(g.C, 0, (int)(unsigned)((long)g.M * g.ldc * 4), 0x00020000);
+                al = g.alpha;
+                if (g.alpha_dev) { float ad = *(cfloat4*)g.alpha_dev; asm volatile("" : "+s"(ad)); al *= ad; }
+                accum = g.accumulate != 0;
+#pragma unroll
+                for (int I = 0; I < 8; ++I) {
+                    const int row = pm0 + wr * 128 + I * 16 + l15;
+                    uo[I] = oob ? 0x80000000u : (unsigned)(((long)row * g.ldc + nb) * 4);
+                    so[I] = 0;
+                }
+            }
+        }
+        q8_u32x4 qo[8], qo2[8];
+        if (!ITEMS && accum) {
+#pragma unroll
+            for (int I = 0; I < 8; ++I) {
+                qo[I] = __builtin_amdgcn_raw_buffer_load_b128(rO, uo[I], 0, 0);
+                qo2[I] = __builtin_amdgcn_raw_buffer_load_b128(rO, uo[I] + 16, 0, 0);
+            }
+        }
+        Q16W_SB();
+#pragma unroll
+        for (int I = 0; I < 8; ++I) {
+            float v[8];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {   // explicit AGPR reads (q16_body)
+                float x0, x1;
+                asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(x0) : "a"(acc[I][2 * P][r]));
+                asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(x1) : "a"(acc[I][2 * P + 1][r]));
+                v[r] = ITEMS ? x0 : x0 * al; v[4 + r] = ITEMS ? x1 : x1 * al;
+            }
+            if (!ITEMS && accum) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { v[r] += __uint_as_float(qo[I][r]); v[4 + r] += __uint_as_float(qo2[I][r]); }
+            }
+            __builtin_amdgcn_raw_buffer_store_b128((q8_u32x4){__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])}, rO, uo[I], so[I], 0);
+            __builtin_amdgcn_raw_buffer_store_b128((q8_u32x4){__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7])}, rO, uo[I] + 16, so[I], 0);
+            Q16W_SB();
+        }
+    };
+    // the finished tile's column sums: lanes of k-group 0 add (exactly 8 instructions whatever the bounds: rows past M fall outside)
+    auto rowsum_flush = [&](int pm0, float al, const float* adp, float* dst, int dstM) __attribute__((always_inline)) {
+        typedef const float __attribute__((address_space(4))) cfloat4;
+        if (adp) { float ad = *(cfloat4*)adp; asm volatile("" : "+s"(ad)); al *= ad; }
+        const __amdgpu_buffer_rsrc_t rS = __builtin_amdgcn_make_buffer_rsrc((void*)dst, 0, (int)(unsigned)((long)dstM * 4), 0x00020000);
+#pragma unroll
+        for (int I = 0; I < 8; ++I) {
+            float tot = rs[I] + __shfl_xor(rs[I], 16, 64);
+            tot = (tot + __shfl_xor(tot, 32, 64)) * al;
+            const unsigned off = lq ? 0x80000000u : (unsigned)((pm0 + wr * 128 + I * 16 + l15) * 4);
+            __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(tot, rS, off, 0, 0);
+        }
+    };
+    const q16_f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+
+    // ---- fragments: two register sets (k-step parity), both sides through transpose reads named behind one explicit wait
+    Q16FragN<false> fa[2][8], fb[2][NW];
+#define Q16W_RDA(S, KS, I, SM_) fa[S][I].template read_tr<((I) & 1) * 32 + (KS) * 8192>((SM_) + offM[(I) >> 1])
+#define Q16W_RDB(S, KS, T, SN_) fb[S][T].template read_tr<((T) & 1) * 8 + (KS) * 8192>((SN_) + offN[(T) >> 1])
+    auto wait_set = [&](Q16FragN<false> (&f)[8], Q16FragN<false> (&e)[8]) __attribute__((always_inline)) {
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0].lo), "+v"(f[0].hi), "+v"(f[1].lo), "+v"(f[1].hi), "+v"(f[2].lo), "+v"(f[2].hi), "+v"(f[3].lo), "+v"(f[3].hi),
+                     "+v"(f[4].lo), "+v"(f[4].hi), "+v"(f[5].lo), "+v"(f[5].hi), "+v"(f[6].lo), "+v"(f[6].hi), "+v"(f[7].lo), "+v"(f[7].hi));
+        asm volatile("" : "+v"(e[0].lo), "+v"(e[0].hi), "+v"(e[1].lo), "+v"(e[1].hi), "+v"(e[2].lo), "+v"(e[2].hi), "+v"(e[3].lo), "+v"(e[3].hi),
+                     "+v"(e[4].lo), "+v"(e[4].hi), "+v"(e[5].lo), "+v"(e[5].hi), "+v"(e[6].lo), "+v"(e[6].hi), "+v"(e[7].lo), "+v"(e[7].hi));
+    };
+#define Q16W_WAIT_SET(S) do { wait_set(fb[S], fa[S]); Q16W_SB(); } while (0)
+#define Q16W_MFMA(S, J, ZERO)                                                                                            \
+    do {                                                                                                                 \
+        constexpr int i_ = (J) / NW, t_ = (J) % NW;                                                                      \
+        acc[i_][t_] = ECAMP_MFMA_16x16x32(fb[S][t_].get(), fa[S][i_].get(), (ZERO) ? zero4 : acc[i_][t_]);               \
+    } while (0)
+    // dword s & 3 of M-side fragment s >> 2 of the set being multiplied into its row's sum
+#define Q16W_RS(S, s_, ON)                                                                                               \
+    do {                                                                                                                 \
+        if constexpr (ROWSUM && (ON)) {                                                                                        \
+            constexpr int i_ = (s_) >> 2, j_ = (s_) & 3;                                                                 \
+            const unsigned w_ = j_ < 2 ? __builtin_bit_cast(q16_u32x2, fa[S][i_].lo)[j_ & 1] : __builtin_bit_cast(q16_u32x2, fa[S][i_].hi)[j_ & 1]; \
+            asm(ECAMP_DOT2C " %0, %1, %2" : "+v"(rs[i_]) : "v"(w_), "v"(rs_ones));                                       \
+        }                                                                                                                \
+    } while (0)
+    // slot s (0 .. 31) behind MFMA pair s: the 16 fragment reads of the next k-step in the order its MFMAs consume them, then the DMA
+    // pieces of part DP0, its bookkeeping, part DP1 likewise (q16_body)
+#define Q16W_SLOT(NS, NKS, SM_, SN_, DP0, DP1, s_)                                                                       \
+    do {                                                                                                                 \
+        constexpr int s__ = (s_);                                                                                        \
+        if (s__ < 8) Q16W_RDB(NS, NKS, (s__ < 8 ? s__ : 0), SN_);                                                        \
+        else if (s__ < 16) Q16W_RDA(NS, NKS, (s__ >= 8 && s__ < 16 ? s__ - 8 : 0), SM_);                                 \
+        else if (s__ < 20) { Q16W_ISSUE1(DP0, (s__ - 16) & 3); }                                                         \
+        else if (s__ == 20) { Q16W_ADVANCE(DP0); }                                                                       \
+        else if (s__ < 25) { Q16W_ISSUE1(DP1, (s__ - 21) & 3); }                                                         \
+        else if (s__ == 25) { Q16W_ADVANCE(DP1); }                                                                       \
+    } while (0)
+#define Q16W_PAIR(S, ZERO, NS, NKS, SM_, SN_, DP0, DP1, RS_, s_)                                                         \
+    do {                                                                                                                 \
+        Q16W_MFMA(S, 2 * (s_), ZERO); Q16W_MFMA(S, 2 * (s_) + 1, ZERO); Q16W_RS(S, s_, RS_); Q16W_SB();                  \
+        Q16W_SLOT(NS, NKS, SM_, SN_, DP0, DP1, s_); Q16W_SB();                                                           \
+    } while (0)
+#define Q16W_PAIR4(S, Z, NS, NKS, SM_, SN_, D0, D1, s_) \
+    do { Q16W_PAIR(S, Z, NS, NKS, SM_, SN_, D0, D1, RS_, (s_)); Q16W_PAIR(S, Z, NS, NKS, SM_, SN_, D0, D1, RS_, (s_) + 1); Q16W_PAIR(S, Z, NS, NKS, SM_, SN_, D0, D1, RS_, (s_) + 2); Q16W_PAIR(S, Z, NS, NKS, SM_, SN_, D0, D1, RS_, (s_) + 3); } while (0)
+#define Q16W_KSTEP(S, Z, NS, NKS, SM_, SN_, D0, D1, RSK_)                                                                    \
+    do {                                                                                                                 \
+        constexpr bool RS_ = (RSK_);                                                                                     \
+        Q16W_SB();                                                                                                       \
+        Q16W_WAIT_SET(S);                                                                                                \
+        Q16W_PAIR4(S, Z, NS, NKS, SM_, SN_, D0, D1, 0);  Q16W_PAIR4(S, Z, NS, NKS, SM_, SN_, D0, D1, 4);                 \
+        Q16W_PAIR4(S, Z, NS, NKS, SM_, SN_, D0, D1, 8);  Q16W_PAIR4(S, Z, NS, NKS, SM_, SN_, D0, D1, 12);                \
+        Q16W_PAIR4(S, Z, NS, NKS, SM_, SN_, D0, D1, 16); Q16W_PAIR4(S, Z, NS, NKS, SM_, SN_, D0, D1, 20);                \
+        Q16W_PAIR4(S, Z, NS, NKS, SM_, SN_, D0, D1, 24); Q16W_PAIR4(S, Z, NS, NKS, SM_, SN_, D0, D1, 28);                \
+    } while (0)
+    int rA = 0, rB = 0;   // ring slots of A_0 / B_0 of the K tile being multiplied
+    // K tile t (q16_body's discipline): k-step 0 stages A_0 / B_0 (t+2), k-step 1 -- behind the counted wait and the barrier that publish
+    // K tile t+1 and retire every read of K tile t -- stages A_1 / B_1 (t+2)
+#define Q16W_RS_(R_, ADD_) ((R_) + (ADD_) >= NSLOT ? (R_) + (ADD_) - NSLOT : (R_) + (ADD_))
+#define Q16W_KTILE(FIRST, RSV)                                                                                             \
+    do {                                                                                                                 \
+        const unsigned char* sM = lds + Q16W_RS_(rA, wr) * Q8_HALF;                                                      \
+        const unsigned char* sN = lds + (NSLOT + Q16W_RS_(rB, wc)) * Q8_HALF;                                            \
+        const unsigned char* sMn = lds + Q16W_RS_(rA, 2 + wr) * Q8_HALF;                                                 \
+        const unsigned char* sNn = lds + (NSLOT + Q16W_RS_(rB, 2 + wc)) * Q8_HALF;                                       \
+        Q16W_KSTEP(0, FIRST, 1, 1, sM, sN, 0, 1, (RSV) == 1);                                                            \
+        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");                                                                 \
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); Q16W_SB();                                                    \
+        __builtin_amdgcn_s_barrier(); Q16W_SB();                                                                         \
+        Q16W_KSTEP(1, false, 0, 0, sMn, sNn, 2, 3, (RSV) == 2);                                                          \
+        rA = Q16W_RS_(rA, 2); rB = Q16W_RS_(rB, 2);                                                                      \
+    } while (0)
+
+    // prologue: K tiles 0 and 1 issued, K tile 0 landed and published, its first k-step's fragments read
+    if (!ITEMS) q_cv();
+    if (qv < total) Q16W_ITEM();
+    Q16W_ISSUE_ALL(0); Q16W_ADVANCE(0); Q16W_ISSUE_ALL(1); Q16W_ADVANCE(1); Q16W_ISSUE_ALL(2); Q16W_ADVANCE(2); Q16W_ISSUE_ALL(3); Q16W_ADVANCE(3);
+    Q16W_ISSUE_ALL(0); Q16W_ADVANCE(0); Q16W_ISSUE_ALL(1); Q16W_ADVANCE(1); Q16W_ISSUE_ALL(2); Q16W_ADVANCE(2); Q16W_ISSUE_ALL(3); Q16W_ADVANCE(3);
+    asm volatile("s_waitcnt vmcnt(16)" ::: "memory");   // in flight: K tile 1
+    __builtin_amdgcn_s_barrier();
+    {
+        const unsigned char* sM = lds + wr * Q8_HALF;
+        const unsigned char* sN = lds + (NSLOT + wc) * Q8_HALF;
+        Q16W_RDB(0, 0, 0, sN); Q16W_RDB(0, 0, 1, sN); Q16W_RDB(0, 0, 2, sN); Q16W_RDB(0, 0, 3, sN);
+        Q16W_RDB(0, 0, 4, sN); Q16W_RDB(0, 0, 5, sN); Q16W_RDB(0, 0, 6, sN); Q16W_RDB(0, 0, 7, sN);
+        Q16W_RDA(0, 0, 0, sM); Q16W_RDA(0, 0, 1, sM); Q16W_RDA(0, 0, 2, sM); Q16W_RDA(0, 0, 3, sM);
+        Q16W_RDA(0, 0, 4, sM); Q16W_RDA(0, 0, 5, sM); Q16W_RDA(0, 0, 6, sM); Q16W_RDA(0, 0, 7, sM);
+    }
+    // landed HERE, once: the item loop's three K-loop versions make hipcc copy fragment registers where they meet, and a copy of a
+    // register whose read is still in flight would take the old value (inside the loop every set is named before anything can move it)
+    Q16W_WAIT_SET(0);
+
+    for (int cv = it_beg; cv < total; cv += G) {
+        int cm0, cn0, cz, cnt, cprob = 0;   // ITEMS: cz is the slab index
+        bool rs_on = false;
+        if (ITEMS) {
+            const Q8ItemRec cr = item_at(cv);
+            cm0 = cr.m0; cn0 = cr.n0; cz = cr.slab; cprob = cr.prob; cnt = (cr.kend - cr.kbeg + 63) >> 6;
+            if (ROWSUM) { const q16_i32x8 p_ = prob_half(cr.prob, 1); rs_on = (cr.flags & 1) != 0 && (p_[2] | p_[3]) != 0; }
+        } else {
+            const Q8Item cit = q8_decode<6>(g, cv, total);
+            cm0 = cit.m0; cn0 = cit.n0; cz = cit.z; cnt = cit.nt;
+            if (ROWSUM) rs_on = g.rowsum != nullptr && cit.ncol == 0;
+        }
+        // (each version ends by naming the next item's first fragments, already requested: landed before the versions meet and before the
+        // epilogue's code moves registers around)
+#define Q16W_KLOOP(RSV) do { Q16W_KTILE(true, RSV); _Pragma("unroll 1") for (int t = 1; t < cnt; ++t) Q16W_KTILE(false, RSV); Q16W_WAIT_SET(0); } while (0)
+        if (ROWSUM && rs_on) {   // (wave-uniform: the item and the wave column)
+#pragma unroll
+            for (int I = 0; I < 8; ++I) rs[I] = 0.f;
+            if (wc == 0) Q16W_KLOOP(1); else Q16W_KLOOP(2);
+        } else {
+            Q16W_KLOOP(0);
+        }
+#undef Q16W_KLOOP
+        if (ROWSUM) {
+            if (rs_on) {
+                if (ITEMS) {
+                    const q16_i32x8 p_ = prob_half(cprob, 1);
+                    rowsum_flush(cm0, __int_as_float(__builtin_amdgcn_readfirstlane(p_[6])), (const float*)ptr_of(p_[4], p_[5]), (float*)ptr_of(p_[2], p_[3]),
+                                 __builtin_amdgcn_readfirstlane(p_[0]));
+                } else rowsum_flush(cm0, g.alpha_out, g.alpha_dev_out, g.rowsum, g.M);
+            }
+        }
+        store_block(cm0, cn0, cz, std::integral_constant<int, 0>()); store_block(cm0, cn0, cz, std::integral_constant<int, 1>());
+        store_block(cm0, cn0, cz, std::integral_constant<int, 2>()); store_block(cm0, cn0, cz, std::integral_constant<int, 3>());
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the exhausted stream's zero-length loads still write their (zero) pieces into this workgroup's LDS
+#undef Q16W_ITEM
+#undef Q16W_ISSUE1
+#undef Q16W_ISSUE_ALL
+#undef Q16W_ADVANCE
+#undef Q16W_SB
+#undef Q16W_RDA
+#undef Q16W_RDB
+#undef Q16W_WAIT_SET
+#undef Q16W_MFMA
+#undef Q16W_RS
+#undef Q16W_SLOT
+#undef Q16W_PAIR
+#undef Q16W_PAIR4
+#undef Q16W_KSTEP
+#undef Q16W_RS_
+#undef Q16W_KTILE
+}
+
+// per-layer weight gradient (split-K slabs or C) / grouped weight gradients (`g` only keeps the unused set-up code in range)
+template <bool ROWSUM>
+__global__ __launch_bounds__(256) void gemm_bf16_q16_wgrad_kernel(GemmArgs g) {
+    Q8Group none;   // never read in this form
+    q16w_body<ROWSUM, false>(g, none);
+}
+template <bool ROWSUM>
+__global__ __launch_bounds__(256) void gemm_bf16_q16_wgrad_items_kernel(GemmArgs g, Q8Group GR) {
+    q16w_body<ROWSUM, true>(g, GR);
 }

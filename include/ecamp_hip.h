@@ -121,6 +121,9 @@ int ecamp_set_option(const char* name, int32_t value);
  * with a plain / bias / residual epilogue, 256 x 256 or 256 x 192 tiles).  0 never; 1 (default) where the 192-column tile removes idle
  * last-round time -- the model's 768-wide outputs; 2 every eligible call; 3 as 2 whatever the size (tests); any other value back to
  * the environment.
+ * "q16_wgrad" (env ECAMP_Q16_WGRAD): the weight-gradient form of that kernel (both operands strided; per-layer and grouped launches).
+ * 0 never; 1 (default) every grouped launch and the per-layer launches the size rule selects whose output is at least 256 x 256 --
+ * nothing while "q16_mode" is 0; 2 wherever legal, whatever the size (lab, tests); any other value back to the environment.
  * "attn_head" (env ECAMP_ATTN_HEAD): 1 (default) one workgroup per (batch, head) with everything resident in LDS for sequences
  * that fit (<= 256 tokens here), 0 the 64-row streaming kernels for every length, negative back to the environment's choice */
 
