@@ -955,11 +955,24 @@ def _q16_count():
 @pytest.mark.parametrize("M,N,K", [(394, 768, 192), (1000, 520, 200), (512, 1536, 136), (300, 2304, 768), (2048, 192, 1088), (777 * 8, 768, 264)])
 def test_gemm_q16_forward_and_data_gradient_ragged(dev, q16_always, M, N, K):
     """The four-wave v_mfma_f32_16x16x32_bf16 kernel (csrc/gemm_q16.h) forced on ragged shapes: forward form y = x w^T + b (+ residual) and
-    data-gradient form dx = dy w (+ residual) against fp32 PyTorch -- edge tiles in M and N (both the 256- and the 192-column tile are
-    picked by the shapes: N = 768 / 192 / 1536 take 192, N = 520 / 2304 take 256), partial last K tiles, one tile per workgroup and several;
-    the launch counter proves the kernel ran."""
+    data-gradient form dx = dy w (+ residual) against fp32 PyTorch -- edge tiles in M and N, partial last K tiles, one tile per workgroup
+    and several.  EVERY shape here, forward and data gradient, takes the 192-column tile: both widths need one round of 256 CUs, and
+    q16_cost prices a 192-column tile at 0.79 of a 256-column one (the 256-column form: tests/test_gemm_float64_gpu.py).  The launch
+    counter proves the kernel ran, the profiler tag its tile width."""
+    import ctypes
+    from ecamp_amd import _lib
+    from _gemm_ref import route
     o = ops()
     dt = h16()
+    lib = _lib.load()
+    ncu = torch.cuda.get_device_properties(dev).multi_processor_count
+    widths = {route("f", M, N, K, "bf16", "bias", force="q16", ncu=ncu, pad=0)[1]}
+    if K % 8 == 0 and N % 8 == 0:
+        widths.add(route("d", M, K, N, "bf16", "plain", force="q16", ncu=ncu, pad=0)[1])
+    if ncu == 256:
+        assert widths == {192}
+    lib.ecamp_prof_collect(-1, None, None, None)
+    lib.ecamp_prof_enable(1)
     x = rnd(gen(M, K, seed=1), dt)
     w = rnd(gen(N, K, seed=2) * K ** -0.5, dt)
     b = gen(N, seed=3)
@@ -968,20 +981,33 @@ def test_gemm_q16_forward_and_data_gradient_ragged(dev, q16_always, M, N, K):
     resx = rnd(gen(M, K, seed=6), dt)
     xd, wd, bd, rd, dyd, rxd = x.to(dev, dt), w.to(dev, dt), b.to(dev), res.to(dev, dt), dy.to(dev, dt), resx.to(dev, dt)
     n0 = _q16_count()
-    y0 = o.linear_fwd(xd, wd, bd)
-    y1 = o.linear_fwd(xd, wd, bd, residual=rd)
-    y2 = o.linear_fwd(xd, wd)
-    check("q16 fwd + bias", y0, x @ w.T + b, 2e-2)
-    check("q16 fwd + bias + residual", y1, x @ w.T + b + res, 2e-2)
-    check("q16 fwd plain", y2, x @ w.T, 2e-2)
-    if K % 8 == 0 and N % 8 == 0:
-        d0 = o.linear_dgrad(dyd, wd)
-        d1 = o.linear_dgrad(dyd, wd, residual=rxd)
-        check("q16 dgrad", d0, dy @ w, 2e-2)
-        check("q16 dgrad + residual", d1, dy @ w + resx, 2e-2)
-        assert _q16_count() - n0 == 5
-    else:
-        assert _q16_count() - n0 == 3
+    try:
+        y0 = o.linear_fwd(xd, wd, bd)
+        y1 = o.linear_fwd(xd, wd, bd, residual=rd)
+        y2 = o.linear_fwd(xd, wd)
+        check("q16 fwd + bias", y0, x @ w.T + b, 2e-2)
+        check("q16 fwd + bias + residual", y1, x @ w.T + b + res, 2e-2)
+        check("q16 fwd plain", y2, x @ w.T, 2e-2)
+        if K % 8 == 0 and N % 8 == 0:
+            d0 = o.linear_dgrad(dyd, wd)
+            d1 = o.linear_dgrad(dyd, wd, residual=rxd)
+            check("q16 dgrad", d0, dy @ w, 2e-2)
+            check("q16 dgrad + residual", d1, dy @ w + resx, 2e-2)
+            assert _q16_count() - n0 == 5
+        else:
+            assert _q16_count() - n0 == 3
+        torch.cuda.synchronize()
+    finally:
+        lib.ecamp_prof_enable(0)
+    buf = ctypes.create_string_buffer(int(lib.ecamp_prof_dump(None, 0)) + 16)
+    lib.ecamp_prof_dump(buf, len(buf))
+    lib.ecamp_prof_collect(-1, None, None, None)
+    tags = [ln.split() for ln in buf.value.decode().splitlines() if ln.strip()]
+    assert sum(int(t[1]) for t in tags) == _q16_count() - n0, tags
+    for t in tags:       # name:form:e<epi>:M:N:K:w<tile width>
+        f = t[0].split(":")
+        assert f[0] == "q16" and f[6] == "w%d" % route(f[1], int(f[3]), int(f[4]), int(f[5]), "bf16", "plain", force="q16", ncu=ncu, pad=0)[1], t
+        assert f[6] == "w192" or ncu != 256, t
 
 
 @pytest.mark.usefixtures("both_halves")
