@@ -40,6 +40,9 @@ typedef void (*AttnKernel)(AttnArgs);
 struct AttnLaunch {
     AttnFamily family;
     int n, block;   // launches; threads per workgroup
+    // what the profiler tag says beside the call's shape (attn_tag, attention.hip): the KCH the kernel is instantiated on (-1: it has none),
+    // FLAGS (key mask or dropout), and whether saved dropout bits are written (forward) or read (backward) -- head-resident kernels only
+    int kch, flags, bits;
     // lds: dynamic LDS of this call.  optin: the size the kernel is allowed once, at its first launch, if it is more than 48 KB (0: never) --
     // for the head kernels the largest size any later call may ask for, not this call's.
     struct Kernel { AttnKernel fn; dim3 grid; size_t lds, optin; } k[2];

@@ -548,12 +548,13 @@ static int attn_check(const AttnArgs& a, int hd, int dtype, bool bwd) {
 }
 
 template <int HD>
-static AttnLaunch select_f32(int B, int H, int Tq, int Tk, bool backward) {
+static AttnLaunch select_f32(int B, int H, int Tq, int Tk, bool flags, bool backward) {
     AttnLaunch l = {};
     l.family = ATTN_F32;
     l.n = backward ? 2 : 1;
     l.block = 256;
-    const int kch = attn_kch(Tk);
+    l.flags = flags;
+    const int kch = l.kch = attn_kch(Tk);
     if (kch == 0) {   // more than 256 keys: one wave per query (dK / dV: key) row, static LDS
         const dim3 qrows((unsigned)(((long)B * H * Tq + 3) / 4)), krows((unsigned)(((long)B * H * Tk + 3) / 4));
         l.k[0] = {backward ? attn_long_bwd_dq_kernel<HD> : attn_long_fwd_kernel<HD>, qrows, 0, 0};
@@ -576,8 +577,15 @@ static AttnLaunch select_f32(int B, int H, int Tq, int Tk, bool backward) {
 // Which kernel(s) serve a shape under the current options (ECAMP_ATTN_HEAD, ECAMP_ATTN_WAVES): no side effect, nothing is launched.
 // Only float instantiates the kernels of this file: every 16-bit shape has a kernel in attention_bf16.hip (any key length).
 static AttnLaunch attn_select(int B, int H, int Tq, int Tk, int hd, int dtype, bool mask_or_dropout, bool bits, bool backward) {
-    if (dtype == ECAMP_F32) return ATTN_HD_SWITCH(hd, select_f32, B, H, Tq, Tk, backward);
+    if (dtype == ECAMP_F32) return ATTN_HD_SWITCH(hd, select_f32, B, H, Tq, Tk, mask_or_dropout, backward);
     return attn16_select(B, H, Tq, Tk, hd, mask_or_dropout, bits, backward);
+}
+// The profiler tag of one call, from what attn_select answered and the call's shape alone:
+// attn:<head|resident|stream|long|f32>:<f|b>:<hd>:<Tq>:<Tk>:k<KCH or ->F<FLAGS>b<saved dropout bits written / read>w<waves per workgroup>
+static void attn_tag(char (&tag)[40], const AttnLaunch& l, bool backward, int hd, int Tq, int Tk) {
+    static const char* const name[] = {"head", "resident", "stream", "long", "f32"};
+    snprintf(tag, sizeof tag, "attn:%s:%c:%d:%d:%d:k%cF%db%dw%d", name[l.family], backward ? 'b' : 'f', hd, Tq, Tk,
+             l.kch < 0 ? '-' : (char)('0' + l.kch), l.flags, l.bits, l.block / 64);
 }
 
 static void stride3(long& sb, long& st, long& sh, const int64_t* s) {
@@ -625,8 +633,13 @@ extern "C" int ecamp_attn_fwd(const void* q, const void* k, const void* v, void*
                                  o_strides, nullptr, nullptr, nullptr, nullptr, scale, drop_p, seed, offset, bits ? drop_mask : nullptr);
     if (int rc = attn_check(a, hd, dtype, false)) return rc;
     const bool prof = ecamp_prof_active();
-    if (prof) ecamp_prof_begin(ECAMP_PROF_ATTN, 4.0 * B * H * (double)Tq * Tk * hd, stream);
-    attn_launch(attn_select(B, H, Tq, Tk, hd, dtype, key_mask != nullptr || drop_p > 0.f, a.drop_bits != nullptr, false), a, stream);
+    const AttnLaunch l = attn_select(B, H, Tq, Tk, hd, dtype, key_mask != nullptr || drop_p > 0.f, a.drop_bits != nullptr, false);
+    if (prof) {
+        char tag[40];
+        attn_tag(tag, l, false, hd, Tq, Tk);
+        ecamp_prof_begin(ECAMP_PROF_ATTN, 4.0 * B * H * (double)Tq * Tk * hd, stream, tag);
+    }
+    attn_launch(l, a, stream);
     if (prof) ecamp_prof_end(stream);
     ECAMP_LAUNCH_CHECK();
     return 0;
@@ -648,8 +661,13 @@ extern "C" int ecamp_attn_bwd(const void* q, const void* k, const void* v, const
                                  do_strides, dq_strides, dk_strides, dv_strides, scale, drop_p, seed, offset, bits ? drop_mask : nullptr);
     if (int rc = attn_check(a, hd, dtype, true)) return rc;
     const bool prof = ecamp_prof_active();
-    if (prof) ecamp_prof_begin(ECAMP_PROF_ATTN, 8.0 * B * H * (double)Tq * Tk * hd, stream);
-    attn_launch(attn_select(B, H, Tq, Tk, hd, dtype, key_mask != nullptr || drop_p > 0.f, a.drop_bits != nullptr, true), a, stream);
+    const AttnLaunch l = attn_select(B, H, Tq, Tk, hd, dtype, key_mask != nullptr || drop_p > 0.f, a.drop_bits != nullptr, true);
+    if (prof) {
+        char tag[40];
+        attn_tag(tag, l, true, hd, Tq, Tk);
+        ecamp_prof_begin(ECAMP_PROF_ATTN, 8.0 * B * H * (double)Tq * Tk * hd, stream, tag);
+    }
+    attn_launch(l, a, stream);
     if (prof) ecamp_prof_end(stream);
     ECAMP_LAUNCH_CHECK();
     return 0;

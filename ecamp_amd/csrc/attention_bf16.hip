@@ -1064,11 +1064,14 @@ static AttnLaunch select16(int B, int H, int Tq, int Tk, bool flags, bool bits, 
     AttnLaunch l = {};
     l.n = 1;
     l.block = 256;
+    l.kch = -1;
+    l.flags = flags;
     const int nqt = (Tq + 15) / 16, nkt = (Tk + 15) / 16;
     const size_t head = head_lds_bytes(Tq, Tk, HD, backward, bits);
     // ECAMP_ATTN_HEAD=0 keeps the 64-row streaming kernels (A/B measurements)
     if (ecamp_opt(OPT_ATTN_HEAD) != 0 && head <= LDS_MAX) {
         l.family = ATTN_HEAD;
+        l.bits = bits;
         // backward, four waves: two (hd = 128: the register file) to five workgroups share a CU and one's staging overlaps another's tile loops
         // (T = 197, hd = 32: 230 us against 260 us with eight; T = 128, hd = 128: 147 against 161)
         l.block = 64 * (backward ? head_waves(nkt > nqt ? nkt : nqt, 4) : head_waves(nqt, 8));
@@ -1087,6 +1090,7 @@ static AttnLaunch select16(int B, int H, int Tq, int Tk, bool flags, bool bits, 
         // They regenerate the dropout mask from the Philox counters: saved bits (drop_bits) are not read here.
         l.family = ATTN_STREAM;
         l.n = 2;
+        l.kch = kch;
         const AttnKernel dq = kch == 1 ? attn16_bwd_dq_kernel<HD, 1> : kch == 2 ? attn16_bwd_dq_kernel<HD, 2> : kch == 4 ? attn16_bwd_dq_kernel<HD, 4>
                                                                                                                        : attn16_bwd_dq_kernel<HD, 0>;
         l.k[0] = {dq, qgrid, stream, 0};
@@ -1103,6 +1107,7 @@ static AttnLaunch select16(int B, int H, int Tq, int Tk, bool flags, bool bits, 
     // Tk <= 128 is kch 1 or 2, at most 2 * 2 * 64 * 288 + 8192 = 81920 B (hd 128) < LDS_MAX: the resident forward always fits, so there is
     // neither a four-chunk instantiation of it nor a 64-row kernel behind it.
     l.family = ATTN_RESIDENT_FWD;
+    l.kch = kch;
     const size_t shm = (size_t)2 * kch * TileCfg<HD>::BYTES + 4 * 2048;
     l.k[0] = {kch == 1 ? attn16r_fwd_kernel<HD, 1> : attn16r_fwd_kernel<HD, 2>, dim3(B * H), shm, shm};
     return l;

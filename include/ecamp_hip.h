@@ -526,7 +526,12 @@ int64_t ecamp_wgrad_group_launches(void);
 int64_t ecamp_gemm_f8_q8_launches(void);
 int64_t ecamp_gemm_q16_launches(void);   /* GEMM calls routed to the four-wave 16x16x32 kernel (csrc/gemm_q16.h) so far */
 int64_t ecamp_attn_head_launches(void);
-int64_t ecamp_prof_dump(char* buf, int64_t cap);   /* per (form, epilogue, shape) totals of the profiled GEMM launches: "<tag> <n> <ms> <flop>" lines */
+/* per-tag totals of the profiled launches, "<tag> <n> <ms> <flop>" lines.  GEMM tags: name:form:e<epi>:M:N:K:<w tile | s split> (per form,
+ * epilogue and shape).  Attention tags say which kernel family served the call:
+ *   attn:<head|resident|stream|long|f32>:<f|b>:<hd>:<Tq>:<Tk>:k<KCH>F<FLAGS>b<bits>w<waves>
+ * f / b = forward / backward call; KCH = the 64-key chunks the kernel is instantiated on (0: more than 256 keys, -: the family has
+ * none); FLAGS = key mask or dropout; bits = the saved dropout bits are written (f) or read (b); waves per workgroup. */
+int64_t ecamp_prof_dump(char* buf, int64_t cap);
 #endif
 
 #ifdef __cplusplus

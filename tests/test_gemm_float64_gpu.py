@@ -67,7 +67,7 @@ def _tags():
     n = int(lib.ecamp_prof_dump(None, 0))
     buf = ctypes.create_string_buffer(n + 16)
     lib.ecamp_prof_dump(buf, len(buf))
-    return [ln.split()[0] for ln in buf.value.decode().splitlines() if ln.strip()]
+    return [ln.split()[0] for ln in buf.value.decode().splitlines() if ln.strip() and not ln.startswith("attn:")]   # attention tags its launches too
 
 
 def _ncu(dev):

@@ -197,6 +197,10 @@ def test_layernorm_dropout_consistency(dev, dtype):
 
 
 # ------------------------------------------------------------------------------------------------ attention
+# The tests below hold one max-norm figure per tensor, on dense buffers, and do not say which kernel family served a shape (the
+# head-resident one by default where it fits LDS).  Every element against float64, operands between NaN / pattern guards and the proof of
+# the kernel that ran are in tests/test_attn_float64_gpu.py; what stays here and nowhere else: head-resident against streaming kernels,
+# bit-identical gradients from saved and regenerated dropout masks at the production head counts, the dropout statistics.
 def ref_attn(q, k, v, scale, key_mask=None):
     # q [B,H,Tq,hd], k/v [B,H,Tk,hd]
     s = (q @ k.transpose(-1, -2)) * scale
@@ -875,7 +879,9 @@ def test_attention_long_sequence_f32(dev, B, H, Tq, Tk, hd, masked):
 @pytest.mark.usefixtures("both_halves")
 @pytest.mark.parametrize("B,H,Tq,Tk,hd,masked", [(1, 16, 785, 785, 32, False), (2, 4, 300, 300, 64, True), (1, 3, 70, 520, 128, False)])
 def test_attention_long_sequence_bf16(dev, B, H, Tq, Tk, hd, masked):
-    """Tk > 256 (ViT-L/16 at 448^2: decoder sequence 785) runs the online-softmax forward and the chunk-streaming backward."""
+    """Tk > 256 (ViT-L/16 at 448^2: decoder sequence 785).  Under the default switches only (70, 520, hd 128) runs the online-softmax
+    forward and the chunk-streaming backward: 785 keys of hd 32 (105 600 B) and 300 of hd 64 (83 200 B) fit a CU's LDS and run the
+    head-resident kernels (head_lds_bytes; tests/test_attn_float64_gpu.py proves the family of each of its cases by the profiler tag)."""
     o = ops()
     dtype = h16()
     D = H * hd
