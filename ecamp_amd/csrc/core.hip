@@ -34,8 +34,6 @@ static OptRow g_opts[OPT_COUNT] = {
     // the eight-wave persistent kernel: -1 automatic, 0 never, 2 whenever legal.  Quirk, kept: a value other than 0 or 2 means AUTOMATIC,
     // not "the environment's value" -- once the option has been set, ECAMP_GEMM_Q8 is no longer consulted
     /* OPT_Q8_MODE */          {"q8_mode", "ECAMP_GEMM_Q8", -1, [](int v) { return v == 0 || v == 2 ? v : -1; }},
-    // development A/B mask of the forms on the lean operand stream (gemm.hip, q8_pick); negative: back to the environment
-    /* OPT_Q8_SCH */           {"q8_sch", "ECAMP_Q8_SCH", 7, [](int v) { return v >= 0 ? v : OPT_ENV; }},
     // the four-wave kernel: 0 never, 1 where the 192-column tile pays, 2 every eligible call, 3 (tests) as 2 whatever the size
     /* OPT_Q16_MODE */         {"q16_mode", "ECAMP_Q16", 1, [](int v) { return v >= 0 && v <= 3 ? v : OPT_ENV; }},
     // the four-wave kernel's weight-gradient form (gemm_q16.h, q16w_body): 0 never, 1 the classes the measurements keep (gemm.hip,
@@ -48,14 +46,12 @@ static OptRow g_opts[OPT_COUNT] = {
     /* OPT_P8_WGRAD */         {"p8_wgrad", nullptr, 1, [](int v) { return v ? 1 : 0; }},   // 0: weight gradients stay off the persistent kernel
     /* OPT_P8_WGRAD_RESERVE */ {"p8_wgrad_reserve_cus", nullptr, 0, [](int v) { return v < 0 ? 0 : v; }},   // CUs the backward-pass forms leave free
     /* OPT_WGRAD_ITEMS */      {nullptr, "ECAMP_WGRAD_ITEMS", 0, nullptr},       // work items a weight-gradient split is chosen for; 0 = CU count
-    /* OPT_WGRAD_PLAN */       {nullptr, "ECAMP_WGRAD_PLAN", 1, nullptr},        // grouped weight gradients: 1 segment-major plan, 0 the round-2 dealing
     /* OPT_WGRAD_GROUP_CUS */  {nullptr, "ECAMP_WGRAD_GROUP_CUS", 0, nullptr},   // workgroups of the grouped launch; 0 = 3/4 of the CUs, capped by the reserve
     /* OPT_GEMM_GRID_CAP */    {nullptr, "ECAMP_GEMM_GRID_CAP", 0, nullptr},     // development: CU count the persistent GEMMs assume (>= 32, below the real one)
     // 1 head-resident attention kernels, 0 the 64-row streaming kernels for every length; negative: back to the environment
     /* OPT_ATTN_HEAD */        {"attn_head", "ECAMP_ATTN_HEAD", 1, [](int v) { return v < 0 ? OPT_ENV : v ? 1 : 0; }},
     /* OPT_ATTN_WAVES */       {nullptr, "ECAMP_ATTN_WAVES", 0, nullptr},        // > 0: cap of the waves per head-kernel workgroup (tuning)
     /* OPT_LN_BWD */           {nullptr, "ECAMP_LN_BWD", 0, nullptr},            // development: 1 = the 4-wide LayerNorm backward forms only
-    /* OPT_CE_KERNEL */        {nullptr, "ECAMP_CE_KERNEL", 1, nullptr},         // development A/B: 0 = the two-exp cross-entropy kernel of round 2
     /* OPT_SR_BLOCKS */        {nullptr, "ECAMP_SR_BLOCKS", 512, nullptr},       // development: grid of the paired super-resolution backward (two workgroups per CU)
 };
 int ecamp_opt_default(EcampOpt id) { return g_opts[id].def; }

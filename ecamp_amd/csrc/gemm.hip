@@ -699,18 +699,13 @@ static int q8_epi(const GemmArgs& g, bool res32) {
     if (g.residual) return 2;
     return 0;
 }
-// switch "q8_sch" picks the operand stream of each form (gemm_q8.h SCH = 1: the lean stream)
 static gemm_fn q8_pick(int a_kc, int b_kc, int epi, bool rowsum) {
-    const int sch = ecamp_opt(OPT_Q8_SCH);
-#define Q8S(A, B, E, R) ((gemm_fn)gemm_bf16_q8_kernel<A, B, E, 0, R, 1>)
-    if (a_kc && b_kc && (sch & 1)) return epi == 0 ? Q8S(true, true, 0, false) : epi == 1 ? Q8S(true, true, 1, false) : epi == 2 ? Q8S(true, true, 2, false) :
-                                          epi == 5 ? Q8S(true, true, 5, false) : (gemm_fn) nullptr;
-    if (a_kc && !b_kc && (sch & 2)) return epi == 0 ? Q8S(true, false, 0, false) : epi == 2 ? Q8S(true, false, 2, false) : epi == 3 ? Q8S(true, false, 3, false) : (gemm_fn) nullptr;
-    if (!a_kc && !b_kc && epi == 4 && (sch & 4)) return rowsum ? Q8S(false, false, 4, true) : Q8S(false, false, 4, false);
+#define Q8S(A, B, E, R) ((gemm_fn)gemm_bf16_q8_kernel<A, B, E, 0, R>)
+    if (a_kc && b_kc) return epi == 0 ? Q8S(true, true, 0, false) : epi == 1 ? Q8S(true, true, 1, false) : epi == 2 ? Q8S(true, true, 2, false) :
+                             epi == 5 ? Q8S(true, true, 5, false) : (gemm_fn) nullptr;
+    if (a_kc && !b_kc) return epi == 0 ? Q8S(true, false, 0, false) : epi == 2 ? Q8S(true, false, 2, false) : epi == 3 ? Q8S(true, false, 3, false) : (gemm_fn) nullptr;
+    if (!a_kc && !b_kc && epi == 4) return rowsum ? Q8S(false, false, 4, true) : Q8S(false, false, 4, false);
 #undef Q8S
-    if (a_kc && b_kc) return epi == 0 ? gemm_bf16_q8_kernel<true, true, 0> : epi == 1 ? gemm_bf16_q8_kernel<true, true, 1> : epi == 2 ? gemm_bf16_q8_kernel<true, true, 2> : (gemm_fn) nullptr;
-    if (a_kc && !b_kc) return epi == 0 ? gemm_bf16_q8_kernel<true, false, 0> : epi == 2 ? gemm_bf16_q8_kernel<true, false, 2> : epi == 3 ? gemm_bf16_q8_kernel<true, false, 3> : (gemm_fn) nullptr;
-    if (!a_kc && !b_kc && epi == 4) return rowsum ? gemm_bf16_q8_kernel<false, false, 4, 0, true> : gemm_bf16_q8_kernel<false, false, 4, 0, false>;
     return nullptr;
 }
 // `g` as gemm_call fills it (nsplit = the rounded split count, partial = the split-K workspace)
@@ -1080,13 +1075,11 @@ static const WgPlan* wg_plan(int n, const int64_t* n_out, const int64_t* k_in, c
             for (int nb = 0; nb < ceil_div(k_in[p], 256); ++nb) tiles.push_back({p, mb * 256, nb * 256, 0, 0});
     std::vector<Q8ItemRec>& items = pl.items;
     std::vector<int>& first = pl.first;
-    // ECAMP_WGRAD_PLAN=0: the round-2 dealing (K tiles of all tiles dealt out evenly in tile order; ranges run across tile boundaries)
-    const int plan_mode = ecamp_opt(OPT_WGRAD_PLAN);
     const long T = (long)tiles.size();
     const int cap = p8_bwd_cus();                     // workgroups the launch may use: every CU, minus the data-parallel reserve
     long S = (ncu + T / 2) / T;                       // K segments per tile: one (tile, segment) piece per workgroup
     while (S > 1 && (T * S > cap || KT / S < 4)) --S;
-    if (plan_mode == 1 && S >= 1 && T * S >= ncu / 2 && T * S <= cap) {
+    if (S >= 1 && T * S >= ncu / 2 && T * S <= cap) {
         // Segment-major plan: every output tile is cut into the same S contiguous K segments and each workgroup owns ONE piece.  The
         // pieces are ordered (segment, tile) and workgroup w -- which the hardware places on XCD w % 8 -- takes piece
         // (w % 8) * P/8 + w / 8: the ~P/8 workgroups of an XCD start together on neighbouring tiles of the SAME K segment, walk the
@@ -1108,7 +1101,8 @@ static const WgPlan* wg_plan(int n, const int64_t* n_out, const int64_t* k_in, c
             items.push_back({Tt.prob, Tt.m0, Tt.n0, (int)(k0 * 64), (int)kend, (int)(t * S + seg), (Tt.n0 == 0 && has_bias[Tt.prob]) ? 1 : 0, 0});
         }
     } else {
-    // the unit of the dealing is a PAIR of K tiles (a tile's last unit also takes its odd K tile, if it has one: 197 K tiles for the
+    // The dealing (e.g. more tiles than workgroups): K tiles of all tiles dealt out evenly in tile order; ranges run across tile boundaries.
+    // The unit of the dealing is a PAIR of K tiles (a tile's last unit also takes its odd K tile, if it has one: 197 K tiles for the
     // 12608 rows of ViT-L/448): every piece has >= 2 K tiles, whatever the row count
     const long U = KT / 2;
     const long units = (long)tiles.size() * U;
@@ -1225,11 +1219,9 @@ extern "C" int ecamp_wgrad_group(int32_t n, const void* const* dy, const void* c
     GemmArgs g = gemm_args(dy[0], x[0], ws, n_out[0], k_in[0], rows, n_out[0], k_in[0], k_in[0]);
     g.out_f32 = 1; g.alpha_out = alpha; g.nbm = 1; g.nbn = 1; g.wide = 1; g.partial = ws;
     typedef void (*q8i_fn)(GemmArgs, Q8Group);
-    const bool lean = (ecamp_opt(OPT_Q8_SCH) & 8) != 0;
     const bool four = q16_wgrad_on(Q16W_GROUPED);   // the four-wave kernel fills the slabs (same table, same slabs, same reduce)
     const q8i_fn fn = four ? (any_bias ? (q8i_fn)gemm_bf16_q16_wgrad_items_kernel<true> : (q8i_fn)gemm_bf16_q16_wgrad_items_kernel<false>)
-                    : any_bias ? (lean ? (q8i_fn)gemm_bf16_q8_items_kernel<true, 1> : (q8i_fn)gemm_bf16_q8_items_kernel<true, 0>)
-                               : (lean ? (q8i_fn)gemm_bf16_q8_items_kernel<false, 1> : (q8i_fn)gemm_bf16_q8_items_kernel<false, 0>);
+                    : any_bias ? (q8i_fn)gemm_bf16_q8_items_kernel<true> : (q8i_fn)gemm_bf16_q8_items_kernel<false>;
     double work = 0.0;
     for (int p = 0; p < n; ++p) work += 2.0 * (double)n_out[p] * (double)k_in[p] * (double)rows;
     const bool prof = ecamp_prof_active();

@@ -9,9 +9,8 @@
 //    four K tiles takes exactly as long as the burst) -- so the epilogue is the plain burst.
 //  * Operand tiles are HALF-TILES of 128 rows x 64 k (16 KB: A_0/A_1 = rows of wave row 0/1, B_0/B_1 = columns of wave columns
 //    0-1 / 2-3) in two rings of 5 slots (all 160 KB of LDS = 2.5 K tiles).  They are filled by buffer_load_dwordx4 ... lds through
-//    per-half-tile descriptors built with scalar ALU only (per-lane offsets are kernel constants; rows / contraction steps past
-//    the end read as zero), one half-tile (2 instructions per wave) per phase, as one flat stream over the workgroup's tiles, and
-//    waited for with a counted s_waitcnt once per K tile.
+//    descriptors kept with scalar ALU only (rows / contraction steps past the end read as zero), one half-tile (2 instructions
+//    per wave) per phase, as one flat stream over the workgroup's tiles, and waited for with a counted s_waitcnt once per K tile.
 //  * PHASE SCHEDULE (round 3).  A K tile is four PHASES (k-steps of 16).  In a phase a wave first LOADS -- the six fragment reads of
 //    this very phase (4 M-side + 2 N-side, one register set), its two DMA instructions, the waits -- then, after a barrier, MULTIPLIES:
 //    its 8 independent MFMAs (4 x 2 tiles of 32x32) back to back at raised priority, then a second barrier.  Wave row 1 runs ONE
@@ -40,10 +39,6 @@ typedef __attribute__((ext_vector_type(4))) short q8_v4s16;
 typedef unsigned int q8_u32x4_t __attribute__((ext_vector_type(4)));
 
 #define Q8_HALF 16384
-#define Q8_GLDS16(SRC, DST) \
-    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(SRC), (void __attribute__((address_space(3)))*)(DST), 16, 0, 0)
-
-static __device__ __attribute__((aligned(16))) unsigned int q8_zero16[4] = {0u, 0u, 0u, 0u};
 
 // one output tile (and split-K slice) of the persistent kernel; every field is wave-uniform
 struct Q8Item {
@@ -73,10 +68,10 @@ __device__ __forceinline__ Q8Item q8_decode(const GemmArgs& g, int v, int total)
 }
 
 // ---- DMA of one half-tile (16 KB = 16 wave pieces of 1 KB; every wave issues pieces `wave` and `8 + wave`) ----------------------
-// buffer_load_dwordx4 ... lds through a buffer descriptor that is rebuilt (scalar ALU only) for every half-tile: base = first
-// element of the half-tile, num_records = bytes from there to the end of the operand's valid range.  The per-lane offsets are
-// computed ONCE per kernel (they only depend on the lane and the leading dimension); rows past the end of the matrix (kc) and
-// contraction rows past kend (oc) fall outside the descriptor and read as zero, so the loop has no clamps and no selects.
+// buffer_load_dwordx4 ... lds through a buffer descriptor (scalar ALU only): base = first element of the half-tile (round-3 stream)
+// or of the K tile's half-tile 0 (lean stream), num_records = bytes from there to the end of the operand's valid range.  The
+// per-lane offsets only depend on the lane and the leading dimension; rows past the end of the matrix (kc) and contraction rows
+// past kend (oc) fall outside the descriptor and read as zero, so the loop has no clamps and no selects.
 //   kc operand P[row*ld + k]: piece = 8 rows x 128 B; LDS position (row, j) holds global 16-B chunk j ^ ((row>>1)&7)
 //   oc operand P[k*ld + row]: half-tile kept as it lies in HBM, 64 k-rows x 256 B; piece = 4 k-rows; position (kr, j) holds
 //                             chunk j ^ ((kr&3)<<2), which puts the four k-rows of a transpose-read block on disjoint banks
@@ -93,20 +88,13 @@ __device__ __forceinline__ unsigned q8_voff(int i, int wave, int lane, long ld) 
         return (unsigned)(((long)kr * ld + oc * 8) * 2);
     }
 }
-// `base`/`rec`: wave-uniform first byte of the half-tile and bytes from there to the end of the valid range (<= 0: nothing valid);
-// `krem`: contraction elements left from this K tile's first column (kc operands: chunks at k >= krem read as zero)
-template <bool KC, int PIECES = 3>
-__device__ __forceinline__ void q8_stage_half(const unsigned char* base, int rec, int krem, unsigned char* dst,
-                                              const unsigned (&voff)[2], int wave, int lane) {
+// one half-tile of a strided operand through a descriptor of its own (the item-table form's stream): `base` / `rec` are the wave-uniform
+// first byte of the half-tile and the bytes from there to the end of the valid range (<= 0: nothing valid)
+__device__ __forceinline__ void q8_stage_half(const unsigned char* base, int rec, unsigned char* dst, const unsigned (&voff)[2], int wave) {
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, rec < 0 ? 0 : rec, 0x00020000);
-    unsigned v0 = voff[0], v1 = voff[1];
-    if (KC && krem < 64) {   // last, partial K tile (uniform branch)
-        const int kc0 = (lane & 7) ^ (((wave * 8 + (lane >> 3)) >> 1) & 7);   // same key for both pieces (64 rows apart)
-        if (kc0 * 8 >= krem) { v0 = 0xFFFFFF00u; v1 = 0xFFFFFF00u; }
-    }
     typedef void __attribute__((address_space(3))) lds_void;
-    if (PIECES & 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(dst + wave * 1024), 16, (int)v0, 0, 0, 0);
-    if (PIECES & 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(dst + 8192 + wave * 1024), 16, (int)v1, 0, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(dst + wave * 1024), 16, (int)voff[0], 0, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(dst + 8192 + wave * 1024), 16, (int)voff[1], 0, 0, 0);
 }
 
 // ---- fragment registers ----------------------------------------------------------------------------------------------------------
@@ -161,16 +149,18 @@ __device__ __forceinline__ q8_u32x4 q8_pack8(const float (&v)[8]) {
     return (q8_u32x4){pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
 }
 
-// DBG bits (development, template parameter): 1 = no MFMA, 2 = no DMA, 4 = no epilogue, 1024 = the epilogue runs but every store / load is out of range (dropped), 8 = no s_setprio, 16 = no barriers in the
-// loop, 32 = no fragment reads, 64 = every DMA re-reads the tile's first K tile (timing decomposition only: 16, 32, 64 give wrong results),
-// 128 / 256 = nt / sc1 output stores, 512 = workgroups start in four phases 9 us apart (lock-step epilogue bursts: the stagger costs what it saves)
+// DBG bits (development, template parameter; tools/gemm_lab): 1 = no MFMA, 2 = no DMA, 4 = no epilogue, 1024 = the epilogue runs but
+// every store / load is out of range (dropped).  Workgroups started in four phases 9 us apart (lock-step epilogue bursts) measured
+// nothing: the stagger costs what it saves.
 // ROWSUM (weight-gradient form only): rowsum[m] += alpha * sum_k opA[m,k] -- the bias gradient -- summed on the VALU from the M-side
 // fragments by the first wave column of the tiles in the first N-tile column, added with 4 buffer atomics per wave and tile.
 // ITEMS (weight-gradient form only): the work items come from a table (Q8Group, gemm_args.h) instead of the tile x split arithmetic;
 // operands and leading dimensions change with the item's problem, every piece stores a dense f32 slab.
-// SCH: 0 = the round-3 stream (descriptors rebuilt per half-tile, bookkeeping spread over the load interval; the item-table form),
-// 1 = lean stream (every other form).  Measured and removed again (profiles/r04_gemm_lab_sch.txt): the lean stream's bookkeeping in the
-// matrix interval (-1..3 %), the DMA issue in the matrix interval as well (= sch 0), two k-steps per phase = four barriers per K tile
+// One operand stream per form, chosen by the form itself: the item-table form keeps the ROUND-3 STREAM below (descriptors rebuilt per
+// half-tile, its bookkeeping spread over the load interval), every other form runs the LEAN STREAM, on which the round-3 stream lost
+// 1-6 % in the forward and weight-gradient forms (profiles/r04_gemm_lab_sch.txt) while the item-table form loses up to 2.9 % on the
+// lean one (profiles/one_stream_refactor.txt).  Measured as well and not kept: the lean stream's bookkeeping in the matrix interval
+// (-1..3 %), the DMA issue in the matrix interval as well (= the round-3 stream), two k-steps per phase = four barriers per K tile
 // instead of eight (+-1 %), and wave-specialised producers -- 8 consumer + 4 producer waves, the whole operand stream in waves of its own
 // (tools/probes/gemm_producer_waves_fragment.hip.txt) -- within 3 % of this kernel on every shape.  Every schedule lands on the same
 // ~1.75 us per 256 x 256 x 64 step: the loop waits for the DATA (the L2 -> LDS path beside a power-limited MFMA stream), not for whoever
@@ -180,16 +170,15 @@ __device__ __forceinline__ q8_u32x4 q8_pack8(const float (&v)[8]) {
 // are the bf16 kernel's byte for byte; a phase is four v_mfma_scale_f32_32x32x64_f8f6f4 (64 matrix-pipe cycles each, block scales
 // 2^0: twice the bf16 rate per byte moved) on one k-step of 64 and one half of the wave's rows, the N-side fragments staying in
 // registers between the two halves.  The per-tensor scales are device scalars multiplied into alpha (alpha_dev, alpha_dev2).
-template <bool A_KC, bool B_KC, int EPI, int DBG, bool ROWSUM, bool ITEMS, int SCH = 0, bool F8 = false>
+template <bool A_KC, bool B_KC, int EPI, int DBG, bool ROWSUM, bool ITEMS, bool F8 = false>
 __device__ __forceinline__ void q8_body(const GemmArgs& g, const Q8Group& GR) {
-    static_assert(!F8 || (A_KC && B_KC && SCH == 1 && !ROWSUM && !ITEMS && DBG == 0), "the e4m3 form is the forward form on the lean stream");
+    static_assert(!F8 || (A_KC && B_KC && !ROWSUM && !ITEMS && DBG == 0), "the e4m3 form is the forward form");
     constexpr int ES = F8 ? 1 : 2;            // bytes per operand element
     constexpr int KT = F8 ? 128 : 64;         // elements per K tile
     constexpr int KT_SHIFT = F8 ? 7 : 6;
     static_assert(!ITEMS || (!A_KC && !B_KC && EPI == 4 && DBG == 0), "the item-table form is the weight-gradient form");
     static_assert(!ROWSUM || (!A_KC && !B_KC && EPI == 4), "rowsum is built for the weight-gradient form");
     constexpr int NSLOT = 5;                          // half-tile slots per operand ring
-    constexpr int ST_AUX = (DBG & 128) ? 2 : (DBG & 256) ? 16 : 0;   // cache policy of the bf16 output stores: 2 = nt, 16 = sc1 (write-through)
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];  // A ring (5 x 16 KB) | B ring (5 x 16 KB); the ONLY LDS object
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 2, wc = wave & 3;
@@ -267,63 +256,44 @@ __device__ __forceinline__ void q8_body(const GemmArgs& g, const Q8Group& GR) {
     }
     f32x16 acc[4][2];
 
-    // ---- DMA cursor over the flat K-tile stream; all of it wave-uniform (SGPRs): byte cursors of the A and B half-tile 0 of the
-    // K tile being staged, bytes left in their valid ranges, contraction elements left in the staged output tile.  The four parts
-    // of a K tile are staged in the order A_0, B_0 ("early": their ring slots were vacated two K tiles ago), A_1, B_1 ("late").
+    // ---- ROUND-3 STREAM (the item-table form).  A DMA cursor over the flat K-tile stream of this workgroup's items; all of it wave-uniform
+    // (SGPRs): byte cursors of the A and B half-tile 0 of the K tile being staged, bytes left in their valid ranges, contraction rows left
+    // in the staged item.  The four parts of a K tile are staged in the order A_0, B_0 ("early": their ring slots were vacated two K tiles
+    // ago), A_1, B_1 ("late"), each through a descriptor rebuilt for its half-tile (half-tile 1 lies 256 bytes behind half-tile 0).
     int pv = it_beg;
-    bool pdone = pv >= total;
+    bool pdone = !ITEMS || pv >= total;
     const unsigned char *sa_base, *sb_base;
     int sa_rec, sb_rec, p_krem;
-    const int a_half = A_KC ? (int)g.lda * 256 : 256;     // bytes from half-tile 0 to half-tile 1 (128 rows)
-    int a_step = A_KC ? 128 : (int)g.lda * 128;   // (ITEMS: follows the staged item's problem)
-    const int b_half = B_KC ? (int)g.ldb * 256 : 256;
+    int a_step = A_KC ? 128 : (int)g.lda * 128;   // bytes from a K tile to the next (ITEMS: follows the staged item's problem)
     int b_step = B_KC ? 128 : (int)g.ldb * 128;
-    long s_lda = ITEMS ? -1 : g.lda, s_ldb = ITEMS ? -1 : g.ldb;   // leading dimensions the per-lane DMA offsets were built for
+    long s_lda = -1, s_ldb = -1;   // leading dimensions the per-lane DMA offsets were built for
     unsigned voffA[2], voffB[2];
-    if (!ITEMS) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) { voffA[i] = q8_voff<A_KC>(i, wave, lane, g.lda); voffB[i] = q8_voff<B_KC>(i, wave, lane, g.ldb); }
-    }
 #define Q8_NEXT_ITEM()                                                                                                   \
     do {                                                                                                                 \
-        if (ITEMS) {                                                                                                     \
-            const Q8ItemRec r_ = item_at(pv);                                                                            \
-            const long la_ = Q8_PROB(r_.prob, lda), lb_ = Q8_PROB(r_.prob, ldb);                                         \
-            const bf16_t* A_ = reinterpret_cast<const bf16_t*>(uniform_ptr(Q8_PROB(r_.prob, A)));                        \
-            const bf16_t* B_ = reinterpret_cast<const bf16_t*>(uniform_ptr(Q8_PROB(r_.prob, B)));                        \
-            p_krem = r_.kend - r_.kbeg;                                                                                  \
-            sa_base = (const unsigned char*)(A_ + ((long)r_.kbeg * la_ + r_.m0)); sa_rec = (int)(((long)p_krem * la_ - r_.m0) * 2); \
-            sb_base = (const unsigned char*)(B_ + ((long)r_.kbeg * lb_ + r_.n0)); sb_rec = (int)(((long)p_krem * lb_ - r_.n0) * 2); \
-            if (la_ != s_lda) { s_lda = la_; a_step = (int)la_ * 128; voffA[0] = q8_voff<A_KC>(0, wave, lane, la_); voffA[1] = q8_voff<A_KC>(1, wave, lane, la_); } \
-            if (lb_ != s_ldb) { s_ldb = lb_; b_step = (int)lb_ * 128; voffB[0] = q8_voff<B_KC>(0, wave, lane, lb_); voffB[1] = q8_voff<B_KC>(1, wave, lane, lb_); } \
-        } else {                                                                                                         \
-        const Q8Item n_ = q8_decode(g, pv, total);                                                                   \
-        p_krem = n_.kend - n_.kbeg;                                                                                      \
-        if (A_KC) { sa_base = (const unsigned char*)(A + ((long)n_.m0 * g.lda + n_.kbeg)); sa_rec = (int)((((long)(g.M - n_.m0)) * g.lda - n_.kbeg) * 2); } \
-        else      { sa_base = (const unsigned char*)(A + ((long)n_.kbeg * g.lda + n_.m0)); sa_rec = (int)(((long)p_krem * g.lda - n_.m0) * 2); }             \
-        if (B_KC) { sb_base = (const unsigned char*)(B + ((long)n_.n0 * g.ldb + n_.kbeg)); sb_rec = (int)((((long)(g.N - n_.n0)) * g.ldb - n_.kbeg) * 2); } \
-        else      { sb_base = (const unsigned char*)(B + ((long)n_.kbeg * g.ldb + n_.n0)); sb_rec = (int)(((long)p_krem * g.ldb - n_.n0) * 2); }             \
-        }                                                                                                                \
+        const Q8ItemRec r_ = item_at(pv);                                                                                \
+        const long la_ = Q8_PROB(r_.prob, lda), lb_ = Q8_PROB(r_.prob, ldb);                                             \
+        const bf16_t* A_ = reinterpret_cast<const bf16_t*>(uniform_ptr(Q8_PROB(r_.prob, A)));                            \
+        const bf16_t* B_ = reinterpret_cast<const bf16_t*>(uniform_ptr(Q8_PROB(r_.prob, B)));                            \
+        p_krem = r_.kend - r_.kbeg;                                                                                      \
+        sa_base = (const unsigned char*)(A_ + ((long)r_.kbeg * la_ + r_.m0)); sa_rec = (int)(((long)p_krem * la_ - r_.m0) * 2); \
+        sb_base = (const unsigned char*)(B_ + ((long)r_.kbeg * lb_ + r_.n0)); sb_rec = (int)(((long)p_krem * lb_ - r_.n0) * 2); \
+        if (la_ != s_lda) { s_lda = la_; a_step = (int)la_ * 128; voffA[0] = q8_voff<A_KC>(0, wave, lane, la_); voffA[1] = q8_voff<A_KC>(1, wave, lane, la_); } \
+        if (lb_ != s_ldb) { s_ldb = lb_; b_step = (int)lb_ * 128; voffB[0] = q8_voff<B_KC>(0, wave, lane, lb_); voffB[1] = q8_voff<B_KC>(1, wave, lane, lb_); } \
     } while (0)
     if (!pdone) Q8_NEXT_ITEM();
     int wA = 0, wB = 0;                                // ring slots the next A / B half-tile goes to
-    // stage pieces PCS (bit 0: piece `wave`, bit 1: piece `8 + wave`) of part PART (0: A_0, 1: B_0, 2: A_1, 3: B_1) of the K tile
-    // being staged; the cursor moves on with the second piece of part 3
-#define Q8_STAGE_PCS(PART, PCS)                                                                                          \
+    // stage part PART (0: A_0, 1: B_0, 2: A_1, 3: B_1) of the K tile being staged; the cursor moves on behind part 3
+#define Q8_STAGE_PART(PART)                                                                                              \
     do {                                                                                                                 \
         if (!pdone) {                                                                                                    \
-            if (!(DBG & 2)) {                                                                                            \
-                if ((PART) == 0) q8_stage_half<A_KC, (PCS)>(sa_base, sa_rec, p_krem, lds + wA * Q8_HALF, voffA, wave, lane);                         \
-                if ((PART) == 1) q8_stage_half<B_KC, (PCS)>(sb_base, sb_rec, p_krem, lds + (NSLOT + wB) * Q8_HALF, voffB, wave, lane);             \
-                if ((PART) == 2) q8_stage_half<A_KC, (PCS)>(sa_base + a_half, sa_rec - a_half, p_krem, lds + wA * Q8_HALF, voffA, wave, lane);       \
-                if ((PART) == 3) q8_stage_half<B_KC, (PCS)>(sb_base + b_half, sb_rec - b_half, p_krem, lds + (NSLOT + wB) * Q8_HALF, voffB, wave, lane); \
-            }                                                                                                            \
-            if ((PCS) & 2) {                                                                                             \
-                if ((PART) == 0 || (PART) == 2) wA = wA == NSLOT - 1 ? 0 : wA + 1; else wB = wB == NSLOT - 1 ? 0 : wB + 1; \
-            }                                                                                                            \
-            if ((PART) == 3 && ((PCS) & 2)) {                                                                            \
+            if ((PART) == 0) q8_stage_half(sa_base, sa_rec, lds + wA * Q8_HALF, voffA, wave);                            \
+            if ((PART) == 1) q8_stage_half(sb_base, sb_rec, lds + (NSLOT + wB) * Q8_HALF, voffB, wave);                  \
+            if ((PART) == 2) q8_stage_half(sa_base + 256, sa_rec - 256, lds + wA * Q8_HALF, voffA, wave);                \
+            if ((PART) == 3) q8_stage_half(sb_base + 256, sb_rec - 256, lds + (NSLOT + wB) * Q8_HALF, voffB, wave);      \
+            if ((PART) == 0 || (PART) == 2) wA = wA == NSLOT - 1 ? 0 : wA + 1; else wB = wB == NSLOT - 1 ? 0 : wB + 1;    \
+            if ((PART) == 3) {                                                                                           \
                 p_krem -= 64;                                                                                            \
-                if (!(DBG & 64)) { sa_base += a_step; sa_rec -= a_step; sb_base += b_step; sb_rec -= b_step; }           \
+                sa_base += a_step; sa_rec -= a_step; sb_base += b_step; sb_rec -= b_step;                                \
                 if (p_krem <= 0) {                                                                                       \
                     pv += G;                                                                                             \
                     if (pv < total) Q8_NEXT_ITEM(); else pdone = true;                                                   \
@@ -331,17 +301,16 @@ __device__ __forceinline__ void q8_body(const GemmArgs& g, const Q8Group& GR) {
             }                                                                                                            \
         }                                                                                                                \
     } while (0)
-#define Q8_STAGE_PART(PART) Q8_STAGE_PCS(PART, 3)
     // every DMA of mine has landed, except that the `N_` youngest vector-memory operations (issued after it) may be pending
 #define Q8_WAIT_DMA(N_) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory")
 
-    // ---- LEAN STREAM (SCH >= 1; round 4).  Counter evidence (profiles/r04_vendor_vs_q8_pmc.txt): the load interval of a phase is the
-    // critical path -- the multiplying wave row waits at the barrier for the loading row, 37-49 % of all wave-cycles are parked -- and two
+    // ---- LEAN STREAM (every other form; round 4): the same stream of parts, all of its state wave-uniform.  Counter evidence
+    // (profiles/r04_vendor_vs_q8_pmc.txt): the load interval of a phase is the critical path -- the multiplying wave row waits at the barrier for the loading row, 37-49 % of all wave-cycles are parked -- and two
     // thirds of its instructions were bookkeeping (3.3x the vendor kernel's SALU, 6x its barrier / wait instructions per tile step).  So:
     //  * ONE descriptor per operand, valid for both half-tiles (the second half-tile is a per-lane offset), ADVANCED per K tile (two adds,
     //    a clamped subtract) instead of rebuilt per half-tile;
     //  * ring positions are LDS byte offsets (wave piece folded in): M0 is one move;
-    //  * no `pdone` tests: an exhausted stream keeps issuing through a descriptor of ZERO records -- nothing is fetched, the slots it
+    //  * no end-of-stream tests: an exhausted stream keeps issuing through a descriptor of ZERO records -- nothing is fetched, the slots it
     //    zero-fills have been consumed (same ring discipline), every counted wait keeps its count, and the kernel drains them before it ends;
     //  * the partial-K lane mask is folded into the per-lane offsets when the stream enters / leaves a tail K tile (twice per item at
     //    most), not evaluated in every part;
@@ -353,7 +322,7 @@ __device__ __forceinline__ void q8_body(const GemmArgs& g, const Q8Group& GR) {
     bool q_tail = false;
     unsigned cvA[4] = {0u, 0u, 0u, 0u}, cvB[4] = {0u, 0u, 0u, 0u};   // per-lane source offsets [half * 2 + piece]
     int dA = wave * 1024, dB = NSLOT * Q8_HALF + wave * 1024;         // LDS byte offset the next A / B half-tile (this wave's first piece) goes to
-    long q_lda = ITEMS ? -1 : g.lda, q_ldb = ITEMS ? -1 : g.ldb;
+    const long q_lda = g.lda, q_ldb = g.ldb;
     auto q_cv = [&](bool tail) __attribute__((always_inline)) {   // (re)build the per-lane offsets for the current leading dimensions; tail: lanes past q_krem read as zero
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -368,30 +337,17 @@ __device__ __forceinline__ void q8_body(const GemmArgs& g, const Q8Group& GR) {
             }
         }
     };
-    // the stream enters item qv.  (A macro, not a lambda: inside a by-reference lambda the Q8_PROB selects become selects between the
-    // ADDRESSES of the captured values, and the argument block ends up as a table in scratch that every item set-up loads from.)
+    // the stream enters output tile qv
 #define Q9_ITEM()                                                                                                        \
     do {                                                                                                                 \
-        if (ITEMS) {                                                                                                     \
-            const Q8ItemRec r_ = item_at(qv);                                                                            \
-            const long la_ = Q8_PROB(r_.prob, lda), lb_ = Q8_PROB(r_.prob, ldb);                                         \
-            const bf16_t* A_ = reinterpret_cast<const bf16_t*>(uniform_ptr(Q8_PROB(r_.prob, A)));                        \
-            const bf16_t* B_ = reinterpret_cast<const bf16_t*>(uniform_ptr(Q8_PROB(r_.prob, B)));                        \
-            q_krem = r_.kend - r_.kbeg;                                                                                  \
-            qa = (const unsigned char*)(A_ + ((long)r_.kbeg * la_ + r_.m0)); qa_rec = (int)(((long)q_krem * la_ - r_.m0) * 2); \
-            qb = (const unsigned char*)(B_ + ((long)r_.kbeg * lb_ + r_.n0)); qb_rec = (int)(((long)q_krem * lb_ - r_.n0) * 2); \
-            a_step = (int)la_ * 128; b_step = (int)lb_ * 128;                                                            \
-            if (la_ != q_lda || lb_ != q_ldb) { q_lda = la_; q_ldb = lb_; q_cv(false); }                                 \
-        } else {                                                                                                         \
-            const Q8Item n_ = q8_decode<KT_SHIFT>(g, qv, total);                                                         \
-            const unsigned char* Ab_ = reinterpret_cast<const unsigned char*>(g.A);                                      \
-            const unsigned char* Bb_ = reinterpret_cast<const unsigned char*>(g.B);                                      \
-            q_krem = n_.kend - n_.kbeg;                                                                                  \
-            if (A_KC) { qa = Ab_ + ((long)n_.m0 * g.lda + n_.kbeg) * ES; qa_rec = (int)((((long)(g.M - n_.m0)) * g.lda - n_.kbeg) * ES); } \
-            else      { qa = Ab_ + ((long)n_.kbeg * g.lda + n_.m0) * ES; qa_rec = (int)(((long)q_krem * g.lda - n_.m0) * ES); }             \
-            if (B_KC) { qb = Bb_ + ((long)n_.n0 * g.ldb + n_.kbeg) * ES; qb_rec = (int)((((long)(g.N - n_.n0)) * g.ldb - n_.kbeg) * ES); } \
-            else      { qb = Bb_ + ((long)n_.kbeg * g.ldb + n_.n0) * ES; qb_rec = (int)(((long)q_krem * g.ldb - n_.n0) * ES); }             \
-        }                                                                                                                \
+        const Q8Item n_ = q8_decode<KT_SHIFT>(g, qv, total);                                                             \
+        const unsigned char* Ab_ = reinterpret_cast<const unsigned char*>(g.A);                                          \
+        const unsigned char* Bb_ = reinterpret_cast<const unsigned char*>(g.B);                                          \
+        q_krem = n_.kend - n_.kbeg;                                                                                      \
+        if (A_KC) { qa = Ab_ + ((long)n_.m0 * g.lda + n_.kbeg) * ES; qa_rec = (int)((((long)(g.M - n_.m0)) * g.lda - n_.kbeg) * ES); } \
+        else      { qa = Ab_ + ((long)n_.kbeg * g.lda + n_.m0) * ES; qa_rec = (int)(((long)q_krem * g.lda - n_.m0) * ES); }             \
+        if (B_KC) { qb = Bb_ + ((long)n_.n0 * g.ldb + n_.kbeg) * ES; qb_rec = (int)((((long)(g.N - n_.n0)) * g.ldb - n_.kbeg) * ES); } \
+        else      { qb = Bb_ + ((long)n_.kbeg * g.ldb + n_.n0) * ES; qb_rec = (int)(((long)q_krem * g.ldb - n_.n0) * ES); }             \
         qa_rec = max(qa_rec, 0); qb_rec = max(qb_rec, 0);                                                                \
     } while (0)
     // issue the two DMA instructions of part PART (0: A half 0, 1: B half 0, 2: A half 1, 3: B half 1) of the K tile being staged
@@ -414,7 +370,7 @@ __device__ __forceinline__ void q8_body(const GemmArgs& g, const Q8Group& GR) {
         else                   { dB += Q8_HALF; if (dB >= 2 * NSLOT * Q8_HALF) dB -= NSLOT * Q8_HALF; }                  \
         if ((PART) == 3) {                                                                                               \
             q_krem -= KT;                                                                                                \
-            if (!(DBG & 64)) { qa += a_step; qb += b_step; qa_rec = max(qa_rec - a_step, 0); qb_rec = max(qb_rec - b_step, 0); } \
+            qa += a_step; qb += b_step; qa_rec = max(qa_rec - a_step, 0); qb_rec = max(qb_rec - b_step, 0);             \
             if (q_krem <= 0) {                                                                                           \
                 qv += G;                                                                                                 \
                 if (qv < total) Q9_ITEM(); else { qa_rec = 0; qb_rec = 0; q_krem = 1 << 30; }                             \
@@ -451,10 +407,8 @@ __device__ __forceinline__ void q8_body(const GemmArgs& g, const Q8Group& GR) {
 #define Q8_RD1(FM, FN, SM, SN, KS, I)                                                                                    \
     do {                                                                                                                 \
         constexpr int isn_ = ((I) == 0 || (I) == 3), idx_ = (I) == 0 ? 0 : (I) == 3 ? 1 : (I) < 3 ? (I) - 1 : (I) - 2;   \
-        if (!(DBG & 32)) {                                                                        \
-            if (isn_) { if (B_KC) FN[idx_].template read<idx_ * 4096>((SN) + offN[KS]); else FN[idx_].template read<(KS) * 4096>((SN) + offN[idx_]); } \
-            else      { if (A_KC) FM[idx_].template read<idx_ * 4096>((SM) + offM[KS]); else FM[idx_].template read<(KS) * 4096>((SM) + offM[idx_]); } \
-        }                                                                                                                \
+        if (isn_) { if (B_KC) FN[idx_].template read<idx_ * 4096>((SN) + offN[KS]); else FN[idx_].template read<(KS) * 4096>((SN) + offN[idx_]); } \
+        else      { if (A_KC) FM[idx_].template read<idx_ * 4096>((SM) + offM[KS]); else FM[idx_].template read<(KS) * 4096>((SM) + offM[idx_]); } \
     } while (0)
 #define Q8_READ_GROUP(FM, FN, SM, SN, KS) \
     do { Q8_RD1(FM, FN, SM, SN, KS, 0); Q8_RD1(FM, FN, SM, SN, KS, 1); Q8_RD1(FM, FN, SM, SN, KS, 2); Q8_RD1(FM, FN, SM, SN, KS, 3); Q8_RD1(FM, FN, SM, SN, KS, 4); Q8_RD1(FM, FN, SM, SN, KS, 5); } while (0)
@@ -636,9 +590,9 @@ __device__ __forceinline__ void q8_body(const GemmArgs& g, const Q8Group& GR) {
                             v[r] = y_[0]; v[r + 1] = y_[1];
                             d_[r] = g_[0]; d_[r + 1] = g_[1];
                         }
-                        __builtin_amdgcn_raw_buffer_store_b128(q8_pack8(d_), rP, up[tm][gq], 0, ST_AUX);
+                        __builtin_amdgcn_raw_buffer_store_b128(q8_pack8(d_), rP, up[tm][gq], 0, 0);
                     } else {
-                    __builtin_amdgcn_raw_buffer_store_b128(q8_pack8(v), rP, up[tm][gq], 0, ST_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b128(q8_pack8(v), rP, up[tm][gq], 0, 0);
 #pragma unroll
                     for (int r = 0; r < 8; r += 2) {   // pair form: packed math (common.h)
                         const f32x2_t y_ = gelu_fast_f2((f32x2_t){rnd<bf16_t>(v[r]), rnd<bf16_t>(v[r + 1])});
@@ -692,7 +646,7 @@ __device__ __forceinline__ void q8_body(const GemmArgs& g, const Q8Group& GR) {
                     __builtin_amdgcn_raw_buffer_store_b128((q8_u32x4){__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])}, rC, uo[tm][gq], 0, 0);
                     __builtin_amdgcn_raw_buffer_store_b128((q8_u32x4){__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7])}, rC, uo[tm][gq] + 16, 0, 0);
                 } else {
-                    __builtin_amdgcn_raw_buffer_store_b128(q8_pack8(v), rC, uo[tm][gq], 0, ST_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b128(q8_pack8(v), rC, uo[tm][gq], 0, 0);
                 }
             }
     };
@@ -725,8 +679,9 @@ __device__ __forceinline__ void q8_body(const GemmArgs& g, const Q8Group& GR) {
         if ((Q) == 3) store_quadrant(TM0, TN0, TZ, I1(), I0());                               \
     } while (0)
 #define Q8_SB() __builtin_amdgcn_sched_barrier(0)
-    // ---- one PHASE = one k-step of 16 of a K tile: [load interval: the six fragment reads of this phase, one half-tile part of DMA,
-    // the waits] barrier [matrix interval: 8 MFMAs back to back at raised priority] barrier.  Wave row 1 runs one barrier behind wave
+    // ---- one PHASE = one k-step of 16 of a K tile: [load interval: the six fragment reads of this phase, the two DMA instructions of
+    // one half-tile part, the bookkeeping behind the part, the waits] barrier [matrix interval at raised priority: MFMA 0-3, (MX_HOOK:
+    // the decode of the next output tile), MFMA 4-7] barrier.  Wave row 1 runs one barrier behind wave
     // row 0, so the two intervals of the two waves of a SIMD alternate (see header).  DMA of K tile t, one part per phase, in stream
     // order: A_1(t+1), B_1(t+1), A_0(t+2), B_0(t+2).  Ring reuse (5 half-tile slots per operand): A_1 / B_1 of K tile u overwrite
     // A_0 / B_0 of K tile u-2, A_0 / B_0 of K tile u the slot of A_1 / B_1 of K tile u-3; the last reads of a slot are retired
@@ -735,46 +690,6 @@ __device__ __forceinline__ void q8_body(const GemmArgs& g, const Q8Group& GR) {
     // a barrier before anyone reads K tile t+1.
     // PRE_HOOK (first phase of an output tile): the previous tile's epilogue -- its accumulators are overwritten by this phase's
     // MFMAs, which start from C = 0 -- and the bias-gradient atomics; all older than the DMA the next wait covers.
-#define Q8_PHASE(KS, DPART, WAIT, ZERO, PRE_HOOK)                                                                     \
-    do {                                                                                                                 \
-        if (PRE_HOOK) {                                                                                                  \
-            if (have_pend) { Q8_STORE_Q(pm0, pn0, pz, 0); Q8_STORE_Q(pm0, pn0, pz, 1); Q8_STORE_Q(pm0, pn0, pz, 2); Q8_STORE_Q(pm0, pn0, pz, 3); } \
-            bias_request(cn0);                                                                                           \
-            if (ROWSUM) { if (rsp_on) rowsum_flush(); }                                                                  \
-            Q8_SB();                                                                                                     \
-        }                                                                                                                \
-        Q8_READ_GROUP(xm, xn, sM, sN, KS); Q8_SB();                                                                      \
-        Q8_STAGE_PART(DPART); Q8_SB();                                                                                   \
-        if (WAIT) { if (pdone) Q8_WAIT_DMA(0); else Q8_WAIT_DMA(4); }   /* in flight: A_0 and B_0 of K tile t+2 */   \
-        if (!A_KC || !B_KC) { q8_wait4(xm); q8_wait2(xn); }                                                              \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); Q8_SB();                                                      \
-        if (!(DBG & 16)) __builtin_amdgcn_s_barrier();                                                                   \
-        Q8_SB();                                                                                                         \
-        if (!(DBG & 8)) __builtin_amdgcn_s_setprio(1);                                                                   \
-        if (ROWSUM) { Q8_RS_ACC(xm); }   /* no scheduling fence: the compiler spreads these between the MFMAs */          \
-        Q8_MFMA1(xm, xn, 0, ZERO); Q8_MFMA1(xm, xn, 1, ZERO); Q8_MFMA1(xm, xn, 2, ZERO); Q8_MFMA1(xm, xn, 3, ZERO);      \
-        Q8_MFMA1(xm, xn, 4, ZERO); Q8_MFMA1(xm, xn, 5, ZERO); Q8_MFMA1(xm, xn, 6, ZERO); Q8_MFMA1(xm, xn, 7, ZERO);      \
-        Q8_SB();                                                                                                         \
-        if (!(DBG & 8)) __builtin_amdgcn_s_setprio(0);                                                                   \
-        if (!(DBG & 16)) __builtin_amdgcn_s_barrier();                                                                   \
-        Q8_SB();                                                                                                         \
-    } while (0)
-#define Q8_KTILE(FIRST)                                                                                               \
-    do {                                                                                                                 \
-        const int ra_ = rA + wr, rb_ = rB + (wc >> 1);                                                                   \
-        const unsigned char* sM = lds + (ra_ >= NSLOT ? ra_ - NSLOT : ra_) * Q8_HALF;                                    \
-        const unsigned char* sN = lds + (NSLOT + (rb_ >= NSLOT ? rb_ - NSLOT : rb_)) * Q8_HALF;                          \
-        Q8_PHASE(0, 2, false, FIRST, FIRST);                                                                          \
-        Q8_PHASE(1, 3, false, false, false);                                                                          \
-        Q8_PHASE(2, 0, false, false, false);                                                                          \
-        Q8_PHASE(3, 1, true, false, false);                                                                           \
-        rA = rA + 2 >= NSLOT ? rA + 2 - NSLOT : rA + 2;                                                                  \
-        rB = rB + 2 >= NSLOT ? rB + 2 - NSLOT : rB + 2;                                                                  \
-    } while (0)
-
-    // ---- the lean-stream phase: [load interval: six fragment reads, the part's two DMA instructions, the bookkeeping behind the part,
-    // the waits] barrier [matrix interval: MFMA 0-3, (MX_HOOK: the decode of the next output tile), MFMA 4-7] barrier.  The counted wait
-    // of phase 3 covers K tile t+1: in flight behind it are A_0 / B_0 of K tile t+2 (4 instructions).
 #define Q9_PHASE(KS, DPART, WAIT, ZERO, PRE_HOOK, MX_HOOK)                                                              \
     do {                                                                                                                 \
         if (PRE_HOOK) {                                                                                                  \
@@ -789,9 +704,9 @@ __device__ __forceinline__ void q8_body(const GemmArgs& g, const Q8Group& GR) {
         if (WAIT) Q8_WAIT_DMA(4);                                                                                        \
         if (!A_KC || !B_KC) { q8_wait4(xm); q8_wait2(xn); }                                                              \
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); Q8_SB();                                                      \
-        if (!(DBG & 16)) __builtin_amdgcn_s_barrier();                                                                   \
+        __builtin_amdgcn_s_barrier();                                                                                    \
         Q8_SB();                                                                                                         \
-        if (!(DBG & 8)) __builtin_amdgcn_s_setprio(1);                                                                   \
+        __builtin_amdgcn_s_setprio(1);                                                                                   \
         Q8_MFMA1(xm, xn, 0, ZERO); Q8_MFMA1(xm, xn, 1, ZERO); Q8_SB();                                                   \
         Q8_MFMA1(xm, xn, 2, ZERO); Q8_MFMA1(xm, xn, 3, ZERO); Q8_SB();                                                   \
         if (MX_HOOK) { if (cv + G < total) Q9_CDECODE(cv + G); }                                                           \
@@ -799,9 +714,47 @@ __device__ __forceinline__ void q8_body(const GemmArgs& g, const Q8Group& GR) {
         if (ROWSUM) { Q8_RS_ACC(xm); }   /* no scheduling fence behind it: the compiler spreads these between the MFMAs */ \
         Q8_MFMA1(xm, xn, 4, ZERO); Q8_MFMA1(xm, xn, 5, ZERO); Q8_MFMA1(xm, xn, 6, ZERO); Q8_MFMA1(xm, xn, 7, ZERO);      \
         Q8_SB();                                                                                                         \
-        if (!(DBG & 8)) __builtin_amdgcn_s_setprio(0);                                                                   \
-        if (!(DBG & 16)) __builtin_amdgcn_s_barrier();                                                                   \
+        __builtin_amdgcn_s_setprio(0);                                                                                   \
+        __builtin_amdgcn_s_barrier();                                                                                    \
         Q8_SB();                                                                                                         \
+    } while (0)
+    // the round-3 stream's phase: the part's DMA and ALL of the cursor's bookkeeping in the load interval, nothing between the MFMAs; an
+    // exhausted cursor issues nothing, so its last waits drain the queue
+#define Q8_PHASE(KS, DPART, WAIT, ZERO, PRE_HOOK)                                                                        \
+    do {                                                                                                                 \
+        if (PRE_HOOK) {                                                                                                  \
+            if (have_pend) { Q8_STORE_Q(pm0, pn0, pz, 0); Q8_STORE_Q(pm0, pn0, pz, 1); Q8_STORE_Q(pm0, pn0, pz, 2); Q8_STORE_Q(pm0, pn0, pz, 3); } \
+            bias_request(cn0);                                                                                           \
+            if (ROWSUM) { if (rsp_on) rowsum_flush(); }                                                                  \
+            Q8_SB();                                                                                                     \
+        }                                                                                                                \
+        Q8_READ_GROUP(xm, xn, sM, sN, KS); Q8_SB();                                                                      \
+        Q8_STAGE_PART(DPART); Q8_SB();                                                                                   \
+        if (WAIT) { if (pdone) Q8_WAIT_DMA(0); else Q8_WAIT_DMA(4); }   /* in flight: A_0 and B_0 of K tile t+2 */       \
+        if (!A_KC || !B_KC) { q8_wait4(xm); q8_wait2(xn); }                                                              \
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); Q8_SB();                                                      \
+        __builtin_amdgcn_s_barrier();                                                                                    \
+        Q8_SB();                                                                                                         \
+        __builtin_amdgcn_s_setprio(1);                                                                                   \
+        if (ROWSUM) { Q8_RS_ACC(xm); }   /* no scheduling fence: the compiler spreads these between the MFMAs */          \
+        Q8_MFMA1(xm, xn, 0, ZERO); Q8_MFMA1(xm, xn, 1, ZERO); Q8_MFMA1(xm, xn, 2, ZERO); Q8_MFMA1(xm, xn, 3, ZERO);      \
+        Q8_MFMA1(xm, xn, 4, ZERO); Q8_MFMA1(xm, xn, 5, ZERO); Q8_MFMA1(xm, xn, 6, ZERO); Q8_MFMA1(xm, xn, 7, ZERO);      \
+        Q8_SB();                                                                                                         \
+        __builtin_amdgcn_s_setprio(0);                                                                                   \
+        __builtin_amdgcn_s_barrier();                                                                                    \
+        Q8_SB();                                                                                                         \
+    } while (0)
+#define Q8_KTILE(FIRST)                                                                                                  \
+    do {                                                                                                                 \
+        const int ra_ = rA + wr, rb_ = rB + (wc >> 1);                                                                   \
+        const unsigned char* sM = lds + (ra_ >= NSLOT ? ra_ - NSLOT : ra_) * Q8_HALF;                                    \
+        const unsigned char* sN = lds + (NSLOT + (rb_ >= NSLOT ? rb_ - NSLOT : rb_)) * Q8_HALF;                          \
+        Q8_PHASE(0, 2, false, FIRST, FIRST);                                                                             \
+        Q8_PHASE(1, 3, false, false, false);                                                                             \
+        Q8_PHASE(2, 0, false, false, false);                                                                             \
+        Q8_PHASE(3, 1, true, false, false);                                                                              \
+        rA = rA + 2 >= NSLOT ? rA + 2 - NSLOT : rA + 2;                                                                  \
+        rB = rB + 2 >= NSLOT ? rB + 2 - NSLOT : rB + 2;                                                                  \
     } while (0)
     // ---- the e4m3 phase: k-step KS8 (64 deep) x row half MH of the wave's tile.  MH = 0 also reads the two N-side fragments of the
     // k-step, which stay in registers for MH = 1.  Four MFMAs of 64 matrix-pipe cycles = the bf16 phase's 256.
@@ -867,17 +820,12 @@ __device__ __forceinline__ void q8_body(const GemmArgs& g, const Q8Group& GR) {
         rB = rB + 2 >= NSLOT ? rB + 2 - NSLOT : rB + 2;                                                                  \
     } while (0)
 
-    if (DBG & 512) {   // probe: workgroups start in four phases ~9 us apart (are the lock-step epilogue bursts of a round the cost?)
-        const long long t0 = wall_clock64();   // 100 MHz
-        const long long d = (long long)(blockIdx.x & 3) * 900;
-        while (wall_clock64() - t0 < d) __builtin_amdgcn_s_sleep(8);
-    }
     // prologue: K tile 0 and A_0 / B_0 of K tile 1 issued, K tile 0 landed and published
-    if constexpr (SCH == 0) {
+    if constexpr (ITEMS) {
         Q8_STAGE_PART(0); Q8_STAGE_PART(1); Q8_STAGE_PART(2); Q8_STAGE_PART(3);
         Q8_STAGE_PART(0); Q8_STAGE_PART(1);
     } else {
-        if (!ITEMS) q_cv(false);
+        q_cv(false);
         if (qv < total) Q9_ITEM();
         Q9_ISSUE(0); Q9_ADVANCE(0); Q9_ISSUE(1); Q9_ADVANCE(1); Q9_ISSUE(2); Q9_ADVANCE(2); Q9_ISSUE(3); Q9_ADVANCE(3);
         Q9_ISSUE(0); Q9_ADVANCE(0); Q9_ISSUE(1); Q9_ADVANCE(1);
@@ -885,12 +833,6 @@ __device__ __forceinline__ void q8_body(const GemmArgs& g, const Q8Group& GR) {
     Q8_WAIT_DMA(4);    // in flight: A_0 and B_0 of the second K tile
     __builtin_amdgcn_s_barrier();
     if (wr == 1) __builtin_amdgcn_s_barrier();   // wave row 1 runs one barrier behind (wave row 0 makes up for it at the end)
-    if constexpr ((DBG & 32) != 0 && A_KC && B_KC) {   // timing decomposition: real (random) fragments, read once and never again
-#pragma unroll
-        for (int i = 0; i < 4; ++i) xm[i].v = *reinterpret_cast<const hw_bf16x8*>(lds + offM[0] + i * 4096);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) xn[i].v = *reinterpret_cast<const hw_bf16x8*>(lds + NSLOT * Q8_HALF + offN[0] + i * 4096);
-    }
 
     // ---- main loop over this workgroup's output tiles (every tile has at least two K tiles: the host guarantees K/split >= 128)
     bool have_pend = false;
@@ -900,17 +842,30 @@ __device__ __forceinline__ void q8_body(const GemmArgs& g, const Q8Group& GR) {
     bool nrs = false;
 #define Q9_CDECODE(V_)                                                                                                   \
     do {                                                                                                                 \
-        if (ITEMS) {                                                                                                     \
-            const Q8ItemRec cr = item_at(V_);                                                                            \
-            nm0 = cr.m0; nn0 = cr.prob; nz = cr.slab; ncnt = (cr.kend - cr.kbeg + 63) >> 6;                              \
-            if (ROWSUM) nrs = (cr.flags & 1) != 0 && wc == 0 && Q8_PROB(cr.prob, rowsum) != nullptr;                     \
-        } else {                                                                                                         \
-            const Q8Item cit = q8_decode<KT_SHIFT>(g, V_, total);                                                        \
-            nm0 = cit.m0; nn0 = cit.n0; nz = cit.z; ncnt = cit.nt;                                                       \
-            if (ROWSUM) nrs = g.rowsum != nullptr && wc == 0 && cit.ncol == 0;                                           \
+        const Q8Item cit = q8_decode<KT_SHIFT>(g, V_, total);                                                            \
+        nm0 = cit.m0; nn0 = cit.n0; nz = cit.z; ncnt = cit.nt;                                                           \
+        if (ROWSUM) nrs = g.rowsum != nullptr && wc == 0 && cit.ncol == 0;                                               \
+    } while (0)
+    // an output tile is done: its epilogue and bias-gradient sums wait for the head of the next tile's first phase
+#define Q8_TILE_DONE()                                                                                                   \
+    do {                                                                                                                 \
+        have_pend = true; pm0 = cm0; pn0 = cn0; pz = cz;                                                                 \
+        if (ROWSUM) {                                                                                                    \
+            rsp_on = rs_on; rsp_m0 = cm0; rsp_prob = cn0;                                                                \
+            _Pragma("unroll") for (int t = 0; t < 4; ++t) { rsp[t] = rs[t]; rs[t] = 0.f; }                               \
         }                                                                                                                \
     } while (0)
-    if constexpr (SCH != 0) {
+    if constexpr (ITEMS) {
+        for (int cv = it_beg; cv < total; cv += G) {
+            const Q8ItemRec cr = item_at(cv);
+            const int cm0 = cr.m0, cn0 = cr.prob, cz = cr.slab, cnt = (cr.kend - cr.kbeg + 63) >> 6;   // cn0 carries the problem index and cz the slab index into the epilogue
+            if (ROWSUM) { rs_on = (cr.flags & 1) != 0 && wc == 0 && Q8_PROB(cr.prob, rowsum) != nullptr; rs_ones = rs_on ? H16_ONE_X2 : 0u; }
+            Q8_KTILE(true); bias_landed();
+#pragma unroll 1
+            for (int t = 1; t < cnt; ++t) Q8_KTILE(false);
+            Q8_TILE_DONE();
+        }
+    } else {
         if (it_beg < total) Q9_CDECODE(it_beg);
         for (int cv = it_beg; cv < total; cv += G) {
             const int cm0 = nm0, cn0 = nn0, cz = nz, cnt = ncnt;
@@ -924,35 +879,9 @@ __device__ __forceinline__ void q8_body(const GemmArgs& g, const Q8Group& GR) {
 #pragma unroll 1
                 for (int t = 1; t < cnt; ++t) Q9_KTILE(false);
             }
-            have_pend = true; pm0 = cm0; pn0 = cn0; pz = cz;
-            if (ROWSUM) {
-                rsp_on = rs_on; rsp_m0 = cm0; rsp_prob = cn0;
-#pragma unroll
-                for (int t = 0; t < 4; ++t) { rsp[t] = rs[t]; rs[t] = 0.f; }
-            }
+            Q8_TILE_DONE();
         }
         Q8_WAIT_DMA(0);   // the zero-length loads an exhausted stream keeps issuing still write their (zero) pieces into this workgroup's LDS
-    } else
-    for (int cv = it_beg; cv < total; cv += G) {
-        int cm0, cn0, cz, cnt;   // ITEMS: cn0 carries the problem index and cz the slab index into the epilogue
-        if (ITEMS) {
-            const Q8ItemRec cr = item_at(cv);
-            cm0 = cr.m0; cn0 = cr.prob; cz = cr.slab; cnt = (cr.kend - cr.kbeg + 63) >> 6;
-            if (ROWSUM) { rs_on = (cr.flags & 1) != 0 && wc == 0 && Q8_PROB(cr.prob, rowsum) != nullptr; rs_ones = rs_on ? H16_ONE_X2 : 0u; }
-        } else {
-            const Q8Item cit = q8_decode(g, cv, total);
-            cm0 = cit.m0; cn0 = cit.n0; cz = cit.z; cnt = cit.nt;
-            if (ROWSUM) { rs_on = g.rowsum != nullptr && wc == 0 && cit.ncol == 0; rs_ones = rs_on ? H16_ONE_X2 : 0u; }
-        }
-        Q8_KTILE(true); bias_landed();
-#pragma unroll 1
-        for (int t = 1; t < cnt; ++t) Q8_KTILE(false);
-        have_pend = true; pm0 = cm0; pn0 = cn0; pz = cz;
-        if (ROWSUM) {
-            rsp_on = rs_on; rsp_m0 = cm0; rsp_prob = cn0;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) { rsp[t] = rs[t]; rs[t] = 0.f; }
-        }
     }
     if (wr == 0) __builtin_amdgcn_s_barrier();   // wave row 0's share of the row lag
     if (have_pend) { Q8_STORE_Q(pm0, pn0, pz, 0); Q8_STORE_Q(pm0, pn0, pz, 1); Q8_STORE_Q(pm0, pn0, pz, 2); Q8_STORE_Q(pm0, pn0, pz, 3); }
@@ -967,11 +896,12 @@ __device__ __forceinline__ void q8_body(const GemmArgs& g, const Q8Group& GR) {
 #undef Q8_READ_GROUP
 #undef Q8_MFMA1
 #undef Q8_RD1
-#undef Q8_STAGE_PART
-#undef Q8_STAGE_PCS
 #undef Q8_RS_ACC
 #undef Q8_KTILE
 #undef Q8_PHASE
+#undef Q8_STAGE_PART
+#undef Q8_NEXT_ITEM
+#undef Q8_TILE_DONE
 #undef Q9_KTILE
 #undef Q9F_KTILE
 #undef Q9F_PHASE
@@ -981,25 +911,24 @@ __device__ __forceinline__ void q8_body(const GemmArgs& g, const Q8Group& GR) {
 #undef Q9_ADVANCE
 #undef Q9_ITEM
 #undef Q9_CDECODE
-#undef Q8_NEXT_ITEM
 #undef Q8_WAIT_DMA
 }
 #undef Q8_PROB
 #undef Q8_VAL_
 
-template <bool A_KC, bool B_KC, int EPI, int DBG = 0, bool ROWSUM = false, int SCH = 0>
+template <bool A_KC, bool B_KC, int EPI, int DBG = 0, bool ROWSUM = false>
 __global__ __launch_bounds__(512) void gemm_bf16_q8_kernel(GemmArgs g) {
     Q8Group none;   // never read in this form
-    q8_body<A_KC, B_KC, EPI, DBG, ROWSUM, false, SCH>(g, none);
+    q8_body<A_KC, B_KC, EPI, DBG, ROWSUM, false>(g, none);
 }
 // e4m3 forward form (per-tensor scales in g.alpha_dev / g.alpha_dev2)
 template <int EPI>
 __global__ __launch_bounds__(512) void gemm_f8_q8_kernel(GemmArgs g) {
     Q8Group none;
-    q8_body<true, true, EPI, 0, false, false, 1, true>(g, none);
+    q8_body<true, true, EPI, 0, false, false, true>(g, none);
 }
 // grouped weight gradients: `g` only supplies the fields the item-table form does not take from the group (none of the operands)
-template <bool ROWSUM, int SCH = 0>
+template <bool ROWSUM>
 __global__ __launch_bounds__(512) void gemm_bf16_q8_items_kernel(GemmArgs g, Q8Group GR) {
-    q8_body<false, false, 4, 0, ROWSUM, true, SCH>(g, GR);
+    q8_body<false, false, 4, 0, ROWSUM, true>(g, GR);
 }

@@ -4,9 +4,8 @@
 #include <limits.h>
 
 enum EcampOpt {
-    OPT_Q8_MODE, OPT_Q8_SCH, OPT_Q16_MODE, OPT_Q16_WGRAD, OPT_F8_Q8, OPT_Q8_MIN_ITEMS, OPT_Q8_BWD_GRID, OPT_P8_WGRAD, OPT_P8_WGRAD_RESERVE,
-    OPT_WGRAD_ITEMS, OPT_WGRAD_PLAN, OPT_WGRAD_GROUP_CUS, OPT_GEMM_GRID_CAP, OPT_ATTN_HEAD, OPT_ATTN_WAVES, OPT_LN_BWD, OPT_CE_KERNEL,
-    OPT_SR_BLOCKS, OPT_COUNT
+    OPT_Q8_MODE, OPT_Q16_MODE, OPT_Q16_WGRAD, OPT_F8_Q8, OPT_Q8_MIN_ITEMS, OPT_Q8_BWD_GRID, OPT_P8_WGRAD, OPT_P8_WGRAD_RESERVE,
+    OPT_WGRAD_ITEMS, OPT_WGRAD_GROUP_CUS, OPT_GEMM_GRID_CAP, OPT_ATTN_HEAD, OPT_ATTN_WAVES, OPT_LN_BWD, OPT_SR_BLOCKS, OPT_COUNT
 };
 #define OPT_ENV INT_MIN    // result of a value rule: forget the explicit value, the environment (or the default) decides again
 #define OPT_AUTO INT_MIN   // default of a switch whose default depends on the device (the reader derives it)

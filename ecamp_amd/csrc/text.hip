@@ -302,87 +302,16 @@ __global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(T* __restrict__ logits,
         st4<T>(x + c * 4, p);
     }
 }
-// bf16 rows of up to 32768 logits: the row is read ONCE into registers (16 B per lane per load, NG loads per thread) and the
-// gradient is written from them -- the two-pass kernel above reads every logit twice (2 GB per pass at B*S = 32768, V = 30000).
-template <int NG>
-__global__ __launch_bounds__(256) void ce_fwd_bwd_reg_kernel(bf16_t* __restrict__ logits, const long* __restrict__ labels,
-                                                             const float* __restrict__ weights, float* __restrict__ loss_sum, int V,
-                                                             long ld, float inv_count) {
-    __shared__ float shm_[8];
-    const long row = blockIdx.x;
-    bf16_t* x = logits + row * ld;
-    const int nv8 = V >> 3;
-    uint4 q[NG];
-    float mx = -INFINITY, sm = 0.f;
-#pragma unroll
-    for (int j = 0; j < NG; ++j) {
-        const int c = threadIdx.x + 256 * j;
-        if (c < nv8) {
-            q[j] = *reinterpret_cast<const uint4*>(x + c * 8);
-            const uint32_t w[4] = {q[j].x, q[j].y, q[j].z, q[j].w};
-            float p[8];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                p[2 * r] = h16_lo(w[r]);
-                p[2 * r + 1] = h16_hi(w[r]);
-            }
-            const float m8 = fmaxf(fmaxf(fmaxf(p[0], p[1]), fmaxf(p[2], p[3])), fmaxf(fmaxf(p[4], p[5]), fmaxf(p[6], p[7])));
-            if (m8 > mx) {
-                sm *= __expf(mx - m8);
-                mx = m8;
-            }
-#pragma unroll
-            for (int r = 0; r < 8; ++r) sm += __expf(p[r] - mx);
-        }
-    }
-    float wm = wave_max(mx);
-    sm = mx == -INFINITY ? 0.f : sm * __expf(mx - wm);   // a lane (or a whole wave) without elements: exp(-inf + inf) would be NaN
-    sm = wave_sum(sm);
-    if ((threadIdx.x & 63) == 0) {
-        shm_[threadIdx.x >> 6] = wm;
-        shm_[4 + (threadIdx.x >> 6)] = sm;
-    }
-    __syncthreads();
-    const float gmx = fmaxf(fmaxf(shm_[0], shm_[1]), fmaxf(shm_[2], shm_[3]));
-    float gsm = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) gsm += shm_[k] == -INFINITY ? 0.f : shm_[4 + k] * __expf(shm_[k] - gmx);
-    const long label = labels[row];
-    const bool ign = label < 0 || label >= (long)V;   // ignore_index (see the generic kernel)
-    const float w = ign ? 0.f : weights[row];
-    if (threadIdx.x == 0 && !ign) {
-        float lse = gmx + __logf(gsm);
-        atomicAdd(loss_sum, w * (lse - to_f<bf16_t>(x[label])));
-    }
-    const float inv = 1.0f / gsm, sc = w * inv_count;
-    __syncthreads();   // thread 0 has read x[label] before anyone overwrites it
-#pragma unroll
-    for (int j = 0; j < NG; ++j) {
-        const int c = threadIdx.x + 256 * j;
-        if (c < nv8) {
-            const uint32_t wq[4] = {q[j].x, q[j].y, q[j].z, q[j].w};
-            float g[8];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                g[2 * r] = h16_lo(wq[r]);
-                g[2 * r + 1] = h16_hi(wq[r]);
-            }
-#pragma unroll
-            for (int r = 0; r < 8; ++r) g[r] = sc * (__expf(g[r] - gmx) * inv - ((long)(c * 8 + r) == label ? 1.0f : 0.0f));
-            uint4 o;
-            o.x = pack_bf16x2(g[0], g[1]); o.y = pack_bf16x2(g[2], g[3]); o.z = pack_bf16x2(g[4], g[5]); o.w = pack_bf16x2(g[6], g[7]);
-            *reinterpret_cast<uint4*>(x + c * 8) = o;
-        }
-    }
-}
-// Round 5: the same row-in-registers pass in THREE phases with ONE exp per logit (the kernel above evaluates two and rescales a running
-// sum whenever its maximum moves: ~570 us of VALU time per 1.97 GB of logits against the ~500 us a pure read + write of them takes,
-// profiles/r05_vocab_head.txt).  NT threads per row, NG 16-B loads per thread (V <= 8 NG NT):
+// bf16 rows of up to 32768 logits: the row is read ONCE into registers (16 B per lane per load) and the gradient is written from them --
+// the two-pass kernel above reads every logit twice (2 GB per pass at B*S = 32768, V = 30000).  THREE phases with ONE exp per logit (a
+// single pass that evaluates two and rescales a running sum whenever its maximum moves spends ~570 us of VALU time per 1.97 GB of logits
+// against the ~500 us a pure read + write of them takes, profiles/r05_vocab_head.txt).  NT threads per row, NG 16-B loads per thread
+// (V <= 8 NG NT):
 //   1  load the row, maximum                                        -> block maximum
 //   2  e = exp(x - max) kept in f32 registers over the loaded row, sum  -> block sum
 //   3  d = e * (w / (M sum)), minus w / M at the label, packed, stored over the logits
 // Lanes past the row hold -inf: they drop out of the maximum and add exp(-inf) = 0.  Measured directly behind the vocabulary GEMM
-// (tools/vocab_head_probe.py, V = 30000): two-exp kernel 1.33x the time of an in-place multiply over the same bytes, this one with 512
+// (tools/vocab_head_probe.py, V = 30000): the two-exp single pass 1.33x the time of an in-place multiply over the same bytes, this one with 512
 // threads x 8 loads 1.25x, with 1024 x 4 (one row's 120 KB of e spread over all sixteen waves a CU's SIMDs take at 66 registers) 1.20-1.23x;
 // forms that keep the row packed and evaluate exp twice (fewer registers, more rows per CU) 1.25-1.33x.
 template <int NG, int NT>
@@ -467,15 +396,9 @@ extern "C" int ecamp_ce_fwd_bwd(void* logits, const int64_t* labels, const float
     if (M == 0) return 0;
     dim3 grid((unsigned)M), block(256);
     if (dtype == ECAMP_BF16 && V % 8 == 0 && ld % 8 == 0 && V <= 32768 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0) {
-        const int ce_variant = ecamp_opt(OPT_CE_KERNEL);   // development A/B: 0 = the two-exp kernel of round 2
-        if (ce_variant == 0) {
-            if (V <= 16384) hipLaunchKernelGGL(ce_fwd_bwd_reg_kernel<8>, grid, block, 0, stream, (bf16_t*)logits, (const long*)labels, weights, loss_sum, V, (long)ld, inv_count);
-            else hipLaunchKernelGGL(ce_fwd_bwd_reg_kernel<16>, grid, block, 0, stream, (bf16_t*)logits, (const long*)labels, weights, loss_sum, V, (long)ld, inv_count);
-        } else {
 #define CE_ROW(NG_, NT_) hipLaunchKernelGGL((ce_fwd_bwd_row_kernel<NG_, NT_>), grid, dim3(NT_), 0, stream, (bf16_t*)logits, (const long*)labels, weights, loss_sum, V, (long)ld, inv_count)
-            if (V <= 4096) CE_ROW(1, 512); else if (V <= 8192) CE_ROW(2, 512); else if (V <= 16384) CE_ROW(4, 512); else CE_ROW(4, 1024);
+        if (V <= 4096) CE_ROW(1, 512); else if (V <= 8192) CE_ROW(2, 512); else if (V <= 16384) CE_ROW(4, 512); else CE_ROW(4, 1024);
 #undef CE_ROW
-        }
         ECAMP_LAUNCH_CHECK();
         return 0;
     }

@@ -115,8 +115,6 @@ int ecamp_set_option(const char* name, int32_t value);
 /* "q8_mode" (env ECAMP_GEMM_Q8): -1 automatic (default), 0 never, 2 whenever its alignment / size conditions hold -- the
  * persistent 256x256x64 kernel (csrc/gemm_q8.h) that serves the forward, data-gradient and weight-gradient forms.  Any other value
  * means -1; once this option has been set the environment variable is no longer consulted.
- * "q8_sch" (env ECAMP_Q8_SCH, default 7): development A/B mask -- bits 0 / 1 / 2 put the forward / data-gradient / weight-gradient
- * forms of that kernel on the lean operand stream, bit 3 the grouped weight gradients; negative back to the environment.
  * "q16_mode" (env ECAMP_Q16): the four-wave v_mfma_f32_16x16x32_bf16 kernel (csrc/gemm_q16.h; forward and data-gradient forms
  * with a plain / bias / residual epilogue, 256 x 256 or 256 x 192 tiles).  0 never; 1 (default) where the 192-column tile removes idle
  * last-round time -- the model's 768-wide outputs; 2 every eligible call; 3 as 2 whatever the size (tests); any other value back to

@@ -60,7 +60,6 @@ CE_OFFSET = 256.0      # the common offset of row 10: a power of two, exact in e
 V_REG = [8, 4096, 4104, 8192, 8200, 16384, 16392, 30000, 32768]     # 16-bit rows the register form takes: both sides of every rung
 V_GENERIC = [4, 30004, 32776]                                       # 16-bit rows it refuses: V % 8 != 0, V > 32768
 V_F32 = [4, 1020, 4100, 30000]
-V_TWO_EXP = [8, 16384, 16392, 32768]                                # ce_fwd_bwd_reg_kernel<8> up to 16384, <16> above
 
 
 def ce_kernel_of(V, fmt, ld=None, aligned=True):

@@ -15,8 +15,8 @@ Every call
   * prints K_yard, Kacc and its worst err / bound (profiles/gemm_float64.txt is one run's output).
 No element is left out of any judgement.
 
-Out of scope: the e4m3 GEMM; the grouped weight-gradient launch (tests/test_gemm_q16_wgrad_gpu.py); the q8_sch = 0 operand stream; the
-2 GB split paths; subnormal operands."""
+Out of scope: the e4m3 GEMM; the grouped weight-gradient launch (tests/test_gemm_q16_wgrad_gpu.py); the 2 GB split paths;
+subnormal operands."""
 import ctypes
 
 import pytest

@@ -59,7 +59,6 @@ def test_cross_entropy_cases_reach_every_dispatch_branch():
     assert {R.ce_kernel_of(V, R.F32) for V in R.V_F32} == {"generic<f32>"}
     assert R.ce_kernel_of(4096, R.BF16, ld=4104) == "row<1,512>" and R.ce_kernel_of(4096, R.BF16, ld=4100) == "generic<16>"
     assert R.ce_kernel_of(30000, R.BF16, ld=30004) == "generic<16>" and R.ce_kernel_of(4096, R.BF16, aligned=False) == "generic<16>"
-    assert all(V % 8 == 0 and V <= 32768 for V in R.V_TWO_EXP) and min(R.V_TWO_EXP) <= 16384 < max(R.V_TWO_EXP)
 
 
 def test_float32_chain_rounds_after_every_addition():

@@ -39,10 +39,9 @@ static void fill_bf16(unsigned short* d, size_t n, float scale) {
 typedef void (*q8_fn)(GemmArgs);
 // epi: 0 plain(+bias) 1 bias+pre+gelu 2 +residual 3 gmul 4 f32.  dbg variants only exist for the forward form.
 static int g_zero = 0;
-static int g_sch = 0;   // schedule variant of the launches that follow (gemm_q8.h SCH)
+static int g_sch = 1;   // kernel of the launches that follow: 1 the eight-wave product kernel (gemm_q8.h), 4 / 5 gemm_q4.h, 16 / 12 gemm_q16.h
 static q8_fn pick(int a_kc, int b_kc, int epi, int nslot, int dbg) {
     (void)nslot;
-#define W(A, B, E, S) ((q8_fn)gemm_bf16_q8_kernel<A, B, E, 0, false, S>)
     if (g_sch == 16 || g_sch == 12) {   // four waves on the 16 x 16 x 32 MFMA (csrc/gemm_q16.h): 256- (16) or 192-column (12) tiles; forward and data-gradient forms, plain / bias / residual
         if (!a_kc) return nullptr;
         if (dbg == 8) {   // data-gradient form with conflict-free (wrong) transpose-read addresses: the price of the 2-way bank meeting
@@ -86,28 +85,16 @@ static q8_fn pick(int a_kc, int b_kc, int epi, int nslot, int dbg) {
         }
         return nullptr;
     }
-    if (g_sch == 1) {
-        if (dbg == 4 || dbg == 1024) {   // the epilogue's cost split: 4 = no epilogue at all, 1024 = its arithmetic and instructions, every store dropped
-            if (!(a_kc && b_kc)) return nullptr;
-            if (epi == 0) return dbg == 4 ? (q8_fn)gemm_bf16_q8_kernel<true, true, 0, 4, false, 1> : (q8_fn)gemm_bf16_q8_kernel<true, true, 0, 1024, false, 1>;
-            if (epi == 1) return dbg == 4 ? (q8_fn)gemm_bf16_q8_kernel<true, true, 1, 4, false, 1> : (q8_fn)gemm_bf16_q8_kernel<true, true, 1, 1024, false, 1>;
-            return nullptr;
-        }
-        if (dbg != 0) return nullptr;
-#define WS(A, B, E) W(A, B, E, 1)
-        if (a_kc && b_kc) { if (epi == 0) return WS(true, true, 0); if (epi == 1) return WS(true, true, 1); if (epi == 2) return WS(true, true, 2); }
-        if (a_kc && !b_kc) { if (epi == 0) return WS(true, false, 0); if (epi == 3) return WS(true, false, 3); if (epi == 2) return WS(true, false, 2); }
-        if (!a_kc && !b_kc && epi == 4) return WS(false, false, 4);
-#undef WS
-        return nullptr;
-    }
-#undef W
+    if (g_sch != 1) return nullptr;
+    // timing decomposition (forward form; results are garbage): 4 = no epilogue at all, 1024 = its arithmetic and instructions with every
+    // store dropped, 5 = no MFMA and no epilogue, 6 = no DMA and no epilogue
 #define V(A, B, E, D) ((q8_fn)gemm_bf16_q8_kernel<A, B, E, D>)
     if (a_kc && b_kc) {
-        if (epi == 1) { if (dbg == 4) return V(true, true, 1, 4); if (dbg == 6) return V(true, true, 1, 6); return V(true, true, 1, 0); }
-        if (epi == 0) { if (dbg == 4) return V(true, true, 0, 4); if (dbg == 6) return V(true, true, 0, 6); if (dbg == 5) return V(true, true, 0, 5); return V(true, true, 0, 0); }
-        if (epi == 2) return V(true, true, 2, 0);
+        if (epi == 1) { if (dbg == 4) return V(true, true, 1, 4); if (dbg == 6) return V(true, true, 1, 6); if (dbg == 1024) return V(true, true, 1, 1024); }
+        if (epi == 0) { if (dbg == 4) return V(true, true, 0, 4); if (dbg == 6) return V(true, true, 0, 6); if (dbg == 5) return V(true, true, 0, 5); if (dbg == 1024) return V(true, true, 0, 1024); }
     }
+    if (dbg != 0) return nullptr;
+    if (a_kc && b_kc) { if (epi == 0) return V(true, true, 0, 0); if (epi == 1) return V(true, true, 1, 0); if (epi == 2) return V(true, true, 2, 0); }
     if (a_kc && !b_kc) { if (epi == 0) return V(true, false, 0, 0); if (epi == 3) return V(true, false, 3, 0); if (epi == 2) return V(true, false, 2, 0); }
     if (!a_kc && !b_kc && epi == 4) return V(false, false, 4, 0);
 #undef V
@@ -210,7 +197,7 @@ int main(int argc, char** argv) {
     int forms = 7;        // bit0 fwd, bit1 dgrad, bit2 wgrad
     bool quick = false;
     std::vector<int> dbgs = {0};
-    std::vector<int> nslots = {0};   // the list of schedule variants to run (--sch=0,1,2); the name is historical
+    std::vector<int> nslots = {1};   // the list of kernels to run (--sch=1,4,16: see g_sch); the name is historical
     int grid_override = 0, stress = 0, hog = 0, plain_only = 0;   // --hog: a small spinning kernel on a second stream beside every launch (uneven load)
     for (int i = 1; i < argc; ++i) {
         if (!strncmp(argv[i], "--stress=", 9)) { stress = atoi(argv[i] + 9); continue; }
@@ -279,7 +266,7 @@ int main(int argc, char** argv) {
             for (int ns : nslots)
                 for (int dbg : dbgs) {
                     if (plain_only) continue;
-                    if (ns != 0 && ns != 4 && ns != 1 && dbg != 0) continue;
+                    if (ns != 4 && ns != 1 && dbg != 0) continue;
                     if (ns == 16 || ns == 12) continue;   // no GELU epilogue in the 16 x 16 x 32 lab kernel
                     CK(hipMemsetAsync(y1, 0xff, (size_t)M * N * 2, s));
                     launch_q8(q, ns, dbg, grid_override, s);
@@ -295,7 +282,7 @@ int main(int argc, char** argv) {
             launch_ref(r2, 0, s);
             for (int ns : nslots)
             for (int dbg : dbgs) {
-                if (ns != 0 && ns != 4 && ns != 1 && ns != 16 && dbg != 0) continue;
+                if (ns != 4 && ns != 1 && ns != 16 && dbg != 0) continue;
                 CK(hipMemsetAsync(y1, 0xff, (size_t)M * N * 2, s));
                 launch_q8(q2, ns, dbg, grid_override, s);
                 CK(hipStreamSynchronize(s));
